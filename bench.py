@@ -24,6 +24,11 @@ a child `python -m torch.distributed.run` BEFORE anything touches the GPU and ex
 configs[3] is `--gpus 8 --workload chair` / `table`: the catalog is embedded in voxel-count-balanced
 shards and all-gathered once (setup, reported as catalog_embed_s); queries are sharded with a fixed
 per-GPU count ("weak"); the timed region contains no collective.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps of the pass that gives `value` and prints the line.  --full adds what
+the line carried before that split: the sequential pass next to the batches-in-flight pass (results compared), the
+roofline and per-kernel figures, the stand-alone prefilter probe, the table / stress / converging legs of a chair run
+and the CPU baseline.  --dump-outputs DIR writes the arrays the last timed step returned as DIR/<name>.npy (rank 0).
 """
 import argparse
 import gc
@@ -112,6 +117,14 @@ def parse():
                          "average, but one run in four shows a 0.5-s stall somewhere -- DESIGN 7)")
     ap.add_argument("--no-overlap-probe", action="store_true",
                     help="skip the extra pass with three batches in flight reported as `batches_in_flight`")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline as well: the sequential pass next to the batches-in-flight pass "
+                         "(results compared), roofline / per-kernel figures, the stand-alone prefilter probe, the table / "
+                         "stress / converging legs and the CPU baseline.  Without it a run times only the pass that gives "
+                         "`value`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0) as DIR/<name>.npy, "
+                         "float32 / float64")
     return ap.parse_args()
 
 
@@ -360,6 +373,7 @@ class RegistrationWorkload:
         self.sym = sym_labels(kind, self.C)
         self.results = []
         self.units_per_step = BATCH
+        self.last_step, self.last_out = ctx.args.warmup + ctx.args.steps - 1, None
 
     def setup(self):
         import torch
@@ -497,6 +511,9 @@ class RegistrationWorkload:
         res = pipe.register(qs, cads, self.sym[top], anchor_ids=ids, force_gate=True, query_anchors=q_anc)
         Tb, Tr, cdb, its = _lib.to_host(res.T_best, res.T_ransac, res.cd_best, res.iters)
         self.results.append((b, top, Tb, Tr, cdb, res.ok, its, res.n_problems))
+        if b == self.last_step:     # --dump-outputs: what a caller of the path receives for these 32 queries
+            self.last_out = {"query_desc": qs.desc, "top1_cad": top, "T_best": Tb, "cd_best": cdb, "T_ransac": Tr,
+                             "cd_ransac": res.cd_ransac, "sym_success": res.ok, "ransac_iters": its}
 
     def same_results(self, a, b):
         return np.array_equal(a[2], b[2]) and np.array_equal(a[6], b[6])
@@ -641,6 +658,7 @@ class StrongEvalWorkload:
         self.sym = sym_labels(kind, self.C)
         self.results = []
         self.units_per_step = self.Q          # of the WHOLE job (all ranks together)
+        self.last_step, self.last_out = ctx.args.warmup + ctx.args.steps - 1, None
 
     def setup(self):
         import torch
@@ -674,6 +692,8 @@ class StrongEvalWorkload:
                                         self.best_match, self.table, np.stack(self.q_T), self.lib_T, self.sym, self.kind,
                                         True, None, True, None, 3)   # three registration batches in flight per rank
         self.results.append((b, res))
+        if b == self.last_step:
+            self.last_out = dict(res.per_query)
 
     def same_results(self, a, b):
         return all(np.array_equal(a[1].per_query[k], b[1].per_query[k]) for k in a[1].per_query)
@@ -721,6 +741,7 @@ class StressWorkload:
         self.results = []
         self.voxels = 0
         self.clouds = 0
+        self.last_step, self.last_out = ctx.args.warmup + ctx.args.steps - 1, None
 
     def setup(self):
         import torch
@@ -781,6 +802,8 @@ class StressWorkload:
             idx, _ = sharding.sharded_topk(self.ctx.dist, qs, lambda qq: B.l2_topk(qq, self.xcat, 10, True, squared=True),
                                            self.shard[0], 10, self.ctx.rank, self.ctx.world)
         self.results.append((b, idx[:64].cpu().numpy(), last.desc[:4].cpu().numpy()))
+        if b == self.last_step:     # the step's 10 240 top-10 lists and the descriptors of its last forward batch
+            self.last_out = {"topk_ids": idx, "desc_last_batch": last.desc}
 
     def same_results(self, a, b):
         return np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2])
@@ -1053,6 +1076,31 @@ class Runner:
         """(the shared workers live until the process ends: see above)"""
 
 
+def bracketed(ctx, runner, first, last, depth=None):
+    """Steps [first, last) bracketed by barrier + torch.cuda.synchronize() on both sides: the bracket of every timed pass
+    (timed_region, piped_pass, in_flight_region).  Everything allocated so far (the catalog, K + W batches of query clouds,
+    the network) is long-lived: moved to the permanent generation so that a full collection of Python's cycle collector
+    inside the region does not walk it (measured: 10 - 50 ms pauses in some steps of a 20-step run, 1 360 vs 1 485 q/s;
+    BENCH_GC=1 keeps the default).  Thawed again right after the region: a leg's workload must be collectable
+    before the next leg starts.  Returns (barrier-to-barrier seconds, this rank's own seconds)."""
+    frozen = os.environ.get("BENCH_GC", "freeze") == "freeze"
+    if frozen:
+        gc.collect()
+        gc.freeze()
+    try:
+        ctx.barrier()
+        t_start = time.time()
+        runner.run_steps(first, last, depth=depth)
+        ctx.sync()
+        own_elapsed = time.time() - t_start
+        ctx.barrier()
+        elapsed = time.time() - t_start
+    finally:
+        if frozen:
+            gc.unfreeze()
+    return elapsed, own_elapsed
+
+
 def timed_region(ctx, wl, runner, warmup, steps):
     """The contract's measurement: W untimed warmup steps, then EXACTLY K steps bracketed by barrier +
     torch.cuda.synchronize() on both sides, the library's HIP-event profile (events on the launch streams) switched on
@@ -1067,25 +1115,7 @@ def timed_region(ctx, wl, runner, warmup, steps):
     if not ctx.dry:
         _lib.prof_enable(True)
         _lib.prof_reset()
-    # Everything allocated so far (the catalog, K + W batches of query clouds, the network) is long-lived: moved to the
-    # permanent generation so that a full collection of Python's cycle collector inside the timed region does not walk it
-    # (measured: 10 - 50 ms pauses in some steps of a 20-step run, 1 360 vs 1 485 q/s; BENCH_GC=1 keeps the default).
-    # Thawed again right after the region: a leg's workload must be collectable before the next leg starts.
-    frozen = os.environ.get("BENCH_GC", "freeze") == "freeze"
-    if frozen:
-        gc.collect()
-        gc.freeze()
-    try:
-        ctx.barrier()
-        t_start = time.time()
-        runner.run_steps(warmup, warmup + steps)
-        ctx.sync()
-        own_elapsed = time.time() - t_start
-        ctx.barrier()
-        elapsed = time.time() - t_start
-    finally:
-        if frozen:
-            gc.unfreeze()
+    elapsed, own_elapsed = bracketed(ctx, runner, warmup, warmup + steps)
     fam = {}
     if not ctx.dry:
         _lib.prof_enable(False)
@@ -1103,22 +1133,56 @@ def piped_pass(ctx, wl, runner, warmup, steps):
     seq_results = {r[0]: r for r in wl.results}
     runner.run_steps(0, min(IN_FLIGHT[0], warmup + steps), depth=IN_FLIGHT[0])   # untimed: every worker's first step (cold scratch)
     wl.results.clear()
-    frozen = os.environ.get("BENCH_GC", "freeze") == "freeze"
-    if frozen:
-        gc.collect()
-        gc.freeze()
-    try:
-        ctx.barrier()
-        t2 = time.time()
-        runner.run_steps(warmup, warmup + steps, depth=IN_FLIGHT[0])
-        ctx.barrier()
-        piped_elapsed = time.time() - t2
-    finally:
-        if frozen:
-            gc.unfreeze()
+    piped_elapsed, _ = bracketed(ctx, runner, warmup, warmup + steps, depth=IN_FLIGHT[0])
     same = len(wl.results) == len(seq_results) and all(wl.same_results(r, seq_results[r[0]]) for r in wl.results)
     wl.results[:] = [seq_results[b] for b in sorted(seq_results)]
     return piped_elapsed, same
+
+
+def in_flight_warmup_steps(warmup, steps, depth, group):
+    """Untimed steps [0, n) in front of in_flight_region: the W warmup steps, and never fewer than one step per worker
+    (no worker meets its cold scratch and streams inside the region) or one whole embed group (the first forward of a
+    group as large as the timed ones runs before the region); at most W + K."""
+    return min(warmup + steps, max(warmup, depth, group))
+
+
+def in_flight_region(ctx, wl, runner, warmup, steps):
+    """A run without --full whose `value` comes from the batches-in-flight pass times that pass alone: the untimed
+    in_flight_warmup_steps with IN_FLIGHT batches in flight, then EXACTLY K steps in the bracket of every timed pass.
+    Unlike --full, nothing compares this pass's results with the sequential pass (`batches_in_flight.identical_results`
+    of a --full run does).  Returns (barrier-to-barrier seconds, this rank's own seconds)."""
+    depth = IN_FLIGHT[0]
+    group = runner.group if hasattr(wl, "step_group") else 1
+    runner.run_steps(0, in_flight_warmup_steps(warmup, steps, depth, group), depth=depth)
+    ctx.log("warmup done")
+    wl.results.clear()
+    elapsed, own_elapsed = bracketed(ctx, runner, warmup, warmup + steps, depth=depth)
+    ctx.log("timed region: %d steps in %.3fs, %d batches in flight" % (steps, elapsed, depth))
+    wl.results.sort(key=lambda r: r[0])       # the workers finish their steps in any order
+    return elapsed, own_elapsed
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(wl, out_dir):
+    """--dump-outputs: the arrays the last timed step returned, one DIR/<name>.npy each -- floating point as float32 /
+    float64, ids, counts and flags as float64 (exact below 2^53).  An array that would take the files past 64 MB in all
+    is cut to a fixed sample of its rows (seed 0, rows in order)."""
+    if wl.last_out is None:
+        raise RuntimeError("--dump-outputs: the last timed step recorded no outputs")
+    arrays = {}
+    for name, v in wl.last_out.items():
+        a = v.detach().cpu().numpy() if hasattr(v, "detach") else np.asarray(v)
+        arrays[name] = a.astype(np.float32 if a.dtype in (np.float16, np.float32) else np.float64)
+    share = DUMP_LIMIT_BYTES // max(len(arrays), 1)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if a.nbytes > share and a.ndim > 0:
+            keep = max(1, share // max(a.nbytes // max(len(a), 1), 1))
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
 
 
 def overlap_probe_allowed(depth, steps, disabled, world, wl):
@@ -1233,6 +1297,7 @@ class DryWorkload:
 
     def __init__(self, ctx):
         self.ctx, self.results, self.units_per_step = ctx, [], BATCH
+        self.last_step, self.last_out = ctx.args.warmup + ctx.args.steps - 1, None
 
     def setup(self):
         import torch
@@ -1257,7 +1322,10 @@ class DryWorkload:
         assert [float(v) for v in self.catalog.desc[:, 0]] == [float(c) for c in range(C)]
 
     def step(self, b):
-        self.results.append((b, float(np.sin(b + self.ctx.rank))))
+        v = float(np.sin(b + self.ctx.rank))
+        self.results.append((b, v))
+        if b == self.last_step:
+            self.last_out = {"step_value": np.float64(v)}
 
     def same_results(self, a, b):
         return a == b
@@ -1315,44 +1383,52 @@ def main():
         sys.exit(2)
     runner = Runner(ctx, wl, depth)
     run_steps = runner.run_steps
-    elapsed, own_elapsed, fam = timed_region(ctx, wl, runner, args.warmup, args.steps)
-    # In the timed region the prefilter launches of a step overlap other work (the vanilla and the
-    # symmetric RANSAC calls run on two host threads, the small kernels of a round run under the next
-    # prefilter), so their event-bracketed durations include the share of the GPU they did not have.
-    # A short extra pass with both overlaps switched off gives the kernel's stand-alone rate (same inputs,
-    # same launches merged back into one call); reported as roofline.solo, not used for `value`.
-    solo = None
-    if ctx.world == 1 and not args.no_solo_probe and args.steps >= 1 and wl.solo_env():
-        env = wl.solo_env()
-        saved = {k: os.environ.get(k) for k in env}
-        os.environ.update(env)
-        try:
-            keep = list(wl.results)
-            _lib.prof_reset()
-            _lib.prof_enable(True)
-            run_steps(args.warmup, args.warmup + min(2, args.steps), depth=1)
-            torch.cuda.synchronize()
-            _lib.prof_enable(False)
-            ms, n, units = _lib.prof_get("ransac_pre")
-            solo = {"ms": ms, "launches": n, "flop": units}
-            wl.results[:] = keep
-        finally:
-            for k, v in saved.items():
-                if v is None:
-                    os.environ.pop(k, None)
-                else:
-                    os.environ[k] = v
-        ctx.log("stand-alone prefilter pass done")
-    # Throughput mode, reported next to the contract number (never instead of it): the same K batches
-    # again with three of them in flight.  Kernels of the two streams share the GPU, so per-launch event
-    # times are not a roofline measurement there; profiling stays off.  The results must come out
-    # identical to the sequential pass.
-    overlap = None
-    # (not with a collective inside the step on several ranks: the worker threads of a rank would issue their
-    # all-gathers in an order of their own and the ranks' collectives would no longer pair up)
-    if overlap_probe_allowed(depth, args.steps, args.no_overlap_probe, ctx.world, wl):
-        overlap = piped_pass(ctx, wl, runner, args.warmup, args.steps)
-        ctx.log("%d batches in flight: %d steps in %.3fs, identical results: %s" % (IN_FLIGHT[0], args.steps, overlap[0], overlap[1]))
+    # Without --full the run times only the pass that gives `value` (the a-priori choice made below): the K steps with
+    # several batches in flight where that pass is allowed, else the sequential timed region.  --full times both passes and
+    # compares their results, and adds the probes, legs and baselines after them.
+    lean_piped = (not args.full and not args.sequential_value
+                  and overlap_probe_allowed(depth, args.steps, args.no_overlap_probe, ctx.world, wl))
+    fam = solo = overlap = None
+    if lean_piped:
+        elapsed, own_elapsed = in_flight_region(ctx, wl, runner, args.warmup, args.steps)
+    else:
+        elapsed, own_elapsed, fam = timed_region(ctx, wl, runner, args.warmup, args.steps)
+    if args.full:
+        # In the timed region the prefilter launches of a step overlap other work (the vanilla and the
+        # symmetric RANSAC calls run on two host threads, the small kernels of a round run under the next
+        # prefilter), so their event-bracketed durations include the share of the GPU they did not have.
+        # A short extra pass with both overlaps switched off gives the kernel's stand-alone rate (same inputs,
+        # same launches merged back into one call); reported as roofline.solo, not used for `value`.
+        if ctx.world == 1 and not args.no_solo_probe and args.steps >= 1 and wl.solo_env():
+            env = wl.solo_env()
+            saved = {k: os.environ.get(k) for k in env}
+            os.environ.update(env)
+            try:
+                keep = list(wl.results)
+                _lib.prof_reset()
+                _lib.prof_enable(True)
+                run_steps(args.warmup, args.warmup + min(2, args.steps), depth=1)
+                torch.cuda.synchronize()
+                _lib.prof_enable(False)
+                ms, n, units = _lib.prof_get("ransac_pre")
+                solo = {"ms": ms, "launches": n, "flop": units}
+                wl.results[:] = keep
+            finally:
+                for k, v in saved.items():
+                    if v is None:
+                        os.environ.pop(k, None)
+                    else:
+                        os.environ[k] = v
+            ctx.log("stand-alone prefilter pass done")
+        # Throughput mode, reported next to the contract number (never instead of it): the same K batches
+        # again with three of them in flight.  Kernels of the two streams share the GPU, so per-launch event
+        # times are not a roofline measurement there; profiling stays off.  The results must come out
+        # identical to the sequential pass.
+        # (not with a collective inside the step on several ranks: the worker threads of a rank would issue their
+        # all-gathers in an order of their own and the ranks' collectives would no longer pair up)
+        if overlap_probe_allowed(depth, args.steps, args.no_overlap_probe, ctx.world, wl):
+            overlap = piped_pass(ctx, wl, runner, args.warmup, args.steps)
+            ctx.log("%d batches in flight: %d steps in %.3fs, identical results: %s" % (IN_FLIGHT[0], args.steps, overlap[0], overlap[1]))
     # contract: the MAX over ranks of the barrier-to-barrier time; per-rank own times show the balance
     elapsed, ov = ctx.reduce_max([elapsed, overlap[0] if overlap else 0.0])
     if overlap:
@@ -1361,16 +1437,18 @@ def main():
 
     cfg = wl.config(args.steps)   # every rank (accuracy bookkeeping of its own queries)
     if ctx.rank == 0:
+        dumped = dump_outputs(wl, args.dump_outputs) if args.dump_outputs else None
         strong = getattr(wl, "scaling", "weak") == "strong"
         total_units = args.steps * wl.units_per_step * (1 if strong else ctx.world)
         # `value`: the K steps with three batches in flight (three host threads x three HIP streams) WHENEVER that pass ran
         # and its results are identical to the sequential pass -- VERDICT r3 #5: the embed of step i+1 under the RANSAC of
         # step i is real throughput.  The choice is made a priori, not per run by which pass came out faster (the
         # faster of two noisy measurements biases the headline); `--sequential-value` / `--no-overlap-probe` select the
-        # sequential pass.  `sequential` always carries the one-batch-at-a-time figures, and `roofline` is measured over
-        # THAT pass (in the pipelined one a launch's event time includes its neighbours).
-        piped = overlap is not None and bool(overlap[1]) and not args.sequential_value
-        head_elapsed = overlap[0] if piped else elapsed
+        # sequential pass.  Without --full only the pass that gives `value` runs (in_flight_region or timed_region); with it
+        # `sequential` carries the one-batch-at-a-time figures, and `roofline` is measured over THAT pass (in the pipelined
+        # one a launch's event time includes its neighbours).
+        piped = lean_piped or (overlap is not None and bool(overlap[1]) and not args.sequential_value)
+        head_elapsed = overlap[0] if overlap is not None and piped else elapsed
         cfg.update({"parallelism": "dp%d" % ctx.world, "batches_in_flight": IN_FLIGHT[0] if piped else depth,
                     "value_pass": ("%d batches in flight" % IN_FLIGHT[0]) if piped else "sequential",
                     "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES")})
@@ -1392,16 +1470,18 @@ def main():
             "dtype": DTYPE_LABEL[args.workload if args.workload in ("stress", "dry") else "registration"],
             "data": "none (dry run)" if ctx.dry else "synthetic",
             "config": cfg,
-            "roofline": None if ctx.dry else roofline_of(fam, solo, args),
-            "roofline_by_kernel": None if ctx.dry else roofline_by_kernel(fam, args),
-            "kernel_ms": {k: round(v["ms"], 3) for k, v in fam.items()},
         }
+        if args.full:
+            out.update({"roofline": None if ctx.dry else roofline_of(fam, solo, args),
+                        "roofline_by_kernel": None if ctx.dry else roofline_by_kernel(fam, args),
+                        "kernel_ms": {k: round(v["ms"], 3) for k, v in fam.items()}})
         if ctx.dry:
             out["metric"] = "DRY RUN (no kernels): steps/s of an empty step"
         if args.workload == "stress":
             out["metric"] = "stress queries/sec (batch-64 forward + top-10 share), configs[4]"
-            out["kernel_tflops"] = {k: round(fam[k]["flop"] / max(fam[k]["ms"], 1e-9) / 1e9, 2)
-                                    for k in ("conv", "topk")}
+            if args.full:
+                out["kernel_tflops"] = {k: round(fam[k]["flop"] / max(fam[k]["ms"], 1e-9) / 1e9, 2)
+                                        for k in ("conv", "topk")}
             out["est_full_job_s"] = 100000.0 / out["value"]  # 100k clouds + 10^6 x 10^6 top-10 (value = all ranks)
         if ctx.world > 1:
             out["dist"] = {"backend": "rccl" if ctx.backend == "nccl" else ctx.backend,
@@ -1409,13 +1489,16 @@ def main():
                            "rank_elapsed_s": [round(float(v), 4) for v in own],
                            "rank_time_max_over_min": float(own.max() / max(own.min(), 1e-9))}
         wl.extras(out)
-        out["sequential"] = {"value": total_units / elapsed, "unit": "queries/s", "ms_per_step": elapsed / args.steps * 1e3,
-                             "note": "the same K steps one batch at a time (the pass `roofline`, `roofline_by_kernel` and "
-                                     "`kernel_ms` are measured over: their launches share the GPU only with their own step)"
-                                     + ("; %d consecutive steps' query batches share one forward of the network, retrieval and "
-                                        "registration per step" % args.embed_group
-                                        if hasattr(wl, "step_group") and args.embed_group > 1 and depth == 1 else "")}
-        if out["roofline"]:
+        if dumped is not None:
+            out["outputs_dumped"] = dumped
+        if args.full:
+            out["sequential"] = {"value": total_units / elapsed, "unit": "queries/s", "ms_per_step": elapsed / args.steps * 1e3,
+                                 "note": "the same K steps one batch at a time (the pass `roofline`, `roofline_by_kernel` and "
+                                         "`kernel_ms` are measured over: their launches share the GPU only with their own step)"
+                                         + ("; %d consecutive steps' query batches share one forward of the network, retrieval and "
+                                            "registration per step" % args.embed_group
+                                            if hasattr(wl, "step_group") and args.embed_group > 1 and depth == 1 else "")}
+        if out.get("roofline"):
             out["roofline"]["pass"] = "sequential"
         if overlap:
             out["batches_in_flight"] = {
@@ -1424,7 +1507,7 @@ def main():
                 "is_headline": bool(piped),
                 "note": "the same K batches with `depth` host threads, one HIP stream each (the library's scratch cache is per "
                         "thread and stream-ordered); results compared with the sequential pass"}
-        if ctx.world == 1 and args.workload == "chair" and not strong and not args.no_extra_workloads:
+        if args.full and ctx.world == 1 and args.workload == "chair" and not strong and not args.no_extra_workloads:
             # configs[2] and configs[4] under the same clock as the headline (short legs, same measurement).  BEFORE the
             # CPU baseline: after it the table leg measured 429 instead of 568 queries/s on the same box (the oracle's
             # OpenMP / BLAS worker threads keep the host cores busy for a while after their last parallel region)
@@ -1432,7 +1515,7 @@ def main():
             # the driver's record keeps `config` whole and of everything else only the key names: the legs'
             # figures that matter go there too
             cfg["legs"] = {name: leg_summary(leg) for name, leg in out["workloads"].items()}
-        if ctx.world == 1 and not args.no_cpu_baseline and hasattr(wl, "cpu_baseline"):
+        if args.full and ctx.world == 1 and not args.no_cpu_baseline and hasattr(wl, "cpu_baseline"):
             out["cpu_baseline"] = wl.cpu_baseline()
         sys.stdout.flush()
         os.write(result_fd, (json.dumps(out) + "\n").encode())

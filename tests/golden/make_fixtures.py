@@ -19,6 +19,15 @@ Fixtures are DATA (inputs + expected outputs); no reference source text is store
                         directories, first 10000 points, f16-rounded coordinates stored as f32 to keep
                         the file small: the clouds are inputs only, nothing is compared with the
                         originals) for the real-occupancy GPU parity tests and the k-means pin.
+  ref_cache_pose_best/  the nine files of the reference's shipped data/cache_pose_best for (chair, top1),
+                        unchanged: the result-cache format test reads them with corsair_amd.cache.
+  reference_model_layout.json
+                        what the reference's own model package is on the MinkowskiEngine shim (names,
+                        counts and shapes only, no source text): the MinkowskiEngine modules its model/*.py
+                        import and the names imported from them, the ME / MEF attributes they name, every
+                        ME / MEF call site (file, line, enclosing Class.method, callee, number of positional
+                        arguments, keyword names), the classes ResUNetBN2C and conv1_max_embedding are made of
+                        when built there, and their state-dict names and shapes.
 """
 import os
 import sys
@@ -155,11 +164,118 @@ def make_real_clouds10():
                         names=np.array(names), cats=np.array(cats))
 
 
+def make_ref_cache():
+    import shutil
+
+    from corsair_amd import cache
+
+    d = f"{OUT}/ref_cache_pose_best"
+    os.makedirs(d, exist_ok=True)
+    for n in cache.NAMES:
+        shutil.copyfile(f"{REF}/data/cache_pose_best/{n}_chair_top1.npy", f"{d}/{n}_chair_top1.npy")
+
+
+# run in a child interpreter with the shim, this tree and the reference on its path (the reference's `model` / `utils`
+# packages must not shadow anything here); prints the two state-dict layouts and the classes the two models are made of
+# (every submodule's class and its bases up to torch.nn.Module) as one JSON line
+LAYOUT_SCRIPT = r"""
+import json, sys
+import torch, model
+from model import load_model, fc
+m = load_model("ResUNetBN2C")(1, 16, bn_momentum=0.05, normalize_feature=True, conv1_kernel_size=3, D=3)
+e = fc.conv1_max_embedding(1024, 512, 256)
+used = sorted({c.__name__ for net in (m, e) for mod in net.modules() for c in type(mod).__mro__
+               if c.__module__.startswith("model.")})
+print(json.dumps({"resunet_bn2c": {k: list(v.shape) for k, v in m.state_dict().items()},
+                  "conv1_max_embedding": {k: list(v.shape) for k, v in e.state_dict().items()},
+                  "classes_built": used}))
+"""
+
+
+def _me_usage(path):
+    """MinkowskiEngine imports, attribute names and call sites of one reference model file (read as data)."""
+    import ast
+
+    with open(path) as fh:
+        tree = ast.parse(fh.read())
+    alias = {}                     # local name -> MinkowskiEngine module path
+    imports, names, calls = [], set(), []
+    for n in ast.walk(tree):
+        if isinstance(n, ast.Import):
+            for a in n.names:
+                if a.name.split(".")[0] == "MinkowskiEngine":
+                    imports.append({"module": a.name, "names": []})
+                    alias[a.asname or a.name] = a.name
+        elif isinstance(n, ast.ImportFrom) and (n.module or "").split(".")[0] == "MinkowskiEngine":
+            imports.append({"module": n.module, "names": [a.name for a in n.names]})
+
+    def dotted(node):
+        parts = []
+        while isinstance(node, ast.Attribute):
+            parts.append(node.attr)
+            node = node.value
+        if isinstance(node, ast.Name) and node.id in alias:
+            sub = alias[node.id].split(".")[1:]
+            return ".".join(sub + list(reversed(parts)))
+        return None
+
+    def visit(node, where, scope):
+        for c in ast.iter_child_nodes(node):
+            if isinstance(c, ast.ClassDef):
+                visit(c, c.name, "class")
+            elif isinstance(c, (ast.FunctionDef, ast.AsyncFunctionDef)):
+                if scope == "class":
+                    visit(c, where.split(".")[0] + "." + c.name, "class")
+                else:
+                    visit(c, where or c.name, "function")
+            else:
+                if isinstance(c, ast.Attribute):
+                    d = dotted(c)
+                    if d:
+                        names.add(d)
+                if isinstance(c, ast.Call):
+                    d = dotted(c.func)
+                    if d:
+                        calls.append({"file": os.path.basename(path), "line": c.lineno, "where": where, "scope": scope,
+                                      "callee": d,
+                                      "n_args": len(c.args), "keywords": [k.arg for k in c.keywords if k.arg],
+                                      "star": any(isinstance(a, ast.Starred) for a in c.args)})
+                visit(c, where, scope)
+
+    visit(tree, "", "module")
+    return imports, names, calls
+
+
+def make_reference_model_layout():
+    import json
+    import subprocess
+
+    imports, names, calls = [], set(), []
+    for f in sorted(os.listdir(f"{REF}/model")):
+        if f.endswith(".py"):
+            i, n, c = _me_usage(f"{REF}/model/{f}")
+            imports += [dict(x, file=f) for x in i]
+            names |= n
+            calls += c
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.join(ROOT, "shim"), ROOT, REF]))
+    p = subprocess.run([sys.executable, "-c", LAYOUT_SCRIPT], cwd=OUT, env=env, capture_output=True, text=True, check=True)
+    layout = json.loads(p.stdout.strip().splitlines()[-1])
+    layout["me_imports"] = imports
+    layout["me_names"] = sorted(names)
+    layout["me_calls"] = sorted(calls, key=lambda c: (c["file"], c["line"]))
+    layout["resunet_bn2c_params"] = int(sum(int(np.prod(s)) for s in layout["resunet_bn2c"].values()))
+    with open(f"{OUT}/reference_model_layout.json", "w") as fh:
+        json.dump(layout, fh, indent=1, sort_keys=True)
+        fh.write("\n")
+
+
 if __name__ == "__main__":
     make_eval_pose_kat()
     make_aggregate_kat()
     make_retrieval_kat()
     make_real_clouds()
     make_real_clouds10()
+    make_ref_cache()
+    make_reference_model_layout()
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)))

@@ -102,7 +102,7 @@ def test_gpus8_launcher_end_to_end_on_cpu_ranks():
 
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--workload", "dry", "--steps", "4",
-                        "--warmup", "1"], env=env, capture_output=True, text=True, timeout=600)
+                        "--warmup", "1", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, p.stdout
@@ -112,7 +112,49 @@ def test_gpus8_launcher_end_to_end_on_cpu_ranks():
     assert out["config"]["parallelism"] == "dp8" and out["config"]["catalog"] == 11
     assert out["batches_in_flight"]["identical_results"] is True and out["config"]["value_pass"] == "3 batches in flight"
     assert "DRY RUN" in out["metric"] and "not a measurement" in out["config"]["workload"]
-    assert "8 ranks on 0 visible device(s)" in p.stderr          # the launcher chose gloo because the ranks share devices
+    # the launcher chose gloo because the ranks share devices (none without a GPU, the one device of a one-GPU box)
+    n_dev = _load_bench().visible_device_count()
+    assert n_dev < 8 and "8 ranks on %d visible device(s): ranks share devices, backend gloo" % n_dev in p.stderr
+
+
+def test_plain_run_times_only_the_headline_pass_and_dumps_its_outputs(tmp_path):
+    """Without --full ONE pass runs (the batches-in-flight one, as its log shows: one timed region, no comparison with a
+    sequential pass, no probe), the line carries the headline alone (no sequential pass, legs or baselines), and
+    --dump-outputs writes the last timed step's arrays as float32 / float64 .npy."""
+    import re
+
+    import json
+
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "dry", "--steps", "5",
+                        "--warmup", "2", "--dump-outputs", str(tmp_path / "out")], env=env, capture_output=True, text=True,
+                       timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, p.stdout
+    out = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in out, k
+    assert out["steps"] == 5 and out["warmup"] == 2 and out["value_pass"] == "3 batches in flight"
+    log = p.stderr.splitlines()
+    assert len([l for l in log if re.match(r"\[bench\] timed region: 5 steps in [0-9.]+s, 3 batches in flight$", l)]) == 1, log
+    assert len([l for l in log if "timed region" in l]) == 1, log
+    assert not [l for l in log if "identical results" in l or "stand-alone" in l], log
+    for k in ("sequential", "batches_in_flight", "roofline", "kernel_ms", "workloads", "cpu_baseline"):
+        assert k not in out, k
+    assert out["outputs_dumped"] == ["step_value"]
+    v = np.load(tmp_path / "out" / "step_value.npy")
+    assert v.dtype == np.float64 and float(v) == float(np.sin(2 + 5 - 1))     # step W + K - 1 of rank 0
+
+
+def test_plain_warmup_covers_every_worker_and_one_embed_group():
+    """The untimed steps in front of a plain run's batches-in-flight pass: W, but at least one per worker and one whole
+    embed group (never more than W + K)."""
+    bench = _load_bench()
+    assert bench.in_flight_warmup_steps(2, 8, 3, 4) == 4       # the defaults: one forward of 4 batches, every worker a step
+    assert bench.in_flight_warmup_steps(2, 8, 3, 1) == 3
+    assert bench.in_flight_warmup_steps(6, 8, 3, 4) == 6
+    assert bench.in_flight_warmup_steps(0, 2, 3, 4) == 2
 
 
 def test_headline_pass_is_fixed_a_priori_not_by_speed():

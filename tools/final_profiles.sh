@@ -25,6 +25,6 @@ for w in chair table stress; do
 done
 bash tools/launch_census.sh $o/census > $o/${tag}_chair_launch_census.txt 2>&1 || { echo "census failed"; tail -5 $o/${tag}_chair_launch_census.txt; }
 rm -rf $o/census
-python3 bench.py > $o/${tag}_default_line.json 2> $o/${tag}_default_line.err || { echo "default line failed"; tail -5 $o/${tag}_default_line.err; exit 1; }
+python3 bench.py --full > $o/${tag}_default_line.json 2> $o/${tag}_default_line.err || { echo "default line failed"; tail -5 $o/${tag}_default_line.err; exit 1; }
 du -sh $o
 echo "[final] done"
