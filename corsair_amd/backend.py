@@ -6,6 +6,7 @@ device buffers and the stream.  No CPU fallback: inputs must be CUDA(HIP) tensor
 from __future__ import annotations
 
 import ctypes
+import os
 from ctypes import c_void_p
 
 import numpy as np
@@ -117,13 +118,16 @@ def _hip_runtime():
 class KernelMap:
     """Owns one cs_kernelmap handle (int32 [n_out,27] neighbour table on the device)."""
 
-    def __init__(self, handle, in_map, out_map, transposed):
+    def __init__(self, handle, in_map, out_map, transposed, kernel_size=3):
         self._h = c_void_p(handle)
+        self.kvol = int(kernel_size) ** 3
         lib = _lib.load()
         self.n_out = int(lib.cs_kernelmap_rows(self._h))
         self.n_in = in_map.n
         self._num_pairs = None
         self.transposed = transposed
+        # stride 1 (in map == out map): the data gradient runs on this same map with mirrored offsets (conv_dgrad)
+        self.stride1 = not transposed and in_map.tensor_stride == out_map.tensor_stride
         self.device = in_map.device
 
     @property
@@ -139,7 +143,7 @@ class KernelMap:
         check(_lib.load().cs_kernelmap_build(in_map._h, out_map._h, kernel_size,
                                              1 if transposed else 0, stream_ptr(),
                                              ctypes.byref(out)))
-        return cls(out.value, in_map, out_map, transposed)
+        return cls(out.value, in_map, out_map, transposed, kernel_size)
 
     @classmethod
     def build_many(cls, specs):
@@ -156,7 +160,7 @@ class KernelMap:
         tr = CI(*[1 if sp[3] else 0 for sp in full])
         kms = VP()
         check(_lib.load().cs_kernelmap_build_many(n, ins, outs, ks, tr, stream_ptr(), kms))
-        return [cls(kms[i], full[i][0], full[i][1], full[i][3]) for i in range(n)]
+        return [cls(kms[i], full[i][0], full[i][1], full[i][3], full[i][2]) for i in range(n)]
 
     def export(self):
         """Canonical (k, in_row, out_row) int32 triples sorted by (k, out_row)."""
@@ -213,6 +217,54 @@ def conv_fwd(kmap, x, weight, scale=None, shift=None, residual=None, relu=False,
     return out
 
 
+def conv_wgrad(kmap, x, g):
+    """Weight gradient of conv_fwd(kmap, x, W) for the output gradient g (cs_conv_wgrad): [27, cin, cout], or
+    [cin, cout] for kernel size 1 (kmap None, or a strided / transposed map of kernel size 1).  x and g may be
+    column slices of wider row-major buffers."""
+    x, ld_in = _rows(_dev(x, torch.float32, "input features"), "input features")
+    g, ld_g = _rows(_dev(g, torch.float32, "output gradient"), "output gradient")
+    n_in, cin = x.shape
+    n_out, cout = g.shape
+    if kmap is not None and (kmap.n_in, kmap.n_out) != (n_in, n_out):
+        raise ValueError(f"kernel map is for {kmap.n_in} -> {kmap.n_out} rows, tensors have {n_in} -> {n_out}")
+    kvol = 1 if kmap is None else kmap.kvol
+    dw = torch.empty((cin, cout) if kvol == 1 else (kvol, cin, cout), dtype=torch.float32, device=x.device)
+    check(_lib.load().cs_conv_wgrad(kmap._h if kmap is not None else None, n_in, n_out, ptr(x), ld_in, cin, ptr(g),
+                                    ld_g, cout, ptr(dw), stream_ptr()))
+    return dw
+
+
+def dgrad_weight(kmap, weight):
+    """W' of the data gradient: conv_fwd(reverse map, gY, W') = dL/dx of conv_fwd(kmap, x, W).  With
+    k = (dx+1) + 3(dy+1) + 9(dz+1) mirroring an offset maps k to 26 - k:
+      stride 1 (the map is its own reverse, T[T[o][k]][26-k] = o):   W'[k] = W[26-k]^T
+      strided / transposed (reverse = the other map, same k):        W'[k] = W[k]^T
+      kernel size 1 (kmap None, or a strided / transposed map):      W' = W^T"""
+    if kmap is None or kmap.kvol == 1:
+        return weight.reshape(weight.shape[-2:]).t().contiguous()
+    if kmap.stride1:
+        return weight.flip(0).transpose(1, 2).contiguous()
+    return weight.transpose(1, 2).contiguous()
+
+
+def conv_dgrad(kmap, rev_kmap, g, weight):
+    """Input gradient of conv_fwd(kmap, x, weight) for the output gradient g: cs_conv_fwd on the reverse map
+    (no kernel of its own).  rev_kmap: for a stride-1 map the map itself (None is accepted), for a strided map
+    (fine -> coarse) the transposed map coarse -> fine, for a transposed map the strided map fine -> coarse;
+    ignored for kmap None (1x1)."""
+    if os.environ.get("CS_CONV_SPLIT", "0") not in ("", "0"):
+        raise _lib.CorsairHipError("conv_dgrad: the CS_CONV_SPLIT experiment caches cut weights per pointer and would "
+                                   "hand back stale ones for the temporary permuted weights; unset it to train")
+    wt = dgrad_weight(kmap, weight)
+    if kmap is None:
+        return conv_fwd(None, g, wt)
+    if kmap.stride1:
+        rev_kmap = kmap if rev_kmap is None else rev_kmap
+    if rev_kmap is None or (rev_kmap.n_in, rev_kmap.n_out, rev_kmap.kvol) != (kmap.n_out, kmap.n_in, kmap.kvol):
+        raise ValueError("conv_dgrad: the reverse map must take the forward's output rows to its input rows")
+    return conv_fwd(rev_kmap, g, wt)
+
+
 def affine_act(x, scale=None, shift=None, residual=None, relu=False, out=None):
     x, ld_in = _rows(_dev(x, torch.float32, "input"), "input")
     if out is None:
@@ -228,6 +280,10 @@ def affine_act(x, scale=None, shift=None, residual=None, relu=False, out=None):
 
 
 def row_l2_normalize(x, eps=0.0, out=None):
+    if out is None and torch.is_grad_enabled() and x.requires_grad:   # training: same kernel, with a backward
+        from .autograd import RowL2NormalizeFunction
+
+        return RowL2NormalizeFunction.apply(x, float(eps))
     x, ld_in = _rows(_dev(x, torch.float32, "input"), "input")
     if out is None:
         out = torch.empty((x.shape[0], x.shape[1]), dtype=torch.float32, device=x.device)
@@ -239,6 +295,10 @@ def row_l2_normalize(x, eps=0.0, out=None):
 
 def segmented_max(x, coords, n_batch):
     """Per-sample column max; `coords` is the int32 [n,4] coordinate tensor (batch in column 0)."""
+    if torch.is_grad_enabled() and x.requires_grad:   # training: same kernel, gradient to the first maximal row
+        from .autograd import SegmentedMaxFunction
+
+        return SegmentedMaxFunction.apply(x, coords, int(n_batch))
     x, ld_in = _rows(_dev(x, torch.float32, "input"), "input")
     coords = _dev(coords, torch.int32, "coords")
     out = torch.empty((n_batch, x.shape[1]), dtype=torch.float32, device=x.device)

@@ -1,4 +1,4 @@
-"""MinkowskiEngine-compatible operator surface on libcorsair_hip.so (inference only).
+"""MinkowskiEngine-compatible operator surface on libcorsair_hip.so (inference and training).
 
 The reference's model code (model/resunet.py, model/residual_block.py, model/common.py, model/fc.py)
 and evaluation.py talk to MinkowskiEngine 0.5.5 through a small Python API.  This module
@@ -11,9 +11,12 @@ implements exactly that subset, so those files run unmodified when ``shim/`` is 
   MEF.relu, SparseTensor.__iadd__, ME.cat    model/resunet.py:212-255, residual_block.py:70
   ME.utils.sparse_quantize / sparse_collate  utils/Info/CADLib.py:106-121,166-168 (CPU, DataLoader workers)
 
-Everything that touches features runs a HIP kernel; there is no CPU fallback and no training path
-(backward is not implemented: the reference's evaluated path is inference under torch.no_grad()).
-The fused production path is corsair_amd.engine.ResUNetEngine; this op-by-op surface is the drop-in.
+Everything that touches features runs a HIP kernel; there is no CPU fallback.  With grad enabled the ops
+go through torch.autograd.Function wrappers (corsair_amd/autograd.py) whose forwards are the same kernels:
+convolutions get their weight gradient from cs_conv_wgrad and their input gradient from cs_conv_fwd on the
+reverse kernel map; MinkowskiBatchNorm in train mode is torch BatchNorm1d over the rows, as in MinkowskiEngine.
+The fused production path is corsair_amd.engine.ResUNetEngine (inference only); this op-by-op surface is the
+drop-in.
 """
 from __future__ import annotations
 
@@ -21,6 +24,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from .. import autograd as AG
 from .. import backend as B
 
 __version__ = "0.5.5"  # model/resunet.py:55 compares ME.__version__ >= "0.5.4" as strings
@@ -135,14 +139,22 @@ class SparseTensor:
             raise RuntimeError("SparseTensor: operands live on different coordinate maps")
 
     def __iadd__(self, other):
-        """out += residual (model/residual_block.py:70)."""
+        """out += residual (model/residual_block.py:70).  Under grad the sum is a new tensor (autograd may need
+        the old one) and `_F` is rebound to it."""
         self._same(other)
-        B.affine_act(self._F, None, None, other.F, False, out=self._F)
+        if _needs_grad(self._F, other.F):
+            self._F = AG.AddFunction.apply(self._F, other.F)
+        else:
+            B.affine_act(self._F, None, None, other.F, False, out=self._F)
         return self
 
     def __add__(self, other):
         self._same(other)
-        return SparseTensor(B.affine_act(self._F, None, None, other.F, False),
+        if _needs_grad(self._F, other.F):
+            out = AG.AddFunction.apply(self._F, other.F)
+        else:
+            out = B.affine_act(self._F, None, None, other.F, False)
+        return SparseTensor(out,
                             coordinate_map_key=self.coordinate_map_key,
                             coordinate_manager=self.coordinate_manager)
 
@@ -151,6 +163,10 @@ class SparseTensor:
 
     def __repr__(self):
         return f"SparseTensor(F={tuple(self._F.shape)}, {self.coordinate_map_key})"
+
+
+def _needs_grad(*tensors):
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
 
 
 def cat(*tensors):
@@ -195,8 +211,6 @@ class _ConvBase(nn.Module):
                 self.bias.uniform_(-s, s)
 
     def forward(self, x):
-        if torch.is_grad_enabled() and (self.kernel.requires_grad and x.F.requires_grad):
-            raise NotImplementedError("corsair_amd implements inference only (wrap in torch.no_grad())")
         cm = x.coordinate_manager
         in_key = x.coordinate_map_key
         if self.kernel_size == 1 and self.stride == 1:
@@ -212,6 +226,11 @@ class _ConvBase(nn.Module):
                 raise RuntimeError("transposed convolution needs the finer coordinate map to exist "
                                    "(expand_coordinates=False semantics)")
             kmap = cm.kernel_map(in_key, out_key, self.kernel_size, True)
+        if _needs_grad(x.F, self.kernel, self.bias):
+            # reverse map of the data gradient (strided <-> transposed, same k), from the manager's cache
+            rev = lambda: cm.kernel_map(out_key, in_key, self.kernel_size, not self.transposed)  # noqa: E731
+            out = AG.ConvFunction.apply(x.F, self.kernel, self.bias, kmap, rev)
+            return SparseTensor(out, coordinate_map_key=out_key, coordinate_manager=cm)
         bias = self.bias.detach().reshape(-1) if self.bias is not None else None
         out = B.conv_fwd(kmap, x.F, self.kernel.detach(), None, bias, None, False)
         return SparseTensor(out, coordinate_map_key=out_key, coordinate_manager=cm)
@@ -226,7 +245,9 @@ class MinkowskiConvolutionTranspose(_ConvBase):
 
 
 class MinkowskiBatchNorm(nn.Module):
-    """BatchNorm1d over rows (state-dict prefix `.bn.`), eval mode only."""
+    """BatchNorm1d over rows (state-dict prefix `.bn.`).  Eval mode: the folded affine kernel (with a backward
+    when grad is enabled: frozen-statistics fine-tuning).  Train mode: `self.bn(x.F)`, as MinkowskiEngine does
+    (batch statistics, running-stat update with the configured momentum)."""
 
     def __init__(self, num_features, eps=1e-5, momentum=0.1, affine=True, track_running_stats=True):
         super().__init__()
@@ -250,9 +271,17 @@ class MinkowskiBatchNorm(nn.Module):
 
     def forward(self, x):
         if self.training:
-            raise NotImplementedError("MinkowskiBatchNorm: training mode is not implemented (call .eval())")
-        scale, shift = self._fold()
-        return SparseTensor(B.affine_act(x.F, scale, shift, None, False),
+            out = self.bn(x.F)
+        elif _needs_grad(x.F, self.bn.weight, self.bn.bias):
+            scale, shift = self._fold()
+            bn = self.bn
+            mean = bn.running_mean.detach().float()
+            inv_std = torch.rsqrt(bn.running_var.detach().float() + bn.eps)
+            out = AG.AffineFunction.apply(x.F, bn.weight, bn.bias, scale, shift, mean, inv_std)
+        else:
+            scale, shift = self._fold()
+            out = B.affine_act(x.F, scale, shift, None, False)
+        return SparseTensor(out,
                             coordinate_map_key=x.coordinate_map_key, coordinate_manager=x.coordinate_manager)
 
 
@@ -270,7 +299,11 @@ class MinkowskiInstanceNorm(nn.Module):
         batch = x.C[:, 0].contiguous()
         n_batch = int(batch[-1].item()) + 1 if batch.numel() else 0      # rows are grouped by sample
         seg = torch.searchsorted(batch, torch.arange(n_batch + 1, device=batch.device, dtype=batch.dtype))
-        out = B.instance_norm(x.F, seg.to(torch.int32), self.weight.detach(), self.bias.detach(), 1e-8)
+        seg = seg.to(torch.int32)
+        if _needs_grad(x.F, self.weight, self.bias):
+            out = AG.InstanceNormFunction.apply(x.F, self.weight, self.bias, seg, 1e-8)
+        else:
+            out = B.instance_norm(x.F, seg, self.weight.detach(), self.bias.detach(), 1e-8)
         return SparseTensor(out, coordinate_map_key=x.coordinate_map_key, coordinate_manager=x.coordinate_manager)
 
 
@@ -285,7 +318,8 @@ class MinkowskiReLU(nn.Module):
 class _Functional:
     @staticmethod
     def relu(x):
-        return SparseTensor(B.affine_act(x.F, None, None, None, True),
+        out = AG.ReLUFunction.apply(x.F) if _needs_grad(x.F) else B.affine_act(x.F, None, None, None, True)
+        return SparseTensor(out,
                             coordinate_map_key=x.coordinate_map_key, coordinate_manager=x.coordinate_manager)
 
 

@@ -119,6 +119,16 @@ int cs_conv_fwd(const cs_kernelmap* km, int64_t n_in, int64_t n_out, const float
                 const float* d_residual, int ld_res, int relu, float* d_out, int ld_out,
                 void* stream);
 
+/* Weight gradient of that convolution (training through the MinkowskiEngine shim):
+ *   d_dw[k, ci, co] = sum_{o : T[o][k] >= 0} in[T[o][k], ci] * gout[o, co]
+ * for any map as built (stride 1, strided, transposed); km == NULL means kernel_size 1 (d_dw = in^T gout,
+ * [cin, cout]).  d_dw is [kvol, cin, cout] like the forward's W; offsets without a pair get exact zeros.  Rows are
+ * summed in fixed chunks of the map's tiling order (f32 MFMA inside a chunk, chunks added in ascending order, no
+ * atomics): the result is bit-identical run to run.  ld_in / ld_gout allow column slices of wider buffers.
+ * The data gradient is cs_conv_fwd on the reverse map (corsair_amd/backend.py conv_dgrad). */
+int cs_conv_wgrad(const cs_kernelmap* km, int64_t n_in, int64_t n_out, const float* d_in, int ld_in, int cin,
+                  const float* d_gout, int ld_gout, int cout, float* d_dw, void* stream);
+
 /* EXPERIMENT, off by default (reduced precision "only behind a parity-checked flag").  With the environment
  * variable CS_CONV_SPLIT=3 (or 2) cs_conv_fwd evaluates the layers the LDS-DMA kernel serves on the bf16 matrix cores:
  * every f32 operand cut into 3 (2) bf16 pieces, 6 (3) products per 16 channels accumulated in f32 -- NOT the fma chain
