@@ -77,6 +77,14 @@ def _declare(lib):
         "cs_partition_by_label": (c_int, [vp, vp, c_int, vp, vp]),
         "cs_cfg_bad": (c_int, [vp, c_int, vp, c_int, vp, vp]),
         "cs_corr_assemble": (c_int, [vp, vp, vp, vp, c_int, vp, c_int, c_int64, vp, vp, vp]),
+        "cs_radius_pairs": (c_int, [vp, POINTER(c_int64), vp, POINTER(c_int64), POINTER(c_int32), POINTER(c_int32),
+                                    c_int, c_double, c_int, vp, vp, POINTER(vp)]),
+        "cs_radius_pairs_fill": (c_int, [vp, vp, vp, vp]),
+        "cs_radius_plan_free": (None, [vp]),
+        "cs_sample_pairs": (c_int, [vp, POINTER(c_int64), POINTER(c_int32), POINTER(c_int32), POINTER(c_int32),
+                                    POINTER(c_int32), c_int, POINTER(c_int64), vp, vp, c_int, c_uint64, c_int,
+                                    c_double, c_int, vp, vp, vp, vp, vp]),
+        "cs_transform_f64": (c_int, [vp, POINTER(c_int64), POINTER(c_int32), c_int, vp, vp, vp]),
         "cs_prof_enable": (None, [c_int]),
         "cs_prof_reset": (None, []),
         "cs_prof_get": (c_int, [c_char_p, POINTER(c_double), POINTER(c_int64)]),

@@ -502,3 +502,95 @@ def symcut_labels(xyz, offsets, Ks, sel_centers):
     check(_lib.load().cs_symcut_labels(ptr(xyz), i64_array(offsets), len(Ks), i32_array(Ks),
                                        ptr(sel_centers), ptr(labels), stream_ptr()))
     return labels
+
+
+# ---- training batches -------------------------------------------------------------------------------
+class RadiusPlan:
+    """Owns one cs_radius_plan: the search of radius_pairs_begin, waiting for its fill.  Keeps the point tensors alive
+    (the fill reads them again)."""
+
+    def __init__(self, handle, keep):
+        self._h = c_void_p(handle)
+        self._keep = keep
+
+    def fill(self, row_ptr, total):
+        """Target indices int32 [total] of the CSR whose row offsets radius_pairs_begin wrote into row_ptr."""
+        idx = torch.empty(max(int(total), 1), dtype=torch.int32, device=row_ptr.device)
+        check(_lib.load().cs_radius_pairs_fill(self._h, ptr(row_ptr), ptr(idx), stream_ptr()))
+        return idx[:int(total)]
+
+    def __del__(self):
+        try:
+            if self._h:
+                _lib.load().cs_radius_plan_free(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+
+def radius_pairs_begin(src, soff, tgt, toff, src_seg=None, tgt_seg=None, radius=0.03, k=None):
+    """Enqueues cs_radius_pairs: returns (row_ptr int64 [rows+1] device, RadiusPlan).  No host wait: the caller reads
+    row_ptr[-1] (with whatever else it needs) and calls plan.fill(row_ptr, total)."""
+    src = _dev(src, torch.float64, "source points").contiguous()
+    tgt = _dev(tgt, torch.float64, "target points").contiguous()
+    if src_seg is None:
+        src_seg = list(range(len(soff) - 1))
+        tgt_seg = list(range(len(toff) - 1))
+    if len(src_seg) != len(tgt_seg):
+        raise ValueError("radius_pairs: src_seg and tgt_seg differ in length")
+    if k is not None and int(k) < 1:
+        raise ValueError("radius_pairs: k must be None or >= 1")
+    rows = sum(int(soff[s + 1]) - int(soff[s]) for s in src_seg)
+    row_ptr = torch.empty(rows + 1, dtype=torch.int64, device=src.device)
+    plan = c_void_p()
+    check(_lib.load().cs_radius_pairs(ptr(src), i64_array(soff), ptr(tgt), i64_array(toff), i32_array(src_seg),
+                                      i32_array(tgt_seg), len(src_seg), float(radius), int(k or 0), ptr(row_ptr),
+                                      stream_ptr(), ctypes.byref(plan)))
+    return row_ptr, RadiusPlan(plan.value, (src, tgt))
+
+
+def radius_pairs(src, soff, tgt, toff, src_seg=None, tgt_seg=None, radius=0.03, k=None):
+    """Batched fixed-radius pairs (cs_radius_pairs): f64 [n,3] device points, host offset lists, per-problem segment
+    ids (default: problem p uses segment p of both).  Returns the CSR (row_ptr int64 [rows+1], tgt_idx int32 [total])
+    over the source rows of all problems, targets local to their segment, each row in ascending (d2, index), at most
+    k per row.  One host wait (the total)."""
+    row_ptr, plan = radius_pairs_begin(src, soff, tgt, toff, src_seg, tgt_seg, radius, k)
+    total = int(_lib.to_host(row_ptr[-1:])[0][0])
+    return row_ptr, plan.fill(row_ptr, total)
+
+
+def sample_pairs(xyz, offsets, base_seg, pos_seg, neg_seg, slots, row_base, row_ptr, tgt_idx, lists, seed, round_,
+                 radius, sample, out=None):
+    """cs_sample_pairs: PiP (lists & 1) and / or PiN + NiN (lists & 2) of every problem into fixed-capacity buffers.
+    xyz f32 [n,3] device (kept canonical points), offsets / *_seg / slots / row_base host lists.  `out` = (pip, pin,
+    nin, counts) from an earlier call to complete (the other lists); returns that tuple: int32 [P * sample, 2] each,
+    counts int32 [P, 4] = {n_pos, PiP, PiN, NiN}."""
+    xyz = _dev(xyz, torch.float32, "points").contiguous()
+    n_prob = len(base_seg)
+    dev = xyz.device
+    if out is None:
+        out = tuple(torch.zeros((n_prob * sample, 2), dtype=torch.int32, device=dev) for _ in range(3)) + (
+            torch.zeros((n_prob, 4), dtype=torch.int32, device=dev),)
+    pip, pin, nin, counts = out
+    if tgt_idx is not None and tgt_idx.numel() == 0:   # no pair at all: never read, but must not be NULL
+        tgt_idx = torch.zeros(1, dtype=torch.int32, device=dev)
+    check(_lib.load().cs_sample_pairs(ptr(xyz), i64_array(offsets), i32_array(base_seg), i32_array(pos_seg),
+                                      i32_array(neg_seg), i32_array(slots), n_prob, i64_array(row_base), ptr(row_ptr),
+                                      ptr(tgt_idx), int(lists), int(seed) & 0xFFFFFFFFFFFFFFFF, int(round_),
+                                      float(radius), int(sample), ptr(pip), ptr(pin), ptr(nin), ptr(counts),
+                                      stream_ptr()))
+    return out
+
+
+def transform_f64(xyz, offsets, seg, T):
+    """cs_transform_f64: segments seg of xyz (f32 [n,3] device, host offsets) concatenated, each mapped by its f64
+    4x4 T[p] (device [P,4,4]) as ((r0 x + r1 y) + r2 z) + t in f64.  Returns f64 [sum, 3]."""
+    xyz = _dev(xyz, torch.float32, "points").contiguous()
+    T = _dev(T, torch.float64, "transforms").contiguous()
+    if T.shape[0] != len(seg):
+        raise ValueError("transform_f64: one transform per segment")
+    total = sum(int(offsets[s + 1]) - int(offsets[s]) for s in seg)
+    out = torch.empty((max(total, 1), 3), dtype=torch.float64, device=xyz.device)
+    check(_lib.load().cs_transform_f64(ptr(xyz), i64_array(offsets), i32_array(seg), len(seg), ptr(T), ptr(out),
+                                       stream_ptr()))
+    return out[:total]

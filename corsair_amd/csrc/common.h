@@ -114,6 +114,17 @@ __host__ __device__ static inline uint64_t hash64(uint64_t k) {
 }
 static constexpr uint64_t kEmptyKey = ~0ULL;
 
+// Counter-based generator (splitmix64 finaliser of a Weyl sequence), shared by RANSAC's sampling and the
+// training-pair sampler (pairs.hip):  x = seed + 0x9E3779B97F4A7C15 * (64 itr + j + 1)  (mod 2^64), then
+// x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27; x *= 0x94D049BB133111EB; x ^= x >> 31.
+__host__ __device__ static inline uint64_t rng_u64(uint64_t seed, uint64_t itr, uint64_t j) {
+  uint64_t x = seed + 0x9E3779B97F4A7C15ULL * (itr * 64ULL + j + 1ULL);
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ULL;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBULL;
+  x = x ^ (x >> 31);
+  return x;
+}
+
 // LDS-DMA of 64 x 16 B (global_load_lds_dwordx4): lane l's 16 bytes at g land at LDS byte address
 // lds_addr + 16 l (lds_addr wave-uniform, in an SGPR).  Written as inline asm ON PURPOSE: behind the
 // __builtin_amdgcn_global_load_lds form hipcc (ROCm 7.2) treats the DMA as a pending LDS write that may

@@ -83,13 +83,7 @@ __device__ __forceinline__ RansacProb prob_view(const RansacProb* probs, int p) 
   return v;
 }
 
-__host__ __device__ static inline uint64_t rng_u64(uint64_t seed, uint64_t itr, uint64_t j) {
-  uint64_t x = seed + 0x9E3779B97F4A7C15ULL * (itr * 64ULL + j + 1ULL);
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ULL;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBULL;
-  x = x ^ (x >> 31);
-  return x;
-}
+// rng_u64: common.h
 __host__ __device__ static inline uint32_t rng_index(uint64_t seed, uint64_t itr, uint64_t j,
                                                      uint32_t m) {
   return (uint32_t)(((rng_u64(seed, itr, j) >> 32) * (uint64_t)m) >> 32);

@@ -37,3 +37,19 @@ def chamfer_1direction_transformed(pc0, T, pc1):
 def chamfer_kdtree_1direction(pc0, pc1):
     """Mean distance from every pc0 point to its nearest pc1 point (utils/preprocess.py:67-70)."""
     return chamfer_1direction_transformed(pc0, np.eye(4, dtype=np.float32), pc1)
+
+
+def get_matching_indices(source_pcd, target_pcd, search_voxel_size, K=None):
+    """(base, match) index tuples of every source / target pair closer than search_voxel_size
+    (utils/preprocess.py:207-228): source rows ascending, within a row by ascending distance (ties: smaller target
+    index), at most K per row.  One cs_radius_pairs launch instead of a KD-tree query per point."""
+    s = np.ascontiguousarray(np.asarray(source_pcd, dtype=np.float64).reshape(-1, 3))
+    t = np.ascontiguousarray(np.asarray(target_pcd, dtype=np.float64).reshape(-1, 3))
+    if K is not None and K <= 0:
+        return []
+    dev = torch.device("cuda")
+    row_ptr, idx = B.radius_pairs(torch.from_numpy(s).to(dev), [0, len(s)], torch.from_numpy(t).to(dev),
+                                  [0, len(t)], radius=search_voxel_size, k=K)
+    rp = row_ptr.cpu().numpy()
+    base = np.repeat(np.arange(len(s)), np.diff(rp))
+    return list(zip(base.tolist(), idx.cpu().numpy().tolist()))

@@ -334,6 +334,67 @@ int cs_corr_assemble(const float* d_xyz0, const float* d_xyz1, const int64_t* d_
                      const int64_t* d_desc, int n_cfg, int64_t max_len, float* d_src, float* d_tgt, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Training batches (datasets/CategoryDataset.py:121-296 builds one triplet at a time on the host).
+ *
+ * Fixed-radius pairs.  Replaces utils/preprocess.py:207-228 get_matching_indices (an Open3D KDTreeFlann
+ * search_radius_vector_3d per source point, run from a Python loop), as generate_local_pair
+ * (datasets/CategoryDataset.py:121-151) calls it.  Segments as cs_knn_feat: problem p searches source segment
+ * h_src_seg[p] of (d_src, h_soff) against target segment h_tgt_seg[p] of (d_tgt, h_toff); points f64 [n,3].
+ * Pair (i, j) is kept iff d2 < r2 with d2 = ((sx-tx)^2 + (sy-ty)^2) + (sz-tz)^2 in f64 without contraction
+ * and r2 = radius * radius.  [O3D-knowledge] Open3D's radius search compares squared distances strictly (a
+ * target at exactly r is not returned) and returns the hits sorted by distance; it leaves the order of equal
+ * distances unspecified -- here ties are broken by ascending target index.
+ * Output CSR over the source rows of all problems (problem-major, rows ascending): d_row_ptr int64 [rows+1];
+ * row r's targets (indices LOCAL to the target segment) in ascending (d2, index), at most k_max of them
+ * (k_max <= 0: all), like idx[:K] in the reference.
+ *   cs_radius_pairs enqueues the search and the row offsets and returns a plan; it does not wait.  The caller
+ *   reads the total (d_row_ptr[rows]) to size d_tgt_idx int32 [total] -- the only host wait -- and calls
+ *   cs_radius_pairs_fill with the same d_row_ptr while d_src and d_tgt are alive and unchanged, then frees the
+ *   plan.  Rows of any length are exact and ordered.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct cs_radius_plan cs_radius_plan;
+int cs_radius_pairs(const double* d_src, const int64_t* h_soff, const double* d_tgt, const int64_t* h_toff,
+                    const int32_t* h_src_seg, const int32_t* h_tgt_seg, int n_prob, double radius, int k_max,
+                    int64_t* d_row_ptr, void* stream, cs_radius_plan** plan);
+int cs_radius_pairs_fill(const cs_radius_plan* plan, const int64_t* d_row_ptr, int32_t* d_tgt_idx, void* stream);
+void cs_radius_plan_free(cs_radius_plan* plan);
+
+/* Pair sampling of a triplet batch.  Replaces generate_rand_negative_pairs + _hash (utils/preprocess.py:231-259)
+ * and the shuffle / [:sample] of generate_local_pair (datasets/CategoryDataset.py:121-151).  d_xyz f32 [n,3] holds
+ * the kept CANONICAL points of every cloud (segments h_off); problem p is triplet slot h_slot[p] with base, positive
+ * and negative segments h_base_seg[p], h_pos_seg[p], h_neg_seg[p]; its PiP CSR rows are [h_row_base[p],
+ * h_row_base[p+1]) of (d_row_ptr, d_tgt_idx) as cs_radius_pairs made them with k_max = 0 (base -> positive).
+ * Randomness: u64 = rng(seed, slot, round, stream, ctr) = x of the generator in common.h with itr = 0 and
+ *   j = slot << 40 | round << 36 | stream << 32 | ctr, i.e.
+ *   x = seed + 0x9E3779B97F4A7C15 * (j + 1)  (mod 2^64);  x ^= x >> 30;  x *= 0xBF58476D1CE4E5B9;
+ *   x ^= x >> 27;  x *= 0x94D049BB133111EB;  x ^= x >> 31
+ * and a uniform index below N is floor(u * N) in f64 with u = (x >> 11) * 2^-53.
+ *   PiP (lists & 1, stream 0): pair t of the problem (CSR order) gets key (rng(.., 0, t) >> 32) << 32 | t; the
+ *     min(sample, n_pos) pairs of smallest key, ascending (ties of the random part by pair index).
+ *   PiN (lists & 2, stream 1): n_draw = n_pos candidates; candidate t = (index(rng(.., 1, 2t), N0),
+ *     index(rng(.., 1, 2t+1), N1)); dropped when it is a positive pair (d2 < r2 in f64, the PiP test itself --
+ *     exactly membership in the uncapped PiP set) or when sqrt((dx*dx + dy*dy) + dz*dz) <= 0.1 in f32 (NumPy's
+ *     np.linalg.norm on the f32 clouds, CategoryDataset.py:141-145); the first `sample` survivors in draw order.
+ *   NiN (lists & 2, stream 2): the same on base x negative, excluding only the pair (0, 0).
+ * d_pip / d_pin / d_nin int32 [n_prob * sample, 2]: problem p's pairs at rows [p * sample, ...), indices local to
+ * the segments.  d_counts int32 [n_prob, 4] = {n_pos, PiP, PiN, NiN} (entries of lists not asked for are left
+ * alone).  PiN / NiN need only the row offsets, so they may run before the caller's host wait for the total.
+ * 1 <= sample <= 4096, 0 <= round < 16, slot < 2^24.  No waits, no float atomics: results are bit-identical. */
+int cs_sample_pairs(const float* d_xyz, const int64_t* h_off, const int32_t* h_base_seg, const int32_t* h_pos_seg,
+                    const int32_t* h_neg_seg, const int32_t* h_slot, int n_prob, const int64_t* h_row_base,
+                    const int64_t* d_row_ptr, const int32_t* d_tgt_idx, int lists, uint64_t seed, int round,
+                    double radius, int sample, int32_t* d_pip, int32_t* d_pin, int32_t* d_nin, int32_t* d_counts,
+                    void* stream);
+
+/* Rigid transform of the train-mode augmentation in f64.  Replaces np.matmul(R, pc[:, :, None])[:, :, 0] + T of
+ * random_rotation (utils/preprocess.py:73-86) and apply_transform (:39-48) in CategoryDataset.py:229-241:
+ * out = the segments h_seg[p] of d_xyz (f32 [n,3], widened exactly), concatenated problem-major, each mapped by
+ * the row-major 4x4 d_T[p] (f64 [n_prob,16]) as x' = ((r00 x + r01 y) + r02 z) + t0 per coordinate, no
+ * contraction.  (The reference's matmul order depends on the BLAS)  Quantise with cs_voxelize_f64. */
+int cs_transform_f64(const float* d_xyz, const int64_t* h_off, const int32_t* h_seg, int n_prob, const double* d_T,
+                     double* d_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Profiling hooks for bench.py: when enabled the library brackets the launches of each named
  * kernel family with hipEvents on the launch stream and accumulates the elapsed time.
  * names: "conv", "ransac_eval", "ransac_pre", "ransac_hyp", "knn", "chamfer", "topk", "symcut",
