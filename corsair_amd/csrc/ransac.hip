@@ -4,42 +4,44 @@
 // (utils/eval_pose.py:82-100 of the reference; ransac_n = 10, 100 000 iterations, confidence 0.999).
 // Semantics: Open3D's loop as executed by ONE thread (iteration order = index order), with the
 // global Mersenne twister replaced by a counter-based generator so that iteration i of every
-// problem is reproducible anywhere.  Iterations are processed in growing chunks (256, 256, 512, ...,
-// 16 384); within a chunk
+// problem is reproducible anywhere.  Iterations are processed in rounds of growing chunks: [0, 64) (CS_RANSAC_FIRST),
+// [64, 512), then doubling -- [512, 1024), [1024, 2048), ... -- up to 16 384 per round.  The first chunk is counted
+// exactly (there is no best count to prune against yet); every later one goes through the f16 prefilter.  A round:
 //   k_ransac_hyp        one lane per hypothesis: sample ransac_n pairs (packed 32-B rows), closed-form
 //                       rigid fit (Horn quaternion; largest eigenpair of the 4x4 matrix from its characteristic
 //                       polynomial, horn_qcp, with the Jacobi eigen-solver as per-lane fallback; f64), emit R|t as f64
 //                       (Open3D keeps the Matrix4d; the f32 cast happens at the very end, where the
-//                       reference casts the result: utils/symmetry.py:274); from iteration 256 on it also emits the
+//                       reference casts the result: utils/symmetry.py:274); in a prefiltered round also the
 //                       hypothesis' prefilter row (pf_emit_row: 16 f16 coefficients + c_h)
-//   k_ransac_prefilter  (from iteration 256 on) an UPPER bound of every hypothesis' inlier count on the
+//   k_ransac_prefilter  (from the second chunk on) an UPPER bound of every hypothesis' inlier count on the
 //                       f16 matrix cores; hypotheses whose bound is below the carried best cannot
-//                       matter and get count 0.  Round 4: <1, true> = one MFMA per tile (K = 16: a_hi . b_hi',
+//                       matter and get count 0.  <1, true> = one MFMA per tile (K = 16: a_hi . b_hi',
 //                       the dropped term bounded per pair), signs counted by v_add_f32 under
-//                       round-toward-minus-infinity; 0.2 % survive, and the survivors go through the K = 32
-//                       bound (<2, false> in list mode) before the exact count.  See the block comments above
-//                       k_ransac_pack16_b0 / the kernel and DESIGN.md ("RANSAC prefilter") for the bound.
+//                       round-toward-minus-infinity; 0.2 % survive.  <2, false> = two MFMAs per tile (K = 32:
+//                       a_hi . (b_hi + b_lo)), signs through a v_alignbit history: the whole prefilter with
+//                       CS_RANSAC_PF_K=32, and always the SECOND STAGE -- the survivors of the K = 16 bound,
+//                       compacted by k_ransac_survivors, go through it (list mode) before the exact count.  See the
+//                       block comments above k_ransac_pack16_b0 / the kernel and DESIGN.md ("RANSAC prefilter").
 //   k_ransac_count      the exact count in Open3D's arithmetic: the reference hands Open3D f64 points
 //                       (utils/eval_pose.py:83-86) and Eigen transforms and compares in double, so the
 //                       inlier test is evaluated in f64: a lane owns one hypothesis (R|t in 12 f64
 //                       registers), the pairs of a 256-row stage are converted to f64 once and read
 //                       from LDS as broadcasts; p = fma(r2,sz, fma(r1,sy, fma(r0,sx, t))), d = p - q,
 //                       |d|^2 = fma(dz,dz, fma(dy,dy, dx dx)) < max_corr^2 (the canonical chain, the
-//                       oracle's).  Used for all hypotheses of the first 256 iterations and (LIST) for
-//                       long survivor lists; k_ransac_count_few handles the usual handful of survivors
-//                       (same chain, count and fixed-point error in one pass).  These kernels see
-//                       ~0.1 % of the (hypothesis, pair) work; the f16 prefilter carries the rest.
+//                       oracle's).  Used for all hypotheses of an unfiltered chunk (<false, 64> for a chunk of 64)
+//                       and (<true>) for survivor lists longer than 1024 per problem; k_ransac_count_few handles
+//                       the usual handful of survivors (same chain, count and fixed-point error in one pass).  These
+//                       kernels see ~0.1 % of the (hypothesis, pair) work; the f16 prefilter carries the rest.
 //   k_ransac_scan1      one wave per problem replays the chunk in iteration order (prefix max of the
 //                       inlier counts -> early-exit bound est_k -> stop position) and lists the
-//                       hypotheses that tie for the best count
-//   k_ransac_err        fixed-point squared error (exact integer sums) of those few candidates (only
-//                       when k_ransac_count_few has not produced it already)
+//                       hypotheses that tie for the best count.  When k_ransac_count_few has left their errors it
+//                       also picks the best of them: the usual round is hyp -> prefilter -> survivors ->
+//                       second-stage prefilter -> count_few -> scan1, six launches.  Otherwise:
+//   k_ransac_err        fixed-point squared error (exact integer sums) of those few candidates
 //   k_ransac_scan2      best = max count, then min error, then first -- the final state of the
 //                       sequential rule "better = more inliers, or equal inliers and smaller rmse"
-//                       (inside k_ransac_scan1 whenever k_ransac_count_few has left the errors: the usual round is
-//                       hyp -> prefilter -> survivors -> second-stage prefilter -> count_few -> scan1, six launches)
-// The host loop synchronises once per chunk (one pinned copy of the per-problem state); the next
-// chunk's hypotheses are already enqueued at that point.
+// The host loop (cs_ransac_batch, at the end of this file) synchronises once per round (one pinned copy of the
+// per-problem state); the next round's hypotheses and prefilter are already enqueued at that point.
 // Inlier counts and fixed-point errors are integers, so any split of the correspondence range across
 // workgroups gives identical sums.
 #include <math.h>
@@ -267,7 +269,7 @@ __global__ __launch_bounds__(256) void k_ransac_hyp(const RansacProb* probs,
                                                     const int32_t* __restrict__ xcd_prob, const XcdTab xcd_tab,
                                                     int slots, int tiles, int force_jacobi,
                                                     double* __restrict__ hyp,
-                                                    // fused prefilter rows (A16 != nullptr): what k_ransac_hyp16 computes
+                                                    // prefilter rows of the chunk (A16 != nullptr): pf_emit_row
                                                     const unsigned* __restrict__ pf_stat, const double* __restrict__ pf_sums,
                                                     double thr2, double tcap, _Float16* __restrict__ A16,
                                                     float* __restrict__ c_h, int32_t* __restrict__ cnt_zero) {
@@ -720,7 +722,7 @@ __global__ __launch_bounds__(256) void k_ransac_pack16(const RansacProb* __restr
 //   k = 1..3, 13..15 (2 R^T t, -2 t): |a| <= 2 |t| sqrt(1 + max|E|) with |t| <= tcap * smax: pf_emit_row CHECKS that and
 //     marks the other hypotheses unusable (they survive to the exact kernels).  |t| = |c_t - R c_s| can reach 2 smax, but
 //     both centroids are means of ten points of a centred object: on the bench clouds |t| / smax has median 0.2 and
-//     99.99 % of the hypotheses are below 0.8, so tcap = 0.75 (CS_RANSAC_PF_TCAP) costs 1e-4 of them and shrinks E_p 2.7x
+//     99.99 % of the hypotheses are below 0.8, so tcap = 0.75 (PF_TCAP) costs 1e-4 of them and shrinks E_p 2.7x
 // The constant term is also CENTRED: b_0 - beta with beta = smax^2 (b_0 = |s|^2 + |q|^2 lies in [0, 2 smax^2]); the
 // hypothesis side adds beta to its accumulator input.  f16 is finer near zero: the round-down costs ~6e-5 instead of 2.4e-4.
 // and |a_hi| <= |a| (1 + 2^-11).  Then  sum_k a_hi_k b'_k  <=  sum_k a_hi_k (b_hi_k + b_lo_k)  for every usable hypothesis:
@@ -784,8 +786,7 @@ __global__ __launch_bounds__(256) void k_ransac_pack16_b0(const RansacProb* __re
 // with W <= (2 smax + |t|)^2.  A hypothesis outside the f16 range (or not finite) gets c_h = -inf and
 // a zero row: every pair counts, it always survives to the exact kernel.
 // Prefilter row of one hypothesis (R, t): 16 f16 coefficients + the f32 constant c_h (see k_ransac_prefilter).  Called by
-// k_ransac_hyp16 (hypotheses read back from the table) and, fused, by k_ransac_hyp itself (round 4: one launch and one
-// 96-byte read per hypothesis less).
+// k_ransac_hyp while R and t are still in registers.
 __device__ __forceinline__ void pf_emit_row(const RansacProb& pr, int p, int h, int bmax, const double (&R)[3][3], double (&t)[3],
                                             const unsigned* __restrict__ stat, const double* __restrict__ sums, double thr2,
                                             double tcap, _Float16* __restrict__ A16, float* __restrict__ c_h) {
@@ -848,29 +849,6 @@ __device__ __forceinline__ void pf_emit_row(const RansacProb& pr, int p, int h, 
   c_h[(int64_t)p * bmax + h] = usable ? __double2float_rd((tt + beta) - (thr2 + eps)) : -1.0f;
 }
 
-__global__ void k_ransac_hyp16(const RansacProb* probs, const double* __restrict__ hyp,
-                               const unsigned* __restrict__ stat, const double* __restrict__ sums, int it0, int bcount,
-                               int bmax, double thr2, _Float16* __restrict__ A16, float* __restrict__ c_h,
-                               int32_t* __restrict__ cnt_zero, double tcap) {
-  const int p = blockIdx.y;
-  const int h = blockIdx.x * blockDim.x + threadIdx.x;
-  if (h >= bcount) return;
-  // the prefilter behind this kernel adds the partial counts of its pair-range splits with atomics: the
-  // counters of this round are cleared here (a hipMemset2DAsync per round before)
-  if (cnt_zero) cnt_zero[(int64_t)p * bmax + h] = 0;
-  const RansacProb pr = prob_view(probs, p);
-  if (pr.done || it0 + h >= pr.est_k) return;
-  const double* hp = hyp + ((int64_t)p * 12) * bmax + h;
-  double R[3][3], t[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-#pragma unroll
-    for (int b = 0; b < 3; ++b) R[a][b] = hp[(int64_t)(4 * a + b) * bmax];
-    t[a] = hp[(int64_t)(4 * a + 3) * bmax];
-  }
-  pf_emit_row(pr, p, h, bmax, R, t, stat, sums, thr2, tcap, A16, c_h);
-}
-
 // Upper bounds of the inlier counts.
 // grid: 1-D, 8 * slots * tiles * splits workgroups.  Workgroups are dealt round-robin to the 8 XCDs, so
 // XCD x = id % 8 is given the problems xcd_prob[x][0..slots) (host: longest-first balancing): all
@@ -884,14 +862,14 @@ __global__ void k_ransac_hyp16(const RansacProb* probs, const double* __restrict
 // 15 LDS-DMA instructions of 1 KiB (global_load_lds_dwordx4: no staging registers, no ds_write); the
 // copy of stage s+1 is in flight while stage s is computed.
 //
-// Inner loop: units k = (row tile t, hypothesis group g), 12 per stage.  The two MFMAs of unit k are
+// Inner loop: units k = (row tile t, hypothesis group g), 12 per stage.  K = 32 (<2, false>): the two MFMAs of unit k are
 // issued interleaved with the sign extraction (16 x v_alignbit into a per-lane history word, one VALU
 // op per pair) of unit k-2, held in another of three rotating accumulator sets: a result is first
 // read a whole unit (>= 64 cycles) after the MFMA that wrote it, beyond the 11 wait states the
 // hardware requires.  The VALU side is the longer one (v_alignbit_b32 issues every ~4.5 cycles per
 // SIMD, tools/ubench/valu_rate.hip: 16 x 4.5 = 72 cycles against 64 for the MFMAs).  The unit is one asm block: the compiler's scheduler does not keep this order
 // (it hoists the dependent VALU ops and pays s_nop 10 per unit).
-// RTN (with NM = 1): the signs are counted by the results THEMSELVES -- under round-toward-minus-infinity (MODE.fp_round)
+// K = 16 (<1, true>, RTN): the signs are counted by the results THEMSELVES -- under round-toward-minus-infinity (MODE.fp_round)
 // and with a counter in [2^63, 2^64), whose ulp is 2^40, `v_add_f32 cnt, acc, cnt` subtracts exactly 2^40 iff acc < 0 for
 // any |acc| < 2^40 (tools/ubench/rtn_count.hip: edge cases incl. -0 and denormals) -- one FULL-RATE VALU op per result
 // instead of a 4.5-cycle v_alignbit.  Full-rate ops do not overlap with the matrix pipe, but the K = 16 unit has only one
@@ -926,7 +904,7 @@ __global__ __launch_bounds__(256) void k_ransac_prefilter(const RansacProb* prob
   const RansacProb pr = prob_view(probs, p);
   if (pr.done) return;
   // n_list: the hypotheses are a COMPACT per-problem list of n_list[p] rows (second stage over the survivors: rows
-  // gathered by k_ransac_stage2_gather, bmax = its row capacity) instead of the iterations it0 .. it0 + bcount of a chunk
+  // compacted by k_ransac_survivors, bmax = its row capacity) instead of the iterations it0 .. it0 + bcount of a chunk
   if (n_list) bcount = min(n_list[p], bmax);
   const int ek_rel = n_list ? 0x7fffffff : pr.est_k - it0;   // hypotheses at or beyond it are past the iteration bound
   if (tile * PF_HYP >= ek_rel || tile * PF_HYP >= bcount) return;
@@ -955,7 +933,7 @@ __global__ __launch_bounds__(256) void k_ransac_prefilter(const RansacProb* prob
   const int per = ((mpad / PF_ROWS + splits - 1) / splits) * PF_ROWS;
   const int beg = split * per;
   const int end = min(mpad, beg + per);
-  static_assert(!RTN || NM == 1, "the add-based sign count is written for the one-MFMA unit");
+  static_assert(RTN == (NM == 1), "two forms: <1, true> = K 16 with the add-based sign count, <2, false> = K 32 with the sign history");
   unsigned bits[PF_NG];
   int cnt[PF_NG];
   constexpr float RTN_C0 = 0x1p64f - 0x1p40f;   // 2^64 - 2^40: all 24 significand bits set, ulp 2^40
@@ -982,31 +960,6 @@ __global__ __launch_bounds__(256) void k_ransac_prefilter(const RansacProb* prob
   static_assert(PF_NG == 2 && PF_ROWS == 192, "the unrolled schedule below is written for 12 units per stage");
   const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   f32x16 S0, S1 = zero16, S2 = zero16;  // +0: the first two (dummy) extractions shift in zeros
-#define PF_UNIT1(DST, SRC, G, A, COUNT) \
-  asm volatile( \
-      "v_mfma_f32_32x32x16_f16 %0, %2, %3, %4\n\t" \
-      "v_alignbit_b32 %1, %1, %5, 31\n\t" \
-      "v_alignbit_b32 %1, %1, %6, 31\n\t" \
-      "v_alignbit_b32 %1, %1, %7, 31\n\t" \
-      "v_alignbit_b32 %1, %1, %8, 31\n\t" \
-      "v_alignbit_b32 %1, %1, %9, 31\n\t" \
-      "v_alignbit_b32 %1, %1, %10, 31\n\t" \
-      "v_alignbit_b32 %1, %1, %11, 31\n\t" \
-      "v_alignbit_b32 %1, %1, %12, 31\n\t" \
-      "v_alignbit_b32 %1, %1, %13, 31\n\t" \
-      "v_alignbit_b32 %1, %1, %14, 31\n\t" \
-      "v_alignbit_b32 %1, %1, %15, 31\n\t" \
-      "v_alignbit_b32 %1, %1, %16, 31\n\t" \
-      "v_alignbit_b32 %1, %1, %17, 31\n\t" \
-      "v_alignbit_b32 %1, %1, %18, 31\n\t" \
-      "v_alignbit_b32 %1, %1, %19, 31\n\t" \
-      "v_alignbit_b32 %1, %1, %20, 31" \
-      : "=&v"(DST), "+v"(bits[G]) \
-      : "v"(A[0]), "v"(bop[G]), \
-        "v"(cin[G]), "v"(SRC[0]), "v"(SRC[1]), "v"(SRC[2]), "v"(SRC[3]), "v"(SRC[4]), "v"(SRC[5]), \
-        "v"(SRC[6]), "v"(SRC[7]), "v"(SRC[8]), "v"(SRC[9]), "v"(SRC[10]), "v"(SRC[11]), \
-        "v"(SRC[12]), "v"(SRC[13]), "v"(SRC[14]), "v"(SRC[15])); \
-  if (COUNT) cnt[G] += __popc(bits[G]);
 #define PF_UNIT2(DST, SRC, G, A, COUNT) \
   asm volatile( \
       "v_mfma_f32_32x32x16_f16 %0, %2, %4, %6\n\t" \
@@ -1060,9 +1013,6 @@ __global__ __launch_bounds__(256) void k_ransac_prefilter(const RansacProb* prob
 #define PF_UNIT(DST, SRC, G, A, COUNT)            \
   if constexpr (NM == 2) {                        \
     PF_UNIT2(DST, SRC, G, A, COUNT)               \
-  } else if constexpr (RTN) {                     \
-  } else {                                        \
-    PF_UNIT1(DST, SRC, G, A, COUNT)               \
   }
 #define PF_LOAD(A, TILE)                                                                          \
   {                                                                                               \
@@ -1145,7 +1095,6 @@ __global__ __launch_bounds__(256) void k_ransac_prefilter(const RansacProb* prob
   }
 #undef PF_UNIT
 #undef PF_UNITR
-#undef PF_UNIT1
 #undef PF_UNIT2
 #undef PF_LOAD
   if (trace && lane == 0) {
@@ -1208,7 +1157,6 @@ struct Stage2Rows {
   _Float16* A16s;
   float* c_hs;
   int32_t* cnt2;
-  int32_t* n_surv2;
 };
 // Survivors: hypotheses whose upper bound reaches the carried best count.  The others get count 0.
 __global__ void k_ransac_survivors(const RansacProb* __restrict__ probs, const int32_t* __restrict__ cnt_up,
@@ -1217,7 +1165,6 @@ __global__ void k_ransac_survivors(const RansacProb* __restrict__ probs, const i
                                    int32_t* __restrict__ hlist, int32_t* __restrict__ n_surv, const Stage2Rows s2) {
   const int p = blockIdx.y;
   const int h = blockIdx.x * blockDim.x + threadIdx.x;
-  if (h == 0 && s2.A16s) s2.n_surv2[p] = 0;
   if (h >= bcount) return;
   const RansacProb pr = probs[p];
   if (pr.done || it0 + h >= pr.est_k) return;
@@ -1242,23 +1189,7 @@ __global__ void k_ransac_survivors(const RansacProb* __restrict__ probs, const i
 // ---- second stage (round 4): the K = 16 bound leaves 3 - 4x the survivors of the K = 32 bound; the survivors of a round --
 // a compact list of ~16 hypotheses per problem -- go through the K = 32 form (a_hi . (b_hi + b_lo), same a_hi rows, same
 // eps_h) before they are counted exactly.  1.5 % of the matrix work of a first-stage launch.
-// survivors of the second stage: hlist2 = the entries of hlist whose K = 32 bound still reaches the carried best count
-__global__ void k_ransac_stage2_survivors(const RansacProb* __restrict__ probs, const int32_t* __restrict__ hlist,
-                                          const int32_t* __restrict__ n_surv, int bmax, const int32_t* __restrict__ cnt2,
-                                          int32_t* __restrict__ hlist2, int32_t* __restrict__ n_surv2,
-                                          unsigned long long* __restrict__ total2) {
-  const int p = blockIdx.y;
-  const int slot = blockIdx.x * blockDim.x + threadIdx.x;
-  const RansacProb pr = probs[p];
-  if (pr.done) return;
-  if (slot >= n_surv[p]) return;
-  // entries beyond the capacity of the compact list were not looked at by the second stage: they pass unfiltered
-  if (slot >= PF_S2_CAP || cnt2[(int64_t)p * PF_S2_CAP + slot] >= pr.best_cnt) {
-    const int o = atomicAdd(&n_surv2[p], 1);
-    hlist2[(int64_t)p * bmax + o] = hlist[(int64_t)p * bmax + slot];
-    atomicAdd(total2, 1ULL);
-  }
-}
+// The list is not compacted again: k_ransac_count_few skips the entries whose K = 32 bound is below the carried best count.
 
 // Debug check (CS_RANSAC_CHECK=1): the bound must dominate the exact count of every hypothesis.
 __global__ void k_ransac_check_bound(const RansacProb* __restrict__ probs, const int32_t* __restrict__ exact,
@@ -1304,8 +1235,8 @@ __global__ __launch_bounds__(256) void k_ransac_count_few(const RansacProb* __re
                                                           unsigned long long* __restrict__ err_by_h,
                                                           const int32_t* __restrict__ hlist,
                                                           const int32_t* __restrict__ n_surv, int list_stride,
-                                                          // fused k_ransac_stage2_survivors (cnt2 != nullptr): entry c of the
-                                                          // first-stage list is skipped when its second-stage bound is below the best
+                                                          // second stage (cnt2 != nullptr): entry c of the first-stage list is
+                                                          // skipped when its K = 32 bound is below the best
                                                           const int32_t* __restrict__ cnt2) {
   const int p = blockIdx.y;
   const RansacProb pr = probs[p];
@@ -1628,8 +1559,12 @@ __global__ void k_ransac_finish(const RansacProb* __restrict__ probs, int n_prob
 
 using namespace cs;
 
-// page-locked host staging buffer of the calling thread (grown on demand, freed at thread exit)
 namespace {
+// prefilter diagnostics: {bound violations, hypotheses checked, sum of (bound - exact)} from
+// CS_RANSAC_CHECK runs, {survivors, hypotheses evaluated} always
+std::atomic<unsigned long long> g_pf_stats[5];  // zero-initialised (static storage)
+
+// page-locked host staging buffer of the calling thread (grown on demand, freed at thread exit)
 struct PinnedScratch {
   char* p = nullptr;
   size_t n = 0;
@@ -1650,11 +1585,570 @@ char* pinned_scratch(size_t bytes) {
   }
   return t_pinned.p;
 }
-}  // namespace
 
-// prefilter diagnostics: {bound violations, hypotheses checked, sum of (bound - exact)} from
-// CS_RANSAC_CHECK runs, {survivors, hypotheses evaluated} always
-static std::atomic<unsigned long long> g_pf_stats[5];  // zero-initialised (static storage)
+// Largest chunk of iterations per round.  One workgroup = 128 hypotheses x all pairs of a problem
+// (~100 us), 1536 workgroups are resident: chunks of 16384 give >= 8 "waves" of workgroups for a
+// 32-query batch, so the partially filled last wave costs ~10 % instead of ~33 % at 4096.
+constexpr int BMAX = 16384;
+// K = 16 form: largest |t| / smax a hypothesis may have to go through the prefilter; the others are counted exactly
+// (k_ransac_pack16_b0 has the measurement behind the value).  The K = 32 form has no cap: its kernels get tcap = 0.
+constexpr double PF_TCAP = 0.75;
+// Survivors per problem up to which k_ransac_count_few does the exact counts; longer lists go to k_ransac_count<true>.
+// (K = 32 prefilter: 32 / 64 / 128 / 256 measured, 128 the fastest by ~1 %.  The K = 16 form leaves 3 - 4x the survivors,
+// ~16 per problem and round on the chair shape: the list kernel -- one workgroup of 256 hypothesis lanes per problem --
+// then ran in every fourth round at 670 us.)
+constexpr int FEW_MAX = 1024;
+
+// The environment knobs of cs_ransac_batch.  All of them are read HERE, once per call: tests flip them between calls
+// of one process, so none is cached.  INTEGRATION.md lists them.
+struct Options {
+  bool prefilter;          // CS_RANSAC_PREFILTER=0: exact-only RANSAC (the reference path of the identity tests)
+  bool check;              // CS_RANSAC_CHECK=1: verify the bound against the exact count of EVERY hypothesis (slow; tests)
+  int pf_nm;               // CS_RANSAC_PF_K=32: 2 = the two-MFMA form a_hi . (b_hi + b_lo); default 16: 1 = one MFMA,
+                           // a_hi . b_hi' with the dropped term bounded per pair.  Same results (the exact kernels decide)
+  bool stage2;             // CS_RANSAC_STAGE2=0: no K = 32 second stage on the survivors of the K = 16 form
+  int first_chunk;         // CS_RANSAC_FIRST=<n>: iterations counted exactly before the prefilter starts (default 64)
+  int force_jacobi;        // CS_RANSAC_JACOBI=1: every hypothesis through the Jacobi eigen-solver (the fallback of horn_qcp;
+                           // the oracle's oc_rigid_fit_force_jacobi is its counterpart)
+  bool overlap;            // CS_RANSAC_OVERLAP=0: every round on the caller's stream
+  int trace_it0;           // CS_PF_TRACE=<it0>: per-workgroup trace of the prefilter launch of the round starting at it0
+  const char* trace_file;  // (-1 = off), written to CS_PF_TRACE_FILE (tools/pf_trace.py)
+};
+Options read_options() {
+  const char* pf = getenv("CS_RANSAC_PREFILTER");
+  const char* ck = getenv("CS_RANSAC_CHECK");
+  const char* k = getenv("CS_RANSAC_PF_K");
+  const char* s2 = getenv("CS_RANSAC_STAGE2");
+  const char* first = getenv("CS_RANSAC_FIRST");
+  const char* jac = getenv("CS_RANSAC_JACOBI");
+  const char* ov = getenv("CS_RANSAC_OVERLAP");
+  const char* tr = getenv("CS_PF_TRACE");
+  const char* trf = getenv("CS_PF_TRACE_FILE");
+  Options o;
+  o.prefilter = !(pf && pf[0] == '0');
+  o.check = ck && ck[0] == '1';
+  o.pf_nm = (k && atoi(k) == 32) ? 2 : 1;
+  o.stage2 = !(s2 && s2[0] == '0');
+  // The unfiltered chunk costs its hypotheses x ALL pairs in f64 (0.31 ms per 48-problem call at 256, twice per chair step);
+  // with 64 the second chunk, [64, 512), is already prefiltered -- against the best of 64 hypotheses instead of 256, which
+  // lets a few more of its hypotheses through to the exact kernels.  Results are the sequential loop's either way.
+  // Clamped: a first chunk above BMAX would index the BMAX-sized scratch out of range, 0 would never advance the chunk loop.
+  o.first_chunk = ((std::min(std::max(first ? atoi(first) : 64, 64), BMAX) + 63) / 64) * 64;
+  o.force_jacobi = jac && atoi(jac) != 0;
+  o.overlap = !(ov && ov[0] == '0');
+  o.trace_it0 = tr ? atoi(tr) : -1;
+  o.trace_file = trf ? trf : "/tmp/pf_trace.bin";
+  return o;
+}
+
+// Every device buffer of a call, and the views of the buffers that exist once per round parity.
+struct Scratch {
+  int n_prob = 0;
+  // per-round state in ONE block, so a round ends with one device->host copy (into pinned memory):
+  // [RansacProb x n_prob | 2 x { n_surv int32 x n_prob (padded to 8 B) | n_active int32 (8 B) }]: the counters
+  // exist once per round parity, the last scan kernel of a round clears the set of the next round
+  size_t st_probs = 0, st_surv = 0, st_cnt = 0, st_bytes = 0;
+  PoolBuf<char> state;
+  char* h_state = nullptr;                 // the thread's pinned staging buffer (not owned)
+  PoolBuf<float> pk;                       // SoA copy of the correspondences
+  PoolBuf<float4> pair32;                  // 32-B rows for the sampling
+  PoolBuf<double> hyp;                     // hypotheses (f64 R|t), one set per round parity
+  PoolBuf<int32_t> res_cnt, cand;
+  PoolBuf<unsigned long long> cand_err;
+  // prefilter: f16 pair image (every problem padded to whole LDS stages), hypothesis rows, bounds, survivor lists
+  PoolBuf<int64_t> off16;
+  PoolBuf<_Float16> B16, A16;
+  PoolBuf<float> c_h;
+  PoolBuf<int32_t> cnt_up, hlist;
+  PoolBuf<unsigned> pf_stat;
+  PoolBuf<double> pf_sums;
+  // second stage: K = 32 image, the compacted rows of the survivors, their bounds
+  PoolBuf<_Float16> B32, A16s;
+  PoolBuf<float> c_hs;
+  PoolBuf<int32_t> cnt2;
+  PoolBuf<unsigned> pf_stat2;              // (the K = 32 pack writes the same statistics again: scratch)
+  PoolBuf<int32_t> exact_dbg;              // CS_RANSAC_CHECK
+  PoolBuf<unsigned long long> chk_stats;
+  PoolBuf<int32_t> xcd_buf;                // placement tables, one per round parity (8 x n_prob entries each)
+  PoolBuf<unsigned long long> trace;       // CS_PF_TRACE
+  size_t trace_cap = 1;
+
+  bool alloc(int n, int64_t tot1, int64_t rows16, int pf_nm, bool pf, bool stage2, bool check, bool tracing) {
+    n_prob = n;
+    st_probs = sizeof(RansacProb) * (size_t)n;
+    st_surv = ((sizeof(int32_t) * (size_t)n + 7) / 8) * 8;
+    st_cnt = st_surv + 8;
+    st_bytes = st_probs + 2 * st_cnt;
+    h_state = pinned_scratch(st_bytes);
+    const size_t nb = (size_t)n * BMAX, ns2 = (size_t)n * PF_S2_CAP;
+    if (tracing) trace_cap = (size_t)8 * n * 64 * 16 * 16;
+    return h_state && state.alloc(st_bytes) && pk.alloc((size_t)tot1 * 6) && pair32.alloc((size_t)tot1 * 2) &&
+           hyp.alloc(2 * nb * 12) && res_cnt.alloc(nb) && cand.alloc(nb) && cand_err.alloc(nb) && off16.alloc(n + 1) &&
+           B16.alloc(pf ? (size_t)rows16 * pf_pitch(pf_nm) : 8) && A16.alloc(pf ? 2 * nb * PF_K : 8) &&
+           c_h.alloc(pf ? 2 * nb : 1) && cnt_up.alloc(pf ? 2 * nb : 1) && hlist.alloc(pf ? nb : 1) &&
+           pf_stat.alloc((size_t)n * PF_STAT) && pf_sums.alloc((size_t)n * 6) &&
+           B32.alloc(stage2 ? (size_t)rows16 * PF_PITCH : 8) && A16s.alloc(stage2 ? ns2 * PF_K : 8) &&
+           c_hs.alloc(stage2 ? ns2 : 1) && cnt2.alloc(stage2 ? ns2 : 1) && pf_stat2.alloc((size_t)n * PF_STAT) &&
+           exact_dbg.alloc(check ? nb : 1) && chk_stats.alloc(4) && xcd_buf.alloc((size_t)16 * n) && trace.alloc(trace_cap);
+  }
+  RansacProb* probs() const { return reinterpret_cast<RansacProb*>(state.p); }
+  // counters of a round parity, device and host copy
+  int32_t* nsurv(int par) const { return reinterpret_cast<int32_t*>(state.p + st_probs + par * st_cnt); }
+  int* nactive(int par) const { return reinterpret_cast<int*>(state.p + st_probs + par * st_cnt + st_surv); }
+  const int32_t* h_nsurv(int par) const { return reinterpret_cast<const int32_t*>(h_state + st_probs + par * st_cnt); }
+  int h_nactive(int par) const { return *reinterpret_cast<const int*>(h_state + st_probs + par * st_cnt + st_surv); }
+  // buffers of a round parity
+  double* hyp_of(int par) const { return hyp.p + (size_t)par * n_prob * 12 * BMAX; }
+  _Float16* A16_of(int par) const { return A16.p + (size_t)par * n_prob * BMAX * PF_K; }
+  float* c_h_of(int par) const { return c_h.p + (size_t)par * n_prob * BMAX; }
+  int32_t* cnt_up_of(int par) const { return cnt_up.p + (size_t)par * n_prob * BMAX; }
+  int32_t* xcd_of(int par) const { return xcd_buf.p + (size_t)par * 8 * n_prob; }
+};
+
+struct Event {
+  hipEvent_t e = nullptr;
+  ~Event() {
+    if (e) (void)hipEventDestroy(e);
+  }
+};
+// an error return must not hand the scratch buffers back to the pool while a side stream still uses
+// them; on the normal path the final wait on the main stream is already ordered behind its events
+struct SideDrain {
+  hipStream_t st = nullptr;
+  bool clean = false;
+  ~SideDrain() {
+    if (st && !clean) (void)hipStreamSynchronize(st);
+  }
+};
+
+// The front half of one round, as enqueued: what the back half needs to know about it.
+struct Front {
+  int it0 = 0, b = 0, par = 0;
+  bool pf = false, on_side = false;
+  // placement of the round's prefilter launch (the second stage of the back half uses the same)
+  XcdTab xtab;
+  const int32_t* xcd_prob = nullptr;
+  int pslots = 1;
+};
+
+// One cs_ransac_batch call: arguments, options, scratch, streams and the state carried from round to round.
+struct RansacCall {
+  int n_prob = 0, ransac_n = 0, max_iter = 0, m_max = 0;
+  uint64_t seed = 0;
+  int64_t total = 0, tot1 = 1;
+  double thr2 = 0.0, scale = 0.0, log_1mc = 0.0, tcap = 0.0;
+  Options opt;
+  bool pf_alloc = false, stage2 = false, check = false;   // what the options come to for THIS call
+  std::vector<RansacProb> hp;                             // host copy of the per-problem state, as of the last read-back
+  std::vector<int64_t> h_off16;
+  std::vector<int32_t> h_xcd[2];
+  Scratch sc;                                             // (declared before the drains: they are destroyed first)
+  Event round_done, front_done[2], hyp_done[2];
+  hipStream_t s = nullptr, side = nullptr, side_hyp = nullptr;
+  SideDrain side_drain, side_hyp_drain;
+  int max_surv_prev = 1 << 30;  // survivors per problem in the previous prefiltered round (unknown: many)
+  unsigned long long tot_surv = 0, tot_eval = 0;
+  size_t trace_n = 0;
+
+  int init(const int64_t* h_off, int n, double max_corr, int rn, int iters, double confidence, uint64_t sd, hipStream_t st);
+  int setup(const float* d_src, const float* d_tgt);
+  int open_streams();
+  bool prefiltered(int it0) const { return pf_alloc && it0 >= opt.first_chunk; }
+  // chunks: [0, first) counted exactly, [first, 512) in one piece, then doubling ([512, 1024), [1024, 2048), ...) up to BMAX
+  int chunk_of(int it0) const {
+    const int b = it0 < opt.first_chunk ? opt.first_chunk : it0 < 512 ? 512 - it0 : (it0 < BMAX ? it0 : BMAX);
+    return b > max_iter - it0 ? max_iter - it0 : b;
+  }
+  // pair-range splits of the exact count of a whole chunk: enough workgroups for 256 CUs x several waves; the
+  // correspondence range is split when the chunk is small (integer partial sums combine exactly)
+  int chunk_splits(int tiles) const {
+    int splits = (int)(4096 / ((int64_t)n_prob * tiles > 0 ? (int64_t)n_prob * tiles : 1));
+    if (splits < 1) splits = 1;
+    if (splits > 16) splits = 16;
+    while (splits > 1 && m_max / splits < 4 * RC_CHUNK) --splits;
+    return splits;
+  }
+  int place(int it0, int par, int* live);
+  Front enqueue_front(int it0, int par, hipStream_t st);
+  int back_half(const Front& cur);
+  int count_chunk(const Front& cur, double eval_pairs);
+  int count_survivors(const Front& cur, bool* err_known);
+  bool read_back(const Front& cur);
+  int finish(float* d_T, int32_t* d_inliers, double* d_rmse, int32_t* d_iters);
+};
+
+// Problem table, derived constants, options and scratch.
+int RansacCall::init(const int64_t* h_off, int n, double max_corr, int rn, int iters, double confidence, uint64_t sd,
+                     hipStream_t st) {
+  n_prob = n;
+  ransac_n = rn;
+  max_iter = iters;
+  seed = sd;
+  s = st;
+  total = h_off[n_prob] - h_off[0];
+  tot1 = total ? total : 1;
+  hp.resize(n_prob);
+  h_off16.assign(n_prob + 1, 0);
+  for (int p = 0; p < n_prob; ++p) {
+    int64_t m = h_off[p + 1] - h_off[p];
+    CS_REQUIRE(m >= 0 && m < (1LL << 24), CS_ERR_INVALID,
+               "cs_ransac_batch: bad segment %d (a problem holds fewer than 2^24 correspondences)", p);
+    RansacProb& pr = hp[p];
+    memset(&pr, 0, sizeof(pr));
+    pr.off = h_off[p];
+    pr.m = (int32_t)m;
+    pr.est_k = max_iter;
+    pr.best_itr = -1;
+    // Open3D returns the default (identity) result when there are fewer pairs than ransac_n
+    pr.done = m < ransac_n ? 1 : 0;
+    if (m > m_max) m_max = (int)m;
+    h_off16[p + 1] = h_off16[p] + pf_padded(m);
+  }
+  // squared threshold (Open3D: max_correspondence_distance * max_correspondence_distance in double) and
+  // the power-of-two fixed-point scale of the inlier error: terms d^2 * scale < 2^38, so the u64 sum over
+  // a problem's (< 2^24) pairs cannot overflow and is exact in any order
+  thr2 = max_corr * max_corr;
+  int ex = 0;
+  (void)frexp(thr2, &ex);
+  scale = ldexp(1.0, 38 - ex);
+  log_1mc = log(1.0 - confidence);  // -inf when confidence == 1: never exits early
+  opt = read_options();
+  // the prefilter needs pairs and at least one iteration behind the exactly counted first chunk
+  pf_alloc = opt.prefilter && total > 0 && max_iter > opt.first_chunk;
+  stage2 = pf_alloc && opt.pf_nm == 1 && opt.stage2;
+  check = pf_alloc && opt.check;   // (no prefiltered round, nothing to check)
+  tcap = opt.pf_nm == 2 ? 0.0 : PF_TCAP;
+  const bool ok = sc.alloc(n_prob, tot1, h_off16[n_prob] ? h_off16[n_prob] : 1, opt.pf_nm, pf_alloc, stage2, check,
+                           opt.trace_it0 >= 0);
+  CS_REQUIRE(ok, CS_ERR_HIP, "cs_ransac_batch: scratch allocation failed");
+  return CS_OK;
+}
+
+// Uploads the problem table and builds what every round reads: the packed pairs and, for the prefilter, the pair sums
+// and the f16 images.
+int RansacCall::setup(const float* d_src, const float* d_tgt) {
+  // problems + zeroed counters in one upload (h_state is page-locked and not read before the first round ends)
+  memset(sc.h_state, 0, sc.st_bytes);
+  memcpy(sc.h_state, hp.data(), sc.st_probs);
+  CS_HIP_CHECK(hipMemcpyAsync(sc.state.p, sc.h_state, sc.st_bytes, hipMemcpyHostToDevice, s));
+  RansacProb* const d_probs = sc.probs();
+  if (total > 0) {
+    hipLaunchKernelGGL(k_ransac_pack, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, s,
+                       d_src, d_tgt, total, sc.pk.p, sc.pair32.p);
+    CS_LAUNCH_CHECK();
+  }
+  if (pf_alloc) {
+    CS_HIP_CHECK(hipMemsetAsync(sc.pf_stat.p, 0, sizeof(unsigned) * n_prob * PF_STAT, s));
+    CS_HIP_CHECK(hipMemsetAsync(sc.chk_stats.p, 0, sizeof(unsigned long long) * 4, s));
+    int pblocks = (int)ceil_div(m_max > 0 ? m_max : 1, 256);
+    if (pblocks > 64) pblocks = 64;
+    const dim3 pgrid((unsigned)pblocks, (unsigned)n_prob);
+    CS_HIP_CHECK(hipMemcpyAsync(sc.off16.p, h_off16.data(), sizeof(int64_t) * (n_prob + 1),
+                                hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_ransac_pair_sums, dim3((unsigned)n_prob), dim3(256), 0, s, d_probs, d_src, d_tgt, sc.pf_sums.p);
+    hipLaunchKernelGGL(opt.pf_nm == 2 ? k_ransac_pack16<2> : k_ransac_pack16<1>, pgrid, dim3(256), 0, s,
+                       d_probs, sc.off16.p, d_src, d_tgt, sc.pf_sums.p, sc.B16.p, sc.pf_stat.p);
+    if (opt.pf_nm == 1)   // K = 16: the per-pair bound of the dropped term goes into the constant term
+      hipLaunchKernelGGL(k_ransac_pack16_b0, pgrid, dim3(256), 0, s,
+                         d_probs, sc.off16.p, d_src, d_tgt, sc.pf_sums.p, sc.pf_stat.p, tcap, sc.B16.p);
+    if (stage2) {
+      CS_HIP_CHECK(hipMemsetAsync(sc.pf_stat2.p, 0, sizeof(unsigned) * n_prob * PF_STAT, s));
+      hipLaunchKernelGGL(k_ransac_pack16<2>, pgrid, dim3(256), 0, s,
+                         d_probs, sc.off16.p, d_src, d_tgt, sc.pf_sums.p, sc.B32.p, sc.pf_stat2.p);
+    }
+    CS_LAUNCH_CHECK();
+  }
+  if (opt.trace_it0 >= 0) CS_HIP_CHECK(hipMemsetAsync(sc.trace.p, 0, sizeof(unsigned long long) * sc.trace_cap, s));
+  return CS_OK;
+}
+
+// Events and the two side streams of the pipelined rounds (see cs_ransac_batch).
+int RansacCall::open_streams() {
+  for (Event* ev : {&round_done, &front_done[0], &front_done[1], &hyp_done[0], &hyp_done[1]})
+    CS_HIP_CHECK(hipEventCreateWithFlags(&ev->e, hipEventDisableTiming));
+  side = opt.overlap ? side_stream() : nullptr;
+  // the hypotheses of a side-stream front half go to a THIRD stream: those of round i+2 are enqueued when round i
+  // is known (their buffers, one set per parity, are free then) and run UNDER the prefilter of round i+1 instead of
+  // behind it on the same stream (f64 vector work beside f16 matrix work)
+  side_hyp = side ? side_stream(1) : nullptr;
+  side_drain.st = side;
+  side_hyp_drain.st = side_hyp;
+  return CS_OK;
+}
+
+// Deals the problems that are live at iteration it0 to the 8 XCDs, longest first onto the least loaded XCD (host only).
+// h_xcd[par] becomes the table [xcd][slot] -> problem (-1 = empty); returns the slots per XCD.
+int RansacCall::place(int it0, int par, int* live) {
+  std::vector<int> order;
+  for (int p = 0; p < n_prob; ++p)
+    if (!hp[p].done && hp[p].est_k > it0) order.push_back(p);
+  *live = (int)order.size();
+  std::sort(order.begin(), order.end(), [&](int a, int c) { return hp[a].m > hp[c].m; });
+  std::vector<std::vector<int>> lists(8);
+  int64_t load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int p : order) {
+    int best = 0;
+    for (int x = 1; x < 8; ++x)
+      if (load[x] < load[best]) best = x;
+    lists[best].push_back(p);
+    load[best] += pf_padded(hp[p].m);
+  }
+  int pslots = 1;
+  for (int x = 0; x < 8; ++x) pslots = std::max(pslots, (int)lists[x].size());
+  std::vector<int32_t>& tab = h_xcd[par];
+  tab.assign((size_t)8 * pslots, -1);
+  for (int x = 0; x < 8; ++x)
+    for (size_t i = 0; i < lists[x].size(); ++i) tab[(size_t)x * pslots + i] = lists[x][i];
+  return pslots;
+}
+
+// Front half of the round that starts at it0: hypotheses (with their prefilter rows) and, from the second chunk on, the
+// prefilter.  Independent of the carried best, so it may be enqueued on `st` = the side stream before the previous
+// round is known; its skip tests read est_k / done while they may be updated (prob_view), and its placement is built
+// from the state one round earlier: finished problems cost a few empty workgroups.
+Front RansacCall::enqueue_front(int it0, int par, hipStream_t st) {
+  Front f;
+  f.it0 = it0;
+  f.b = chunk_of(it0);
+  f.par = par;
+  f.pf = prefiltered(it0);
+  f.on_side = st != s;
+  const int b = f.b;
+  int live = 0;
+  f.pslots = place(it0, par, &live);
+  const int pslots = f.pslots;
+  // stream of the hypothesis kernel: the third stream for a prefiltered front half on the side stream
+  hipStream_t sh = (f.on_side && f.pf && side_hyp) ? side_hyp : st;
+  // the table travels as a kernel argument; rounds with more than XCD_SLOTS problems per XCD copy it to the device
+  if (pslots <= XCD_SLOTS) {
+    memcpy(f.xtab.v, h_xcd[par].data(), sizeof(int32_t) * 8 * pslots);
+  } else {
+    (void)hipMemcpyAsync(sc.xcd_of(par), h_xcd[par].data(), sizeof(int32_t) * 8 * pslots, hipMemcpyHostToDevice, sh);
+    f.xcd_prob = sc.xcd_of(par);
+  }
+  RansacProb* const d_probs = sc.probs();
+  _Float16* A16_r = f.pf ? sc.A16_of(par) : nullptr;
+  float* c_h_r = f.pf ? sc.c_h_of(par) : nullptr;
+  int32_t* cnt_up_r = f.pf ? sc.cnt_up_of(par) : nullptr;
+  const int ptiles = (b + PF_HYP - 1) / PF_HYP;
+  // 1024 workgroups are resident (4 per CU): split the pair range until there are >= 8 rounds of
+  // workgroups, as long as a workgroup keeps >= 8 stages
+  int psplits = (int)((8 * 1024 + (int64_t)live * ptiles - 1) / std::max<int64_t>((int64_t)live * ptiles, 1));
+  if (psplits < 1) psplits = 1;
+  if (psplits > 16) psplits = 16;
+  while (psplits > 1 && m_max / psplits < 8 * PF_ROWS) --psplits;
+  {
+    ProfScope prof("ransac_hyp", sh);
+    const int htiles = (b + 255) / 256;
+    // the prefilter adds the partial counts of its pair-range splits with atomics: the hypothesis kernel clears them
+    int32_t* fz = psplits > 1 ? cnt_up_r : nullptr;
+    const auto kernel = ransac_n == 10 ? k_ransac_hyp<10> : k_ransac_hyp<0>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(8 * pslots * htiles)), dim3(256), 0, sh, d_probs,
+                       sc.pair32.p, it0, b, BMAX, ransac_n, seed, f.xcd_prob, f.xtab, pslots, htiles, opt.force_jacobi,
+                       sc.hyp_of(par), sc.pf_stat.p, sc.pf_sums.p, thr2, tcap, A16_r, c_h_r, fz);
+  }
+  if (f.pf) {
+    if (sh != st) {   // the prefilter (side stream) follows the hypotheses (third stream)
+      (void)hipEventRecord(hyp_done[par].e, sh);
+      (void)hipStreamWaitEvent(st, hyp_done[par].e, 0);
+    }
+    ProfScope prof("ransac_pre", st);  // work units are added by the back half (state known there)
+    const unsigned nblk = (unsigned)(8 * pslots * ptiles * psplits);
+    unsigned long long* tr = (opt.trace_it0 == it0) ? sc.trace.p : nullptr;
+    const auto kernel = opt.pf_nm == 2 ? k_ransac_prefilter<2, false> : k_ransac_prefilter<1, true>;
+    hipLaunchKernelGGL(kernel, dim3(nblk), dim3(256), 0, st, d_probs, sc.off16.p, sc.B16.p, A16_r, c_h_r, it0, b, BMAX,
+                       psplits, f.xcd_prob, f.xtab, pslots, ptiles, cnt_up_r, tr, (const int32_t*)nullptr);
+    if (tr) trace_n = (size_t)nblk * 16;
+  }
+  if (f.on_side) (void)hipEventRecord(front_done[par].e, st);
+  return f;
+}
+
+// Exact count of EVERY hypothesis of an unfiltered chunk (the first of a call, or all of them without the prefilter).
+int RansacCall::count_chunk(const Front& cur, double eval_pairs) {
+  const int b = cur.b;
+  const int hpw = b <= 64 ? 64 : RC_HYP;      // hypotheses per workgroup
+  const int tiles = (b + hpw - 1) / hpw;
+  const int splits = chunk_splits(tiles);
+  if (splits > 1 || hpw != RC_HYP)  // partial counts (pair-range splits, lane quarters) are combined with integer atomics
+    CS_HIP_CHECK(hipMemset2DAsync(sc.res_cnt.p, sizeof(int32_t) * BMAX, 0, sizeof(int32_t) * b, n_prob, s));
+  ProfScope prof("ransac_eval", s, 30.0 * eval_pairs);
+  const dim3 grid((unsigned)(tiles * splits), (unsigned)n_prob);
+  const auto kernel = hpw == 64 ? k_ransac_count<false, 64> : k_ransac_count<false, RC_HYP>;
+  hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, sc.probs(), sc.pk.p, tot1, sc.hyp_of(cur.par), cur.it0, b, BMAX,
+                     splits, thr2, sc.res_cnt.p, (const int32_t*)nullptr, (const int32_t*)nullptr);
+  return CS_OK;
+}
+
+// Prefiltered round: the hypotheses whose bound reaches the carried best are listed, go through the K = 32 bound (second
+// stage) and are counted exactly.  *err_known: their fixed-point errors are in cand_err (by hypothesis) as well.
+int RansacCall::count_survivors(const Front& cur, bool* err_known) {
+  const int it0 = cur.it0, b = cur.b;
+  RansacProb* const d_probs = sc.probs();
+  const double* hyp_r = sc.hyp_of(cur.par);
+  const int32_t* cnt_up_r = sc.cnt_up_of(cur.par);
+  int32_t* const d_nsurv = sc.nsurv(cur.par);   // cleared by the previous round's last scan kernel (or the upload)
+  // This round's survivor counts are not known on the host: the previous round's pick the kernels (each is exact for
+  // any count).  The first prefiltered round has no previous count, but a chunk of b <= FEW_MAX cannot leave more.
+  const int surv_cap = std::min(max_surv_prev, b);
+  const bool few = max_surv_prev <= FEW_MAX || b <= FEW_MAX;
+  // the second stage runs when the few-survivor kernel will; its rows are written by the survivors kernel itself
+  const bool run_s2 = stage2 && few && surv_cap <= PF_S2_CAP;
+  Stage2Rows s2rows{};
+  if (run_s2) {
+    s2rows.A16 = sc.A16_of(cur.par);
+    s2rows.c_h = sc.c_h_of(cur.par);
+    s2rows.stat = sc.pf_stat.p;
+    s2rows.tcap = tcap;
+    s2rows.A16s = sc.A16s.p;
+    s2rows.c_hs = sc.c_hs.p;
+    s2rows.cnt2 = sc.cnt2.p;
+  }
+  hipLaunchKernelGGL(k_ransac_survivors, dim3((unsigned)((b + 255) / 256), (unsigned)n_prob), dim3(256), 0, s, d_probs,
+                     cnt_up_r, it0, b, BMAX, sc.res_cnt.p, sc.cand_err.p, sc.hlist.p, d_nsurv, s2rows);
+  {
+    ProfScope prof("ransac_eval", s);
+    if (few) {
+      if (run_s2) {
+        // K = 32 bound of the survivors (rows compacted by k_ransac_survivors): one small prefilter launch over all pairs,
+        // with the placement of the round's first stage.  Tiles for the WHOLE capacity: workgroups past a problem's list
+        // leave at once.  k_ransac_count_few then skips the entries whose bound is below the best.
+        const int s2tiles = std::max(1, (std::min(b, PF_S2_CAP) + PF_HYP - 1) / PF_HYP);
+        int s2splits = 8;
+        while (s2splits > 1 && m_max / s2splits < 8 * PF_ROWS) --s2splits;
+        hipLaunchKernelGGL((k_ransac_prefilter<2, false>), dim3((unsigned)(8 * cur.pslots * s2tiles * s2splits)), dim3(256),
+                           0, s, d_probs, sc.off16.p, sc.B32.p, sc.A16s.p, sc.c_hs.p, 0, PF_S2_CAP, PF_S2_CAP, s2splits,
+                           cur.xcd_prob, cur.xtab, cur.pslots, s2tiles, sc.cnt2.p, (unsigned long long*)nullptr, d_nsurv);
+      }
+      // pair slices short enough for a thread to keep its pairs in registers across the survivors (8 per thread)
+      int fslices = 8;
+      while (fslices < 32 && m_max > fslices * 2048) fslices *= 2;
+      // survivor slots per (slice, problem): a workgroup loads its pairs once and walks its share of the survivors, so
+      // FEW slots amortise the load (chair, same box: 2 / 4 / 8 / 16 slots -> 1 431 / 1 454 / 1 424 / 1 370 queries/s)
+      const int fslots = surv_cap <= 256 ? 4 : 8;
+      hipLaunchKernelGGL(k_ransac_count_few, dim3((unsigned)fslices, (unsigned)n_prob, (unsigned)fslots), dim3(256), 0, s,
+                         d_probs, sc.pk.p, tot1, hyp_r, BMAX, thr2, scale, sc.res_cnt.p, sc.cand_err.p, sc.hlist.p, d_nsurv,
+                         BMAX, run_s2 ? sc.cnt2.p : (const int32_t*)nullptr);
+      *err_known = true;
+    } else {
+      // few hypotheses, so the pair range is split finely
+      int lsplits = 16;
+      while (lsplits > 1 && m_max / lsplits < RC_CHUNK) --lsplits;
+      const int ltiles = std::min((b + RC_HYP - 1) / RC_HYP, 4);  // tile slots; the kernel strides over longer lists
+      hipLaunchKernelGGL(k_ransac_count<true>, dim3((unsigned)(ltiles * lsplits), (unsigned)n_prob), dim3(256), 0, s,
+                         d_probs, sc.pk.p, tot1, hyp_r, it0, b, BMAX, lsplits, thr2, sc.res_cnt.p, sc.hlist.p, d_nsurv);
+    }
+  }
+  if (check) {   // both bounds against the exact count of every hypothesis of the chunk
+    const int tiles = (b + RC_HYP - 1) / RC_HYP;
+    const int splits = chunk_splits(tiles);
+    CS_HIP_CHECK(hipMemset2DAsync(sc.exact_dbg.p, sizeof(int32_t) * BMAX, 0, sizeof(int32_t) * b, n_prob, s));
+    hipLaunchKernelGGL(k_ransac_count<false>, dim3((unsigned)(tiles * splits), (unsigned)n_prob), dim3(256), 0, s,
+                       d_probs, sc.pk.p, tot1, hyp_r, it0, b, BMAX, splits, thr2, sc.exact_dbg.p, (const int32_t*)nullptr,
+                       (const int32_t*)nullptr);
+    hipLaunchKernelGGL(k_ransac_check_bound, dim3((unsigned)((b + 255) / 256), (unsigned)n_prob), dim3(256), 0, s,
+                       d_probs, sc.exact_dbg.p, cnt_up_r, it0, b, BMAX, sc.chk_stats.p);
+    if (run_s2)
+      hipLaunchKernelGGL(k_ransac_check_bound2, dim3(PF_S2_CAP / 256, (unsigned)n_prob), dim3(256), 0, s, d_probs,
+                         sc.exact_dbg.p, sc.hlist.p, d_nsurv, BMAX, sc.cnt2.p, sc.chk_stats.p);
+  }
+  return CS_OK;
+}
+
+// Back half of a round, on the caller's stream: exact counts (of the whole chunk, or of the prefilter's survivors), then the
+// replay of the chunk in iteration order -- the sequential RANSAC state (best, est_k, done) advances here.
+int RansacCall::back_half(const Front& cur) {
+  const int it0 = cur.it0, b = cur.b;
+  // algorithmic work of this chunk (hp is the state before it): 30 FLOP per (evaluated hypothesis,
+  // correspondence) (transform 18 + squared distance 8 + compare/accumulate) -- for the
+  // exact count and for the prefilter alike (its matrix pipe executes 32 or 64 per pair: bench.py reports both)
+  double eval_pairs = 0.0;
+  for (int p = 0; p < n_prob; ++p) {
+    if (hp[p].done) continue;
+    const int nh = std::min(hp[p].est_k - it0, b);
+    if (nh > 0) {
+      eval_pairs += (double)nh * (double)hp[p].m;
+      tot_eval += (unsigned long long)nh;
+    }
+  }
+  bool err_known = false;  // the fixed-point errors of all candidates are already in cand_err (by hypothesis)
+  if (!cur.pf) {
+    if (int rc = count_chunk(cur, eval_pairs)) return rc;
+  } else {
+    prof_add_units("ransac_pre", 30.0 * eval_pairs);   // the units of the launch the front half bracketed
+    if (int rc = count_survivors(cur, &err_known)) return rc;
+  }
+  static const hipError_t scan1_lds = hipFuncSetAttribute(
+      reinterpret_cast<const void*>(k_ransac_scan1), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+  CS_REQUIRE(scan1_lds == hipSuccess, CS_ERR_HIP, "cs_ransac_batch: cannot reserve LDS for k_ransac_scan1");
+  RansacProb* const d_probs = sc.probs();
+  const double* hyp_r = sc.hyp_of(cur.par);
+  int32_t* const next_nsurv = sc.nsurv(cur.par ^ 1);
+  int* const next_nactive = sc.nactive(cur.par ^ 1);
+  // scan1 replays the chunk and lists the candidates that tie for the best count.  When k_ransac_count_few has left the
+  // error of every survivor it also picks the best of them; otherwise (unfiltered chunk, long survivor list) the errors
+  // of the candidates are computed by k_ransac_err and k_ransac_scan2 picks.
+  hipLaunchKernelGGL(k_ransac_scan1, dim3((unsigned)n_prob), dim3(256), sizeof(int32_t) * (b + 64), s, d_probs, n_prob,
+                     sc.res_cnt.p, it0, b, BMAX, ransac_n, max_iter, log_1mc, sc.cand.p, sc.nactive(cur.par),
+                     err_known ? sc.cand_err.p : (const unsigned long long*)nullptr, hyp_r, next_nsurv, next_nactive);
+  if (!err_known) {
+    hipLaunchKernelGGL(k_ransac_err, dim3(8, (unsigned)n_prob), dim3(256), 0, s, d_probs, sc.pk.p,
+                       tot1, hyp_r, BMAX, sc.cand.p, thr2, scale, sc.cand_err.p);
+    hipLaunchKernelGGL(k_ransac_scan2, dim3((unsigned)ceil_div(n_prob, 64)), dim3(64), 0, s,
+                       d_probs, n_prob, hyp_r, sc.cand.p, sc.cand_err.p, 0, it0, BMAX, next_nsurv, next_nactive);
+  }
+  CS_LAUNCH_CHECK();
+  return CS_OK;
+}
+
+// The round's state has arrived in h_state: survivor bookkeeping, then hp becomes the state after the round.
+// Returns whether any problem is still active.
+bool RansacCall::read_back(const Front& cur) {
+  if (cur.pf) {   // (hp is still the state before the round: the problems that were live in it)
+    const int32_t* h_surv = sc.h_nsurv(cur.par);
+    max_surv_prev = 0;
+    for (int p = 0; p < n_prob; ++p)
+      if (!hp[p].done) {
+        tot_surv += (unsigned long long)h_surv[p];
+        if (h_surv[p] > max_surv_prev) max_surv_prev = h_surv[p];
+      }
+  }
+  memcpy(hp.data(), sc.h_state, sc.st_probs);
+  return sc.h_nactive(cur.par) != 0;
+}
+
+// Trace dump, statistics, results.
+int RansacCall::finish(float* d_T, int32_t* d_inliers, double* d_rmse, int32_t* d_iters) {
+  if (trace_n) {
+    std::vector<unsigned long long> ht(trace_n);
+    CS_HIP_CHECK(hipMemcpy(ht.data(), sc.trace.p, sizeof(unsigned long long) * trace_n, hipMemcpyDeviceToHost));
+    FILE* f = fopen(opt.trace_file, "wb");
+    if (f) {
+      fwrite(ht.data(), sizeof(unsigned long long), trace_n, f);
+      fclose(f);
+    }
+  }
+  g_pf_stats[3] += tot_surv;
+  g_pf_stats[4] += tot_eval;
+  if (check) {
+    unsigned long long h_stats[4] = {0, 0, 0, 0};
+    CS_HIP_CHECK(hipMemcpyAsync(h_stats, sc.chk_stats.p, sizeof(h_stats), hipMemcpyDeviceToHost, s));
+    CS_HIP_CHECK(hipStreamSynchronize(s));
+    g_pf_stats[0] += h_stats[0];
+    g_pf_stats[1] += h_stats[1];
+    g_pf_stats[2] += h_stats[2];
+    CS_REQUIRE(h_stats[0] == 0, CS_ERR_INTERNAL,
+               "cs_ransac_batch: prefilter bound violated for %llu hypotheses", h_stats[0]);
+  }
+  hipLaunchKernelGGL(k_ransac_finish, dim3((unsigned)ceil_div(n_prob, 64)), dim3(64), 0, s,
+                     sc.probs(), n_prob, scale, d_T, d_inliers, d_rmse, d_iters);
+  CS_LAUNCH_CHECK();
+  CS_HIP_CHECK(hipStreamSynchronize(s));
+  side_drain.clean = true;
+  side_hyp_drain.clean = true;
+  return CS_OK;
+}
+}  // namespace
 
 extern "C" {
 
@@ -1682,555 +2176,53 @@ int cs_ransac_batch(const float* d_src, const float* d_tgt, const int64_t* h_off
   const int64_t total = h_off[n_prob] - h_off[0];
   CS_REQUIRE(h_off[0] == 0 && total >= 0, CS_ERR_INVALID, "cs_ransac_batch: bad offsets");
   CS_REQUIRE(total == 0 || (d_src && d_tgt), CS_ERR_INVALID, "cs_ransac_batch: NULL correspondences");
+  RansacCall c;
+  if (int rc = c.init(h_off, n_prob, max_corr, ransac_n, max_iter, confidence, seed, s)) return rc;
+  if (int rc = c.setup(d_src, d_tgt)) return rc;
+  if (int rc = c.open_streams()) return rc;
 
-  std::vector<RansacProb> hp(n_prob);
-  int m_max = 0;
-  for (int p = 0; p < n_prob; ++p) {
-    int64_t m = h_off[p + 1] - h_off[p];
-    CS_REQUIRE(m >= 0 && m < (1LL << 24), CS_ERR_INVALID,
-               "cs_ransac_batch: bad segment %d (a problem holds fewer than 2^24 correspondences)", p);
-    RansacProb& pr = hp[p];
-    memset(&pr, 0, sizeof(pr));
-    pr.off = h_off[p];
-    pr.m = (int32_t)m;
-    pr.est_k = max_iter;
-    pr.best_itr = -1;
-    // Open3D returns the default (identity) result when there are fewer pairs than ransac_n
-    pr.done = m < ransac_n ? 1 : 0;
-    if (m > m_max) m_max = (int)m;
-  }
-  // Largest chunk of iterations per round.  One workgroup = 128 hypotheses x all pairs of a problem
-  // (~100 us), 1536 workgroups are resident: chunks of 16384 give >= 8 "waves" of workgroups for a
-  // 32-query batch, so the partially filled last wave costs ~10 % instead of ~33 % at 4096.
-  const int bmax = 16384;
-  const int64_t tot1 = total ? total : 1;
-  // f16 prefilter (see k_ransac_prefilter): on from the third chunk, when every live problem normally
-  // carries a best count; CS_RANSAC_PREFILTER=0 disables it, CS_RANSAC_CHECK=1 verifies the bound
-  // against the exact count of EVERY hypothesis (slow; tests).
-  const char* env_pf = getenv("CS_RANSAC_PREFILTER");
-  const char* env_ck = getenv("CS_RANSAC_CHECK");
-  const bool use_pf = !(env_pf && env_pf[0] == '0') && total > 0;
-  // CS_RANSAC_PF_K = 32: the two-MFMA form a_hi . (b_hi + b_lo); 16 (default, round 4): one MFMA, a_hi . b_hi with the
-  // dropped term bounded per pair (k_ransac_pack16_b0).  Same results either way (the exact kernels decide).
-  const int pf_nm = (getenv("CS_RANSAC_PF_K") && atoi(getenv("CS_RANSAC_PF_K")) == 32) ? 2 : 1;
-  // K = 16: largest |t| / smax a hypothesis may have to go through the prefilter (the others are counted exactly)
-  double pf_tcap = getenv("CS_RANSAC_PF_TCAP") ? atof(getenv("CS_RANSAC_PF_TCAP")) : 0.75;
-  if (!(pf_tcap > 0.01 && pf_tcap <= 2.002)) pf_tcap = 2.002;
-  if (pf_nm == 2) pf_tcap = 0.0;
-  // CS_RANSAC_PF_COUNT=alignbit: the sign history of rounds 1-3 instead of the add-based count (K = 16 only)
-  const bool pf_rtn = pf_nm == 1 && !(getenv("CS_RANSAC_PF_COUNT") && getenv("CS_RANSAC_PF_COUNT")[0] == 'a');
-  const bool check = use_pf && env_ck && env_ck[0] == '1';
-  // first chunk (all hypotheses counted exactly: there is no best count to prune against yet) and first
-  // prefiltered iteration.  Round 1 (f32 matrix-pipe exact kernel): 512 = 256, no difference; with the f64
-  // exact kernel of round 2 the unfiltered rounds are the expensive ones: 256 instead of 512 is +2.4 % queries/s
-  // (experiment knobs: clamped -- a first chunk above bmax would index the bmax-sized scratch out of range, 0 would
-  // never advance the chunk loop)
-  // Round 5: 64.  The unfiltered chunk costs its hypotheses x ALL pairs in f64 (0.31 ms per 48-problem call at 256, twice per
-  // chair step); with 64 the second chunk, [64, 512), is already prefiltered -- against the best of 64 hypotheses instead of 256,
-  // which lets a few more of its hypotheses through to the exact kernels.  Results are the sequential loop's either way.
-  int first_chunk = getenv("CS_RANSAC_FIRST") ? atoi(getenv("CS_RANSAC_FIRST")) : 64;
-  first_chunk = ((std::min(std::max(first_chunk, 64), bmax) + 63) / 64) * 64;
-  int pf_from = getenv("CS_RANSAC_PF_FROM") ? atoi(getenv("CS_RANSAC_PF_FROM")) : first_chunk;
-  pf_from = std::max(pf_from, first_chunk);
-  // per-round state in ONE block, so a round ends with one device->host copy (into pinned memory):
-  // [RansacProb x n_prob | 2 x { n_surv int32 x n_prob (padded to 8 B) | n_active int32 (8 B) }]: the counters
-  // exist once per round parity, k_ransac_scan2 clears the set of the next round
-  const size_t st_probs = sizeof(RansacProb) * (size_t)n_prob;
-  const size_t st_surv = ((sizeof(int32_t) * (size_t)n_prob + 7) / 8) * 8;
-  const size_t st_cnt = st_surv + 8;
-  const size_t st_bytes = st_probs + 2 * st_cnt;
-  PoolBuf<char> state(st_bytes);
-  RansacProb* const d_probs = reinterpret_cast<RansacProb*>(state.p);
-  auto nsurv_of = [&](int par) { return reinterpret_cast<int32_t*>(state.p + st_probs + par * st_cnt); };
-  auto nactive_of = [&](int par) { return reinterpret_cast<int*>(state.p + st_probs + par * st_cnt + st_surv); };
-  char* const h_state = pinned_scratch(st_bytes);
-  CS_REQUIRE(state.p && h_state, CS_ERR_HIP, "cs_ransac_batch: scratch allocation failed");
-  PoolBuf<float> pk((size_t)tot1 * 6);
-  PoolBuf<float4> pair32((size_t)tot1 * 2);
-  PoolBuf<double> hyp((size_t)2 * n_prob * 12 * bmax);  // hypotheses (f64 R|t), one set per round parity
-  PoolBuf<int32_t> res_cnt((size_t)n_prob * bmax), cand((size_t)n_prob * bmax);
-  PoolBuf<unsigned long long> cand_err((size_t)n_prob * bmax);
-  CS_REQUIRE(pk.p && pair32.p && hyp.p && res_cnt.p && cand.p && cand_err.p,
-             CS_ERR_HIP, "cs_ransac_batch: scratch allocation failed");
-  const bool pf_alloc = use_pf && max_iter > pf_from;
-  // f16 pair image: every problem padded to whole LDS stages
-  std::vector<int64_t> h_off16(n_prob + 1, 0);
-  for (int p = 0; p < n_prob; ++p) h_off16[p + 1] = h_off16[p] + pf_padded(hp[p].m);
-  const int64_t rows16 = h_off16[n_prob] ? h_off16[n_prob] : 1;
-  PoolBuf<_Float16> B16(pf_alloc ? (size_t)rows16 * pf_pitch(pf_nm) : 8), A16(pf_alloc ? (size_t)2 * n_prob * bmax * PF_K : 8);
-  PoolBuf<int64_t> off16(n_prob + 1);
-  PoolBuf<float> c_h(pf_alloc ? (size_t)2 * n_prob * bmax : 1);
-  PoolBuf<int32_t> cnt_up(pf_alloc ? (size_t)2 * n_prob * bmax : 1), hlist(pf_alloc ? (size_t)n_prob * bmax : 1);
-  PoolBuf<unsigned> pf_stat((size_t)n_prob * PF_STAT);
-  PoolBuf<double> pf_sums((size_t)n_prob * 6);
-  // second stage (K = 32 on the compacted survivors of the K = 16 stage; CS_RANSAC_STAGE2=0 switches it off)
-  const bool stage2 = pf_alloc && pf_nm == 1 && !(getenv("CS_RANSAC_STAGE2") && getenv("CS_RANSAC_STAGE2")[0] == '0');
-  PoolBuf<_Float16> B32(stage2 ? (size_t)rows16 * PF_PITCH : 8), A16s(stage2 ? (size_t)n_prob * PF_S2_CAP * PF_K : 8);
-  PoolBuf<float> c_hs(stage2 ? (size_t)n_prob * PF_S2_CAP : 1);
-  PoolBuf<int32_t> cnt2(stage2 ? (size_t)n_prob * PF_S2_CAP : 1), hlist2(stage2 ? (size_t)n_prob * bmax : 1),
-      n_surv2((size_t)n_prob);
-  PoolBuf<unsigned> pf_stat2((size_t)n_prob * PF_STAT);   // (the K = 32 pack writes the same statistics again: scratch)
-  PoolBuf<unsigned long long> s2_total(1);
-  CS_REQUIRE(B32.p && A16s.p && c_hs.p && cnt2.p && hlist2.p && n_surv2.p && pf_stat2.p && s2_total.p, CS_ERR_HIP,
-             "cs_ransac_batch: scratch allocation failed");
-  PoolBuf<int32_t> exact_dbg(check ? (size_t)n_prob * bmax : 1);
-  PoolBuf<unsigned long long> chk_stats(4);
-  CS_REQUIRE(off16.p && B16.p && A16.p && c_h.p && cnt_up.p && hlist.p && pf_stat.p && pf_sums.p &&
-                 exact_dbg.p && chk_stats.p,
-             CS_ERR_HIP, "cs_ransac_batch: scratch allocation failed");
-  std::vector<int32_t> h_surv(n_prob), h_xcd[2];
-  // placement tables, one per round parity (8 x n_prob entries each)
-  PoolBuf<int32_t> xcd_buf((size_t)16 * n_prob);
-  CS_REQUIRE(xcd_buf.p, CS_ERR_HIP, "cs_ransac_batch: scratch allocation failed");
-  {
-    // problems + zeroed counters in one upload (h_state is page-locked and not read before the first round ends)
-    memset(h_state, 0, st_bytes);
-    memcpy(h_state, hp.data(), st_probs);
-    CS_HIP_CHECK(hipMemcpyAsync(state.p, h_state, st_bytes, hipMemcpyHostToDevice, s));
-  }
-  if (total > 0) {
-    hipLaunchKernelGGL(k_ransac_pack, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, s,
-                       d_src, d_tgt, total, pk.p, pair32.p);
-    CS_LAUNCH_CHECK();
-  }
-  if (pf_alloc) {
-    CS_HIP_CHECK(hipMemsetAsync(pf_stat.p, 0, sizeof(unsigned) * n_prob * PF_STAT, s));
-    CS_HIP_CHECK(hipMemsetAsync(chk_stats.p, 0, sizeof(unsigned long long) * 4, s));
-    int pblocks = (int)ceil_div(m_max > 0 ? m_max : 1, 256);
-    if (pblocks > 64) pblocks = 64;
-    CS_HIP_CHECK(hipMemcpyAsync(off16.p, h_off16.data(), sizeof(int64_t) * (n_prob + 1),
-                                hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_ransac_pair_sums, dim3((unsigned)n_prob), dim3(256), 0, s, d_probs, d_src, d_tgt, pf_sums.p);
-    if (pf_nm == 2) {
-      hipLaunchKernelGGL(k_ransac_pack16<2>, dim3((unsigned)pblocks, (unsigned)n_prob), dim3(256), 0, s,
-                         d_probs, off16.p, d_src, d_tgt, pf_sums.p, B16.p, pf_stat.p);
-    } else {
-      hipLaunchKernelGGL(k_ransac_pack16<1>, dim3((unsigned)pblocks, (unsigned)n_prob), dim3(256), 0, s,
-                         d_probs, off16.p, d_src, d_tgt, pf_sums.p, B16.p, pf_stat.p);
-      hipLaunchKernelGGL(k_ransac_pack16_b0, dim3((unsigned)pblocks, (unsigned)n_prob), dim3(256), 0, s,
-                         d_probs, off16.p, d_src, d_tgt, pf_sums.p, pf_stat.p, pf_tcap, B16.p);
-    }
-    if (stage2) {
-      CS_HIP_CHECK(hipMemsetAsync(pf_stat2.p, 0, sizeof(unsigned) * n_prob * PF_STAT, s));
-      CS_HIP_CHECK(hipMemsetAsync(s2_total.p, 0, sizeof(unsigned long long), s));
-      hipLaunchKernelGGL(k_ransac_pack16<2>, dim3((unsigned)pblocks, (unsigned)n_prob), dim3(256), 0, s,
-                         d_probs, off16.p, d_src, d_tgt, pf_sums.p, B32.p, pf_stat2.p);
-    }
-    CS_LAUNCH_CHECK();
-  }
-  // squared threshold (Open3D: max_correspondence_distance * max_correspondence_distance in double) and
-  // the power-of-two fixed-point scale of the inlier error: terms d^2 * scale < 2^38, so the u64 sum over
-  // a problem's (< 2^24) pairs cannot overflow and is exact in any order
-  const double thr2 = max_corr * max_corr;
-  int ex = 0;
-  (void)frexp(thr2, &ex);
-  const double scale = ldexp(1.0, 38 - ex);
-  const double log_1mc = log(1.0 - confidence);  // -inf when confidence == 1: never exits early
-  unsigned long long tot_surv = 0, tot_eval = 0;
-  const int trace_it0 = getenv("CS_PF_TRACE") ? atoi(getenv("CS_PF_TRACE")) : -1;
-  PoolBuf<unsigned long long> trace(trace_it0 >= 0 ? (size_t)8 * n_prob * 64 * 16 * 16 : 1);
-  size_t trace_n = 0;
-  if (trace_it0 >= 0) CS_HIP_CHECK(hipMemsetAsync(trace.p, 0, sizeof(unsigned long long) * (size_t)8 * n_prob * 64 * 16 * 16, s));
-
-  struct Event {
-    hipEvent_t e = nullptr;
-    ~Event() {
-      if (e) (void)hipEventDestroy(e);
-    }
-  } round_done, front_done[2], hyp_done[2];
-  CS_HIP_CHECK(hipEventCreateWithFlags(&round_done.e, hipEventDisableTiming));
-  CS_HIP_CHECK(hipEventCreateWithFlags(&front_done[0].e, hipEventDisableTiming));
-  CS_HIP_CHECK(hipEventCreateWithFlags(&front_done[1].e, hipEventDisableTiming));
-  CS_HIP_CHECK(hipEventCreateWithFlags(&hyp_done[0].e, hipEventDisableTiming));
-  CS_HIP_CHECK(hipEventCreateWithFlags(&hyp_done[1].e, hipEventDisableTiming));
-  // A round = front half (hypotheses, f16 rows, prefilter: independent of the carried best) + back
-  // half (survivors, exact counts, scans: the sequential RANSAC state).  The front half of round i+1
-  // is enqueued on a second, low-priority stream before the host waits for round i, so it fills the
-  // GPU while the back half of round i (many small dependent kernels) and the host turnaround run.
-  // Its skip tests read est_k / done while they may be updated (prob_view); its placement table is
-  // built from the state one round earlier: finished problems cost a few empty workgroups.
-  // CS_RANSAC_JACOBI=1: every hypothesis through the Jacobi eigen-solver (the fallback of horn_qcp; the oracle's
-  // oc_rigid_fit_force_jacobi is its counterpart) -- tests and A/B timing
-  const int force_jacobi = getenv("CS_RANSAC_JACOBI") && atoi(getenv("CS_RANSAC_JACOBI")) != 0;
-  const char* env_ov = getenv("CS_RANSAC_OVERLAP");
-  hipStream_t side = (env_ov && env_ov[0] == '0') ? nullptr : side_stream();
-  // ... and the hypotheses of a side-stream front half go to a THIRD stream: those of round i+2 are enqueued when round i
-  // is known (their buffers, one set per parity, are free then) and run UNDER the prefilter of round i+1 instead of
-  // behind it on the same stream (f64 vector work beside f16 matrix work).  CS_RANSAC_HYP_STREAM=0: one side stream.
-  const char* env_hs = getenv("CS_RANSAC_HYP_STREAM");
-  hipStream_t side_hyp = (side && !(env_hs && env_hs[0] == '0')) ? side_stream(1) : nullptr;
-  // an error return must not hand the scratch buffers back to the pool while the side stream still uses
-  // them; on the normal path the final wait on the main stream is already ordered behind its events
-  struct SideDrain {
-    hipStream_t st;
-    bool clean = false;
-    ~SideDrain() {
-      if (st && !clean) (void)hipStreamSynchronize(st);
-    }
-  } side_drain{side}, side_hyp_drain{side_hyp};
-  struct Front {
-    int it0 = 0, b = 0, par = 0;
-    bool pf = false, on_side = false;
-    // placement of the round's prefilter launch (the second stage of the back half uses the same)
-    XcdTab xtab;
-    const int32_t* xcd_prob = nullptr;
-    int pslots = 1;
-  };
-  // chunks: [0, first) counted exactly, [first, 512) in one piece, then doubling ([512, 1024), [1024, 2048), ...) up to bmax
-  auto chunk_of = [&](int it0) {
-    int b = it0 < first_chunk ? first_chunk : it0 < 512 ? 512 - it0 : (it0 < bmax ? it0 : bmax);
-    return b > max_iter - it0 ? max_iter - it0 : b;
-  };
-  auto enqueue_front = [&](int it0, int par, hipStream_t st) -> Front {
-    Front f;
-    f.it0 = it0;
-    f.b = chunk_of(it0);
-    f.par = par;
-    f.pf = pf_alloc && it0 >= pf_from;
-    f.on_side = st != s;
-    const int b = f.b;
-    // deal the live problems to the 8 XCDs, longest first onto the least loaded XCD
-    std::vector<int> order;
-    for (int p = 0; p < n_prob; ++p)
-      if (!hp[p].done && hp[p].est_k > it0) order.push_back(p);
-    const int live = (int)order.size();
-    std::sort(order.begin(), order.end(), [&](int a, int c) { return hp[a].m > hp[c].m; });
-    std::vector<std::vector<int>> lists(8);
-    int64_t load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int p : order) {
-      int best = 0;
-      for (int x = 1; x < 8; ++x)
-        if (load[x] < load[best]) best = x;
-      lists[best].push_back(p);
-      load[best] += pf_padded(hp[p].m);
-    }
-    int pslots = 1;
-    for (int x = 0; x < 8; ++x) pslots = std::max(pslots, (int)lists[x].size());
-    std::vector<int32_t>& tab = h_xcd[par];
-    tab.assign((size_t)8 * pslots, -1);
-    for (int x = 0; x < 8; ++x)
-      for (size_t i = 0; i < lists[x].size(); ++i) tab[(size_t)x * pslots + i] = lists[x][i];
-    int32_t* xcd_prob = nullptr;
-    XcdTab xtab;
-    // stream of the hypothesis kernels: the third stream for a prefiltered front half on the side stream
-    hipStream_t sh = (f.on_side && f.pf && side_hyp) ? side_hyp : st;
-    if (pslots <= XCD_SLOTS) {
-      memcpy(xtab.v, tab.data(), sizeof(int32_t) * 8 * pslots);
-    } else {
-      xcd_prob = xcd_buf.p + (size_t)par * 8 * n_prob;
-      (void)hipMemcpyAsync(xcd_prob, tab.data(), sizeof(int32_t) * 8 * pslots, hipMemcpyHostToDevice, sh);
-    }
-    double* hyp_r = hyp.p + (size_t)par * n_prob * 12 * bmax;
-    _Float16* A16_r = f.pf ? A16.p + (size_t)par * n_prob * bmax * PF_K : nullptr;
-    float* c_h_r = f.pf ? c_h.p + (size_t)par * n_prob * bmax : nullptr;
-    int32_t* cnt_up_r = f.pf ? cnt_up.p + (size_t)par * n_prob * bmax : nullptr;
-    const int ptiles = (b + PF_HYP - 1) / PF_HYP;
-    // 1024 workgroups are resident (4 per CU): split the pair range until there are >= 8 rounds of
-    // workgroups, as long as a workgroup keeps >= 8 stages
-    int psplits = (int)((8 * 1024 + (int64_t)live * ptiles - 1) / std::max<int64_t>((int64_t)live * ptiles, 1));
-    if (psplits < 1) psplits = 1;
-    if (psplits > 16) psplits = 16;
-    while (psplits > 1 && m_max / psplits < 8 * PF_ROWS) --psplits;
-    // the prefilter rows of the hypotheses come out of the hypothesis kernel itself (CS_RANSAC_FUSE_HYP16=0: a second
-    // kernel reads the table back, the arrangement of rounds 1 - 3)
-    static const bool fuse16 = !(getenv("CS_RANSAC_FUSE_HYP16") && getenv("CS_RANSAC_FUSE_HYP16")[0] == '0');
-    const bool fused = f.pf && fuse16;
-    {
-      ProfScope prof("ransac_hyp", sh);
-      const int htiles = (b + 255) / 256;
-      _Float16* fa = fused ? A16_r : nullptr;
-      int32_t* fz = fused && psplits > 1 ? cnt_up_r : nullptr;
-      if (ransac_n == 10)
-        hipLaunchKernelGGL(k_ransac_hyp<10>, dim3((unsigned)(8 * pslots * htiles)), dim3(256), 0, sh, d_probs,
-                           pair32.p, it0, b, bmax, ransac_n, seed, xcd_prob, xtab, pslots, htiles, force_jacobi, hyp_r,
-                           pf_stat.p, pf_sums.p, thr2, pf_tcap, fa, c_h_r, fz);
-      else
-        hipLaunchKernelGGL(k_ransac_hyp<0>, dim3((unsigned)(8 * pslots * htiles)), dim3(256), 0, sh, d_probs,
-                           pair32.p, it0, b, bmax, ransac_n, seed, xcd_prob, xtab, pslots, htiles, force_jacobi, hyp_r,
-                           pf_stat.p, pf_sums.p, thr2, pf_tcap, fa, c_h_r, fz);
-    }
-    if (f.pf) {
-      if (!fused)
-        hipLaunchKernelGGL(k_ransac_hyp16, dim3((unsigned)((b + 255) / 256), (unsigned)n_prob), dim3(256),
-                           0, sh, d_probs, hyp_r, pf_stat.p, pf_sums.p, it0, b, bmax, thr2, A16_r, c_h_r,
-                           psplits > 1 ? cnt_up_r : (int32_t*)nullptr, pf_tcap);
-      if (sh != st) {   // the prefilter (side stream) follows the hypotheses (third stream)
-        (void)hipEventRecord(hyp_done[par].e, sh);
-        (void)hipStreamWaitEvent(st, hyp_done[par].e, 0);
-      }
-      {
-        ProfScope prof("ransac_pre", st);  // work units are added by the back half (state known there)
-        const unsigned nblk = (unsigned)(8 * pslots * ptiles * psplits);
-        if (pf_nm == 2)
-          hipLaunchKernelGGL((k_ransac_prefilter<2, false>), dim3(nblk), dim3(256), 0, st, d_probs, off16.p, B16.p,
-                             A16_r, c_h_r, it0, b, bmax, psplits, xcd_prob, xtab, pslots, ptiles, cnt_up_r,
-                             (trace_it0 == it0) ? trace.p : nullptr, (const int32_t*)nullptr);
-        else if (pf_rtn)
-          hipLaunchKernelGGL((k_ransac_prefilter<1, true>), dim3(nblk), dim3(256), 0, st, d_probs, off16.p, B16.p,
-                             A16_r, c_h_r, it0, b, bmax, psplits, xcd_prob, xtab, pslots, ptiles, cnt_up_r,
-                             (trace_it0 == it0) ? trace.p : nullptr, (const int32_t*)nullptr);
-        else
-          hipLaunchKernelGGL((k_ransac_prefilter<1, false>), dim3(nblk), dim3(256), 0, st, d_probs, off16.p, B16.p,
-                             A16_r, c_h_r, it0, b, bmax, psplits, xcd_prob, xtab, pslots, ptiles, cnt_up_r,
-                             (trace_it0 == it0) ? trace.p : nullptr, (const int32_t*)nullptr);
-        if (trace_it0 == it0) trace_n = (size_t)nblk * 16;
-      }
-    }
-    f.xtab = xtab;
-    f.xcd_prob = xcd_prob;
-    f.pslots = pslots;
-    if (f.on_side) (void)hipEventRecord(front_done[par].e, st);
-    return f;
-  };
-
-  int max_surv_prev = 1 << 30;  // survivors per problem in the previous prefiltered round (unknown: many)
-  Front cur = enqueue_front(0, 0, s);
+  // A round = front half (hypotheses, f16 rows, prefilter: independent of the carried best) + back half (survivors,
+  // exact counts, scans: the sequential RANSAC state), then ONE host wait for the round's state in pinned memory.
+  // Streams: the back half always runs on the caller's stream s.  The front half of round i+1 is enqueued BEFORE the host
+  // waits for round i: behind it on s while the rounds are short, on the low-priority c.side once rounds i and i+1 are both
+  // prefiltered (its hypothesis kernel on c.side_hyp) -- so it fills the GPU while the back half of round i (many small
+  // dependent kernels) and the host turnaround run.  s waits for a side-stream front half through front_done[parity].
+  Front cur = c.enqueue_front(0, 0, s);
   CS_LAUNCH_CHECK();
   bool side_pending = false;  // the side stream holds work the main stream has not waited for
   int side_par = 0;
   while (true) {
-    const int it0 = cur.it0, b = cur.b;
-    const bool pf = cur.pf;
-    const double* hyp_r = hyp.p + (size_t)cur.par * n_prob * 12 * bmax;
-    const int32_t* cnt_up_r = cnt_up.p + (size_t)cur.par * n_prob * bmax;
     if (cur.on_side) {
-      CS_HIP_CHECK(hipStreamWaitEvent(s, front_done[cur.par].e, 0));
+      CS_HIP_CHECK(hipStreamWaitEvent(s, c.front_done[cur.par].e, 0));
       side_pending = false;
     }
-    bool err_known = false;  // the fixed-point errors of all candidates are already in cand_err (by hypothesis)
-    const int hpw = (!pf && b <= 64) ? 64 : RC_HYP;      // hypotheses per workgroup of the unfiltered exact count
-    const int tiles = (b + hpw - 1) / hpw;
-    // enough workgroups for 256 CUs x several waves; the correspondence range is split when the
-    // chunk is small (integer partial sums combine exactly)
-    int splits = (int)(4096 / ((int64_t)n_prob * tiles > 0 ? (int64_t)n_prob * tiles : 1));
-    if (splits < 1) splits = 1;
-    if (splits > 16) splits = 16;
-    while (splits > 1 && m_max / splits < 4 * RC_CHUNK) --splits;
-    int32_t* const d_nsurv = nsurv_of(cur.par);   // cleared by the previous round's k_ransac_scan2 (or the upload)
-    int* const d_nactive = nactive_of(cur.par);
-    // algorithmic work of this chunk (hp is the state before it): 30 FLOP per (evaluated hypothesis,
-    // correspondence) (transform 18 + squared distance 8 + compare/accumulate) -- for the
-    // exact count and for the prefilter alike (its matrix pipe executes 64 per pair: the 32
-    // multiply-adds of the a_hi (b_hi + b_lo) expansion)
-    double eval_pairs = 0.0;
-    for (int p = 0; p < n_prob; ++p) {
-      if (hp[p].done) continue;
-      int nh = hp[p].est_k - it0;
-      if (nh > b) nh = b;
-      if (nh > 0) {
-        eval_pairs += (double)nh * (double)hp[p].m;
-        tot_eval += (unsigned long long)nh;
-      }
-    }
-    if (!pf) {
-      if (splits > 1 || hpw != RC_HYP)  // partial counts (pair-range splits, lane quarters) are combined with integer atomics
-        CS_HIP_CHECK(hipMemset2DAsync(res_cnt.p, sizeof(int32_t) * bmax, 0, sizeof(int32_t) * b,
-                                      n_prob, s));
-      ProfScope prof("ransac_eval", s, 30.0 * eval_pairs);
-      if (hpw == 64)
-        hipLaunchKernelGGL((k_ransac_count<false, 64>), dim3((unsigned)(tiles * splits), (unsigned)n_prob),
-                           dim3(256), 0, s, d_probs, pk.p, tot1, hyp_r, it0, b, bmax, splits, thr2,
-                           res_cnt.p, (const int32_t*)nullptr, (const int32_t*)nullptr);
-      else
-        hipLaunchKernelGGL(k_ransac_count<false>, dim3((unsigned)(tiles * splits), (unsigned)n_prob),
-                           dim3(256), 0, s, d_probs, pk.p, tot1, hyp_r, it0, b, bmax, splits, thr2,
-                           res_cnt.p, (const int32_t*)nullptr, (const int32_t*)nullptr);
-    } else {
-      // SURVEY 8d unit: 30 FLOP per (hypothesis, pair) -- the work of the exact formulation the prefilter
-      // stands in for (the matrix pipe executes 64 FLOP per pair: bench.py reports both)
-      prof_add_units("ransac_pre", 30.0 * eval_pairs);
-      // the second stage runs when the few-survivor kernel will (decided from the previous round's counts, like the kernel
-      // choice below); its rows are written by the survivors kernel itself
-      static const int few_max = getenv("CS_RANSAC_FEW_MAX") ? std::max(atoi(getenv("CS_RANSAC_FEW_MAX")), 1) : 1024;
-      const int surv_cap = std::min(max_surv_prev, b);
-      const bool few = max_surv_prev <= few_max || b <= few_max;
-      const bool run_s2 = stage2 && few && surv_cap <= PF_S2_CAP;
-      Stage2Rows s2rows{};
-      if (run_s2) {
-        s2rows.A16 = A16.p + (size_t)cur.par * n_prob * bmax * PF_K;
-        s2rows.c_h = c_h.p + (size_t)cur.par * n_prob * bmax;
-        s2rows.stat = pf_stat.p;
-        s2rows.tcap = pf_tcap;
-        s2rows.A16s = A16s.p;
-        s2rows.c_hs = c_hs.p;
-        s2rows.cnt2 = cnt2.p;
-        s2rows.n_surv2 = n_surv2.p;
-      }
-      hipLaunchKernelGGL(k_ransac_survivors, dim3((unsigned)((b + 255) / 256), (unsigned)n_prob),
-                         dim3(256), 0, s, d_probs, cnt_up_r, it0, b, bmax, res_cnt.p, cand_err.p, hlist.p,
-                         d_nsurv, s2rows);
-      // exact counts of the survivors; few hypotheses, so the pair range is split finely
-      int lsplits = 16;
-      while (lsplits > 1 && m_max / lsplits < RC_CHUNK) --lsplits;
-      {
-        ProfScope prof("ransac_eval", s);
-        // the previous round's survivor counts pick the kernel (both are exact for any count)
-        // (round 3, K = 32 prefilter: 32 / 64 / 128 / 256 measured, 128 the fastest by ~1 %.  The K = 16 form of round 4
-        // leaves 3 - 4x the survivors, ~16 per problem and round on the chair shape: the list kernel -- one workgroup of
-        // 256 hypothesis lanes per problem -- then ran in every fourth round at 670 us)
-        // (the first prefiltered round has no previous count, but a chunk of b <= few_max hypotheses cannot leave more)
-        if (few) {
-          // pair slices short enough for a thread to keep its pairs in registers across the survivors (8 per thread)
-          int fslices = 8;
-          while (fslices < 32 && m_max > fslices * 2048) fslices *= 2;
-          // survivor slots per (slice, problem): a workgroup loads its pairs once and walks its share of the survivors, so
-          // FEW slots amortise the load (chair, same box: 2 / 4 / 8 / 16 slots -> 1 431 / 1 454 / 1 424 / 1 370 queries/s)
-          int fslots = surv_cap <= 256 ? 4 : 8;
-          if (getenv("CS_RANSAC_FEW_SLOTS")) fslots = std::max(1, atoi(getenv("CS_RANSAC_FEW_SLOTS")));
-          if (getenv("CS_RANSAC_FEW_SLICES")) fslices = std::max(1, atoi(getenv("CS_RANSAC_FEW_SLICES")));
-          const int32_t* list_p = hlist.p;
-          const int32_t* list_n = d_nsurv;
-          const int32_t* list_cnt2 = nullptr;
-          int list_stride = bmax;
-          const int s2_pslots = cur.pslots;
-          const int32_t* s2_xcd_prob = cur.xcd_prob;
-          const XcdTab& s2_xtab = cur.xtab;
-          // CS_RANSAC_KNOCKOUT (TIMING EXPERIMENT ONLY, results are wrong): bit 0 skips the exact count of the survivors, bit 1
-          // the second-stage launch -- what a perfect bound in front of them could save at most (profiles/r5f_*)
-          static const int knockout = getenv("CS_RANSAC_KNOCKOUT") ? atoi(getenv("CS_RANSAC_KNOCKOUT")) : 0;
-          if (run_s2 && !(knockout & 2)) {
-            // K = 32 bound of the survivors (rows compacted by k_ransac_survivors): one small prefilter launch over all
-            // pairs, then the list filtered again
-            // tiles for the WHOLE capacity: this round's survivor counts are not known on the host (surv_cap comes from the
-            // previous round and only picks kernels that are exact for any count); workgroups past a problem's list leave at once
-            const int s2tiles = std::max(1, (std::min(b, PF_S2_CAP) + PF_HYP - 1) / PF_HYP);
-            int s2splits = 8;
-            while (s2splits > 1 && m_max / s2splits < 8 * PF_ROWS) --s2splits;
-            hipLaunchKernelGGL((k_ransac_prefilter<2, false>), dim3((unsigned)(8 * s2_pslots * s2tiles * s2splits)), dim3(256), 0,
-                               s, d_probs, off16.p, B32.p, A16s.p, c_hs.p, 0, PF_S2_CAP, PF_S2_CAP, s2splits, s2_xcd_prob,
-                               s2_xtab, s2_pslots, s2tiles, cnt2.p, (unsigned long long*)nullptr, d_nsurv);
-            // the list filter of the second stage runs inside k_ransac_count_few (it skips the entries whose K = 32 bound is
-            // below the best); the separate compaction kernel only for the statistics / CS_RANSAC_FUSE_S2LIST=0
-            static const bool fuse_s2 = !(getenv("CS_RANSAC_FUSE_S2LIST") && getenv("CS_RANSAC_FUSE_S2LIST")[0] == '0') &&
-                                        !getenv("CS_RANSAC_STAGE2_STATS");
-            if (fuse_s2) {
-              list_cnt2 = cnt2.p;
-            } else {
-              hipLaunchKernelGGL(k_ransac_stage2_survivors, dim3((unsigned)((b + 255) / 256), (unsigned)n_prob), dim3(256), 0, s,
-                                 d_probs, hlist.p, d_nsurv, bmax, cnt2.p, hlist2.p, n_surv2.p, s2_total.p);
-              list_p = hlist2.p;
-              list_n = n_surv2.p;
-            }
-          }
-          if (!(knockout & 1))
-            hipLaunchKernelGGL(k_ransac_count_few, dim3((unsigned)fslices, (unsigned)n_prob, (unsigned)fslots), dim3(256), 0, s,
-                               d_probs, pk.p, tot1, hyp_r, bmax, thr2, scale, res_cnt.p, cand_err.p, list_p, list_n, list_stride,
-                               (knockout & 2) ? (const int32_t*)nullptr : list_cnt2);
-          err_known = true;
-        } else {
-          const int ltiles = tiles < 4 ? tiles : 4;  // tile slots; the kernel strides over longer lists
-          hipLaunchKernelGGL(k_ransac_count<true>, dim3((unsigned)(ltiles * lsplits), (unsigned)n_prob),
-                             dim3(256), 0, s, d_probs, pk.p, tot1, hyp_r, it0, b, bmax, lsplits, thr2,
-                             res_cnt.p, hlist.p, d_nsurv);
-        }
-      }
-      if (check) {
-        CS_HIP_CHECK(hipMemset2DAsync(exact_dbg.p, sizeof(int32_t) * bmax, 0, sizeof(int32_t) * b,
-                                      n_prob, s));
-        hipLaunchKernelGGL(k_ransac_count<false>, dim3((unsigned)(tiles * splits), (unsigned)n_prob),
-                           dim3(256), 0, s, d_probs, pk.p, tot1, hyp_r, it0, b, bmax, splits, thr2,
-                           exact_dbg.p, (const int32_t*)nullptr, (const int32_t*)nullptr);
-        hipLaunchKernelGGL(k_ransac_check_bound, dim3((unsigned)((b + 255) / 256), (unsigned)n_prob),
-                           dim3(256), 0, s, d_probs, exact_dbg.p, cnt_up_r, it0, b, bmax, chk_stats.p);
-        if (run_s2)
-          hipLaunchKernelGGL(k_ransac_check_bound2, dim3(PF_S2_CAP / 256, (unsigned)n_prob), dim3(256), 0, s, d_probs,
-                             exact_dbg.p, hlist.p, d_nsurv, bmax, cnt2.p, chk_stats.p);
-      }
-    }
-    static const hipError_t scan1_lds = hipFuncSetAttribute(
-        reinterpret_cast<const void*>(k_ransac_scan1), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    CS_REQUIRE(scan1_lds == hipSuccess, CS_ERR_HIP, "cs_ransac_batch: cannot reserve LDS for k_ransac_scan1");
-    // the best-candidate update (k_ransac_scan2) runs inside scan1 when the errors of all survivors are already known
-    // (CS_RANSAC_FUSE_SCAN=0: three kernels as before)
-    static const bool fuse_scan = !(getenv("CS_RANSAC_FUSE_SCAN") && getenv("CS_RANSAC_FUSE_SCAN")[0] == '0');
-    const bool fused_scan = err_known && fuse_scan;
-    hipLaunchKernelGGL(k_ransac_scan1, dim3((unsigned)n_prob), dim3(256), sizeof(int32_t) * (b + 64), s, d_probs, n_prob,
-                       res_cnt.p, it0, b, bmax, ransac_n, max_iter, log_1mc, cand.p, d_nactive,
-                       fused_scan ? cand_err.p : (const unsigned long long*)nullptr, hyp_r, nsurv_of(cur.par ^ 1),
-                       nactive_of(cur.par ^ 1));
-    if (!err_known)
-      hipLaunchKernelGGL(k_ransac_err, dim3(8, (unsigned)n_prob), dim3(256), 0, s, d_probs, pk.p,
-                         tot1, hyp_r, bmax, cand.p, thr2, scale, cand_err.p);
-    if (!fused_scan)
-      hipLaunchKernelGGL(k_ransac_scan2, dim3((unsigned)ceil_div(n_prob, 64)), dim3(64), 0, s,
-                         d_probs, n_prob, hyp_r, cand.p, cand_err.p, err_known ? 1 : 0, it0, bmax, nsurv_of(cur.par ^ 1),
-                         nactive_of(cur.par ^ 1));
-    CS_LAUNCH_CHECK();
+    if (int rc = c.back_half(cur)) return rc;
     // the per-problem state (est_k, done), the survivor counts and the activity counter come back in
     // one copy behind a synchronisation the chunk loop needs anyway
-    std::vector<RansacProb> prev;
-    if (pf) prev = hp;
-    CS_HIP_CHECK(hipMemcpyAsync(h_state, state.p, st_bytes, hipMemcpyDeviceToHost, s));
-    CS_HIP_CHECK(hipEventRecord(round_done.e, s));
-    // front half of the next round: on the side stream once both rounds are prefiltered (before that
-    // the rounds are short and the exact count of round i+1 would compete with round i), else behind
-    // this round on the main stream
+    CS_HIP_CHECK(hipMemcpyAsync(c.sc.h_state, c.sc.state.p, c.sc.st_bytes, hipMemcpyDeviceToHost, s));
+    CS_HIP_CHECK(hipEventRecord(c.round_done.e, s));
     Front nxt;
-    const bool have_next = it0 + b < max_iter;
+    const int it1 = cur.it0 + cur.b;
+    const bool have_next = it1 < max_iter;
     if (have_next) {
-      const bool nxt_pf = pf_alloc && it0 + b >= pf_from;
-      hipStream_t st = (side && pf && nxt_pf) ? side : s;
-      nxt = enqueue_front(it0 + b, cur.par ^ 1, st);
+      // on the side stream once both rounds are prefiltered: before that the rounds are short and the exact count of
+      // round i+1 would compete with round i
+      nxt = c.enqueue_front(it1, cur.par ^ 1, (c.side && cur.pf && c.prefiltered(it1)) ? c.side : s);
       if (nxt.on_side) {
         side_pending = true;
         side_par = nxt.par;
       }
       CS_LAUNCH_CHECK();
     }
-    CS_HIP_CHECK(hipEventSynchronize(round_done.e));
-    memcpy(hp.data(), h_state, st_probs);
-    memcpy(h_surv.data(), h_state + st_probs + cur.par * st_cnt, sizeof(int32_t) * n_prob);
-    int h_active = 0;
-    memcpy(&h_active, h_state + st_probs + cur.par * st_cnt + st_surv, sizeof(int));
-    if (pf) {
-      max_surv_prev = 0;
-      for (int p = 0; p < n_prob; ++p)
-        if (!prev[p].done) {
-          tot_surv += (unsigned long long)h_surv[p];
-          if (h_surv[p] > max_surv_prev) max_surv_prev = h_surv[p];
-        }
-    }
-    if (h_active == 0 || !have_next) break;
+    CS_HIP_CHECK(hipEventSynchronize(c.round_done.e));   // the host's only wait of a round
+    const bool active = c.read_back(cur);
+    if (!active || !have_next) break;
     cur = nxt;
   }
   // a speculative front half may still be running on the side stream (its workgroups see done = 1 and
   // leave): the scratch buffers go back to the main stream's pool only behind it
-  if (side_pending) CS_HIP_CHECK(hipStreamWaitEvent(s, front_done[side_par].e, 0));
-  if (trace_n) {
-    std::vector<unsigned long long> ht(trace_n);
-    CS_HIP_CHECK(hipMemcpy(ht.data(), trace.p, sizeof(unsigned long long) * trace_n, hipMemcpyDeviceToHost));
-    FILE* f = fopen(getenv("CS_PF_TRACE_FILE") ? getenv("CS_PF_TRACE_FILE") : "/tmp/pf_trace.bin", "wb");
-    if (f) {
-      fwrite(ht.data(), sizeof(unsigned long long), trace_n, f);
-      fclose(f);
-    }
-  }
-  g_pf_stats[3] += tot_surv;
-  g_pf_stats[4] += tot_eval;
-  if (stage2 && getenv("CS_RANSAC_STAGE2_STATS")) {   // diagnostics: survivors of the first / second stage of this call
-    unsigned long long h2 = 0;
-    CS_HIP_CHECK(hipMemcpyAsync(&h2, s2_total.p, sizeof(h2), hipMemcpyDeviceToHost, s));
-    CS_HIP_CHECK(hipStreamSynchronize(s));
-    fprintf(stderr, "[cs_ransac_batch] prefilter survivors: stage 1 %llu, stage 2 %llu of %llu hypotheses\n", tot_surv, h2,
-            tot_eval);
-  }
-  if (check) {
-    unsigned long long h_stats[4] = {0, 0, 0, 0};
-    CS_HIP_CHECK(hipMemcpyAsync(h_stats, chk_stats.p, sizeof(h_stats), hipMemcpyDeviceToHost, s));
-    CS_HIP_CHECK(hipStreamSynchronize(s));
-    g_pf_stats[0] += h_stats[0];
-    g_pf_stats[1] += h_stats[1];
-    g_pf_stats[2] += h_stats[2];
-    CS_REQUIRE(h_stats[0] == 0, CS_ERR_INTERNAL,
-               "cs_ransac_batch: prefilter bound violated for %llu hypotheses", h_stats[0]);
-  }
-  hipLaunchKernelGGL(k_ransac_finish, dim3((unsigned)ceil_div(n_prob, 64)), dim3(64), 0, s,
-                     d_probs, n_prob, scale, d_T, d_inliers, d_rmse, d_iters);
-  CS_LAUNCH_CHECK();
-  CS_HIP_CHECK(hipStreamSynchronize(s));
-  side_drain.clean = true;
-  side_hyp_drain.clean = true;
-  return CS_OK;
+  if (side_pending) CS_HIP_CHECK(hipStreamWaitEvent(s, c.front_done[side_par].e, 0));
+  return c.finish(d_T, d_inliers, d_rmse, d_iters);
 }
 
 }  // extern "C"
