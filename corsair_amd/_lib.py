@@ -85,6 +85,13 @@ def _declare(lib):
                                     POINTER(c_int32), c_int, POINTER(c_int64), vp, vp, c_int, c_uint64, c_int,
                                     c_double, c_int, vp, vp, vp, vp, vp]),
         "cs_transform_f64": (c_int, [vp, POINTER(c_int64), POINTER(c_int32), c_int, vp, vp, vp]),
+        "cs_pair_loss_fwd": (c_int, [c_int, POINTER(vp), POINTER(c_int64), POINTER(c_int32), c_int, c_int,
+                                     POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(c_float),
+                                     POINTER(c_double), POINTER(vp), POINTER(c_int64), vp, vp, vp]),
+        "cs_pair_loss_bwd": (c_int, [c_int, POINTER(vp), POINTER(c_int64), POINTER(c_int32), c_int, c_int,
+                                     POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(c_float),
+                                     POINTER(c_double), POINTER(vp), POINTER(c_int64), vp, POINTER(vp),
+                                     POINTER(c_int32), vp]),
         "cs_prof_enable": (None, [c_int]),
         "cs_prof_reset": (None, []),
         "cs_prof_get": (c_int, [c_char_p, POINTER(c_double), POINTER(c_int64)]),

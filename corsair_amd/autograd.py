@@ -181,3 +181,26 @@ class InstanceNormFunction(torch.autograd.Function):
         gb = g.sum(0)
         return (gx.to(x.dtype), gw.to(weight.dtype).reshape(weight.shape), gb.to(weight.dtype).reshape(weight.shape),
                 None, None)
+
+
+class PairLossFunction(torch.autograd.Function):
+    """total, term_losses = PairLossFunction.apply(terms, *mats): cs_pair_loss_fwd / cs_pair_loss_bwd.
+    mats are the distinct feature matrices (f32 [n, C]; `out.F` of the shim as it comes, views with a leading
+    dimension included), terms a list of (a, b, pairs int32 [P, 2], kind, margin, weight) with a, b indices into
+    mats.  total is the f32 scalar, term_losses f64 [T] (for logging: not differentiable).  The backward returns one
+    gradient per matrix, all terms summed into it with integer accumulators: bit-identical from run to run."""
+
+    @staticmethod
+    def forward(ctx, terms, *mats):
+        mats = [_rowmajor(m.detach()) for m in mats]
+        ctx.terms = [(int(t[0]), int(t[1]), t[2].detach(), int(t[3]), float(t[4]), float(t[5])) for t in terms]
+        ctx.save_for_backward(*mats)
+        term_losses, total = B.pair_loss_fwd(mats, ctx.terms)
+        ctx.mark_non_differentiable(term_losses)
+        return total.reshape(()), term_losses
+
+    @staticmethod
+    def backward(ctx, g, _g_terms):
+        mats = list(ctx.saved_tensors)
+        grads = B.pair_loss_bwd(mats, ctx.terms, g.reshape(1).float().contiguous())
+        return (None,) + tuple(gr if need else None for gr, need in zip(grads, ctx.needs_input_grad[1:]))

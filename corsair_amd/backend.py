@@ -594,3 +594,63 @@ def transform_f64(xyz, offsets, seg, T):
     check(_lib.load().cs_transform_f64(ptr(xyz), i64_array(offsets), i32_array(seg), len(seg), ptr(T), ptr(out),
                                        stream_ptr()))
     return out[:total]
+
+
+# ---- metric-learning loss ---------------------------------------------------------------------------
+PAIR_PULL, PAIR_PUSH = 0, 1
+
+
+def _pair_loss_args(mats, terms):
+    """The host side of cs_pair_loss_*: mats = list of f32 [n, C] device tensors (unit inner stride, any leading
+    dimension), terms = list of (a, b, pairs int32 [P, 2], kind, margin, weight) with a, b indices into mats."""
+    if not mats:
+        raise ValueError("pair_loss: no feature matrix")
+    C = int(mats[0].shape[1])
+    lds = []
+    for m in mats:
+        _dev(m, torch.float32, "features")
+        _, ld = _rows(m, "features")
+        if int(m.shape[1]) != C:
+            raise ValueError("pair_loss: the feature matrices differ in width")
+        lds.append(ld)
+    pairs = []
+    for t in terms:
+        p = _dev(t[2], torch.int32, "pairs")
+        if p.dim() != 2 or p.shape[1] != 2:
+            raise ValueError("pair_loss: pairs must be [P, 2]")
+        pairs.append(p.contiguous())
+    vp = (c_void_p * len(mats))(*[m.data_ptr() for m in mats])
+    pp = (c_void_p * max(len(terms), 1))(*[p.data_ptr() if p.numel() else None for p in pairs])
+    head = (len(mats), vp, i64_array([m.shape[0] for m in mats]), i32_array(lds), C, len(terms),
+            i32_array([t[0] for t in terms]), i32_array([t[1] for t in terms]), i32_array([t[3] for t in terms]),
+            (ctypes.c_float * max(len(terms), 1))(*[float(t[4]) for t in terms]),
+            (ctypes.c_double * max(len(terms), 1))(*[float(t[5]) for t in terms]), pp,
+            i64_array([p.shape[0] for p in pairs]))
+    return head, pairs, C
+
+
+def pair_loss_fwd(mats, terms, out=None):
+    """cs_pair_loss_fwd: returns (term losses f64 [T], total f32 [1]) on the device, no host wait.  `out` = the two
+    tensors to write into."""
+    head, keep, _ = _pair_loss_args(mats, terms)
+    dev = mats[0].device
+    if out is None:
+        out = (torch.empty(max(len(terms), 1), dtype=torch.float64, device=dev),
+               torch.empty(1, dtype=torch.float32, device=dev))
+    check(_lib.load().cs_pair_loss_fwd(*head, ptr(out[0]), ptr(out[1]), stream_ptr()))
+    return out[0][:len(terms)], out[1]
+
+
+def pair_loss_bwd(mats, terms, grad_up, out=None):
+    """cs_pair_loss_bwd: the gradient of every matrix of mats (f32 [n, C], all terms summed into one), scaled by the
+    device scalar grad_up (f32, one element).  Returns the list; `out` = tensors to write into."""
+    head, keep, C = _pair_loss_args(mats, terms)
+    g = _dev(grad_up, torch.float32, "upstream gradient").reshape(-1)
+    if g.numel() != 1:
+        raise ValueError("pair_loss_bwd: the upstream gradient is one scalar")
+    if out is None:
+        out = [torch.empty((m.shape[0], C), dtype=torch.float32, device=m.device) for m in mats]
+    lds = [_rows(_dev(o, torch.float32, "gradient"), "gradient")[1] for o in out]
+    gp = (c_void_p * len(out))(*[o.data_ptr() for o in out])
+    check(_lib.load().cs_pair_loss_bwd(*head, ptr(g), gp, i32_array(lds), stream_ptr()))
+    return out

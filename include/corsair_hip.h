@@ -395,10 +395,49 @@ int cs_transform_f64(const float* d_xyz, const int64_t* h_off, const int32_t* h_
                      double* d_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Metric-learning loss on feature pairs: the FCGF-form contrastive loss that the PiP / PiN / NiN lists
+ * of a training batch feed.  The reference ships the pair lists and no loss: this is the specification.
+ *
+ * One call evaluates up to CS_PAIR_LOSS_MAX_TERMS terms over n_mat distinct feature matrices d_mat[m] (f32
+ * [h_rows[m], C] with leading dimension h_ld[m] >= C, 1 <= C <= 256).  Term t pairs rows of matrix h_a[t] (A) with
+ * rows of matrix h_b[t] (B) through d_pairs[t] (int32 [h_npairs[t], 2]: row of A, row of B; at most 2^22 pairs; rows
+ * out of range are a caller error that is not detected), with kind h_kind[t], margin h_margin[t] in [0, 16] and weight
+ * h_weight[t] in [0, 1024].  Several terms may name the same matrix.  h_npairs[t] = 0 is legal: the term is 0 and
+ * contributes no gradient.  PRECONDITION: every feature row has norm <= 8 (the network's rows are unit vectors), so
+ * d <= 16; rows outside it (or non-finite) give meaningless numbers but no fault.
+ * Arithmetic (every operation one IEEE f32 operation unless it says f64; no contraction):
+ *   pair p = (i, j): diff_k = A[i][k] - B[j][k];  s = 0, s = s + diff_k * diff_k for k ascending;  d = sqrt(s);
+ *     h = max(d - m, 0) for PULL, max(m - d, 0) for PUSH;  l_p = h * h.
+ *   value: S_t = sum_p (uint64)((double)l_p * 2^32) (cast truncates), an exact 64-bit integer sum (l_p <= 2^8, so
+ *     S_t <= 2^8 * 2^32 * 2^22 = 2^62);  L_t = w * (double)S_t * 2^-32 / P in f64, 0 when P = 0.
+ *     d_term_loss f64 [n_term] = L_t, d_total f32 [1] = (float)(sum_t L_t), summed in f64 in term order.
+ *   gradient: r_t = (float)((double)w / P).  A pair with h > 0 and d > 0: a = (h + h) * r_t; u_k = diff_k / d;
+ *     e_k = a * u_k (negated for PUSH); row i of A's matrix gets +e_k, row j of B's gets -e_k, each entering a 64-bit
+ *     integer accumulator as (int64)((double)e_k * 2^44) (cast truncates toward zero; |e_k| <= 32 w / P, so an
+ *     accumulator stays below 32 * 1024 * 2^44 = 2^59 even if every pair of a term hits one row).  All terms'
+ *     contributions to one matrix land in ONE output: d_grad[m] f32 [h_rows[m], C], leading dimension h_ld_grad[m],
+ *     element = (float)((double)acc * 2^-44) * g with g = d_grad_up[0] read on the device.  Every element is written
+ *     (zeros where nothing contributes).
+ * Integer sums: the results do not depend on the order of the pairs, the launch shape or the run.  No host waits.
+ * Refused arguments (status < 0, cs_last_error) leave the outputs untouched.
+ * ---------------------------------------------------------------------------------------- */
+#define CS_PAIR_LOSS_MAX_TERMS 8
+#define CS_PAIR_PULL 0
+#define CS_PAIR_PUSH 1
+int cs_pair_loss_fwd(int n_mat, const float* const* d_mat, const int64_t* h_rows, const int32_t* h_ld, int C,
+                     int n_term, const int32_t* h_a, const int32_t* h_b, const int32_t* h_kind, const float* h_margin,
+                     const double* h_weight, const int32_t* const* d_pairs, const int64_t* h_npairs,
+                     double* d_term_loss, float* d_total, void* stream);
+int cs_pair_loss_bwd(int n_mat, const float* const* d_mat, const int64_t* h_rows, const int32_t* h_ld, int C,
+                     int n_term, const int32_t* h_a, const int32_t* h_b, const int32_t* h_kind, const float* h_margin,
+                     const double* h_weight, const int32_t* const* d_pairs, const int64_t* h_npairs,
+                     const float* d_grad_up, float* const* d_grad, const int32_t* h_ld_grad, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Profiling hooks for bench.py: when enabled the library brackets the launches of each named
  * kernel family with hipEvents on the launch stream and accumulates the elapsed time.
  * names: "conv", "ransac_eval", "ransac_pre", "ransac_hyp", "knn", "chamfer", "topk", "symcut",
- * "kmap".
+ * "kmap", "loss".
  * ---------------------------------------------------------------------------------------- */
 void cs_prof_enable(int on);
 void cs_prof_reset(void);

@@ -2,7 +2,7 @@
 
 The chair training shape: B = 32 triplets of 10 000-point synthetic clouds at voxel 0.03.  Times
 TripletSource.batch (device events, median of a few builds) and, on the same batch, one shim ResUNetBN2C +
-conv1_max_embedding training step over base, positive and negative (forward, contrastive + triplet loss, backward,
+conv1_max_embedding training step over base, positive and negative (forward, losses.corsair_loss, backward,
 SGD).  Reports the pair search's algorithmic bytes (source rows read, candidate target rows probed, pairs and row
 offsets written) over its kernel time as a share of HBM peak, and the same batch's pair mining done by a NumPy + SciPy
 cKDTree.query_ball_point restatement on 16 threads -- a stand-in for the reference's per-point Open3D loop, which is not
@@ -19,10 +19,9 @@ sys.path.insert(0, os.path.join(ROOT, "shim"))
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
-import torch.nn.functional as F  # noqa: E402
 from scipy.spatial import cKDTree  # noqa: E402
 
-from corsair_amd import backend as B, synth, training as TR  # noqa: E402
+from corsair_amd import backend as B, losses, synth, training as TR  # noqa: E402
 from corsair_amd.model import fc, load_model  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0   # MI355X HBM3E peak
@@ -100,15 +99,11 @@ def scipy_restatement(clouds, data, seed):
 def train_step(model, head, opt, data):
     import MinkowskiEngine as ME
 
-    outs, embs = {}, {}
+    feats, embs = {}, {}
     for k in ("base", "pos", "neg"):
         out, feat = model(ME.SparseTensor(data[k + "_feat"], data[k + "_coords"]))
-        outs[k], embs[k] = out.F, F.normalize(head(feat), dim=1)
-    pip, pin = data["PiP_pairs"].long(), data["PiN_pairs"].long()
-    pos_d = (outs["base"][pip[:, 0]] - outs["pos"][pip[:, 1]]).norm(dim=1)
-    neg_d = (outs["base"][pin[:, 0]] - outs["pos"][pin[:, 1]]).norm(dim=1)
-    loss = pos_d.square().mean() + F.relu(1.4 - neg_d).square().mean()
-    loss = loss + F.triplet_margin_loss(embs["base"], embs["pos"], embs["neg"], margin=0.5)
+        feats[k], embs[k] = out.F, head(feat)
+    loss, _ = losses.corsair_loss(feats, embs, data)   # PiP, PiN and NiN in the library + descriptor triplet
     opt.zero_grad()
     loss.backward()
     opt.step()
