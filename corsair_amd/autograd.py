@@ -89,7 +89,8 @@ class AddFunction(torch.autograd.Function):
 
 
 class RowL2NormalizeFunction(torch.autograd.Function):
-    """y = x / ||x|| per row (eps = 0, model/resunet.py:260-262);  dx = (g - y (y . g)) / ||x||."""
+    """y = x / max(||x||, eps) per row (eps = 0: model/resunet.py:260-262).  ||x|| >= eps: dx = (g - y (y . g)) / ||x||;
+    below the clamp the forward is x / eps and dx = g / eps."""
 
     @staticmethod
     def forward(ctx, x, eps):
@@ -101,8 +102,14 @@ class RowL2NormalizeFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, y = ctx.saved_tensors
-        nrm = torch.linalg.vector_norm(x, dim=1, keepdim=True).clamp_min(ctx.eps)
-        return (g - y * (y * g).sum(1, keepdim=True)) / nrm, None
+        # eps as the kernel sees it (an f32 argument).  The kernel clamps its own f32 sum of squares; within a few ulp of
+        # eps this norm may fall on the other side of the clamp -- at the kink, where no gradient is defined
+        eps = torch.tensor(ctx.eps, dtype=x.dtype, device=x.device)
+        nrm = torch.linalg.vector_norm(x, dim=1, keepdim=True)
+        gx = (g - y * (y * g).sum(1, keepdim=True)) / torch.maximum(nrm, eps)
+        if ctx.eps > 0:
+            gx = torch.where(nrm < eps, g / eps, gx)
+        return gx, None
 
 
 def _seg_sum(v, seg):

@@ -54,3 +54,56 @@ def rot_y_pose(deg, trans=(0.05, -0.02, 0.03)):
     T[:3, :3] = [[c, 0, s], [0, 1, 0], [-s, 0, c]]
     T[:3, 3] = trans
     return T
+
+
+# ---- operator-level contract tests: column views of wider buffers ------------------------------------------
+# A quiet NaN whose payload no arithmetic produces: a buffer filled with it shows both a stray WRITE (the bits
+# change) and a stray READ (a NaN reaches the result).
+SENTINEL_BITS = 0x7FC5A5A5
+
+
+def sentinel_buffer(n, ld, device):
+    """f32 [n, ld] device buffer, every element SENTINEL_BITS."""
+    import torch
+
+    return torch.full((n, ld), SENTINEL_BITS, dtype=torch.int32, device=device).view(torch.float32)
+
+
+def column_view(values, device, col0=0, ld=None):
+    """values (f32 ndarray [n, c]) as columns col0 .. col0 + c of a sentinel-filled [n, ld] device buffer: returns
+    (wide buffer, the view).  ld None: a plain contiguous tensor (wide is the tensor itself)."""
+    import torch
+
+    t = torch.from_numpy(np.ascontiguousarray(values, dtype=np.float32)).to(device)
+    if ld is None:
+        return t, t
+    n, c = values.shape
+    assert col0 + c <= ld
+    wide = sentinel_buffer(n, ld, device)
+    wide[:, col0:col0 + c] = t
+    view = wide[:, col0:col0 + c]
+    assert n <= 1 or view.stride(0) == ld
+    return wide, view
+
+
+def outside_view_untouched(wide, col0, c):
+    """Every element of the sentinel-filled buffer outside columns col0 .. col0 + c still holds SENTINEL_BITS."""
+    import torch
+
+    bits = wide.view(torch.int32).cpu().numpy()
+    mask = np.ones(bits.shape, bool)
+    mask[:, col0:col0 + c] = False
+    return bool((bits[mask] == SENTINEL_BITS).all())
+
+
+EPILOGUES = [(mode, res, relu) for mode in ("scale+shift", "shift", "none") for res in (False, True)
+             for relu in (False, True)]   # the twelve combinations of include/corsair_hip.h
+
+
+def epilogue_args(rng, n, c, combo):
+    """(scale, shift, residual, relu) ndarrays / None for one of EPILOGUES; values of mixed sign so that ReLU bites."""
+    mode, res, relu = combo
+    scale = rng.uniform(-1.5, 1.5, c).astype(np.float32) if mode == "scale+shift" else None
+    shift = rng.standard_normal(c).astype(np.float32) if mode != "none" else None
+    residual = rng.standard_normal((n, c)).astype(np.float32) if res else None
+    return scale, shift, residual, relu
