@@ -407,6 +407,48 @@ def knn_feat(qf, qoff, tf, toff, k, qseg=None, tseg=None, qlabel=None, tlabel=No
     return (idx, dist) if return_distance else idx
 
 
+def hardest_negatives(qf, qxyz, qoff, tf, txyz, toff, anchors, radius, qseg=None, tseg=None, return_distance=False):
+    """cs_hardest_negatives: for every anchor (int32 [A] device, GLOBAL rows of qf) the feature-nearest row of its
+    problem's target segment that is not within `radius` of the anchor's canonical point (radius <= 0: no exclusion).
+    qf / tf f32 [n, C] device (unit inner stride, any leading dimension), qxyz / txyz f32 [n, 3] row-aligned with them,
+    qoff / toff host offset lists, qseg / tseg per problem segment ids (default: problem p uses segment p of both).
+    Returns int32 [A] rows LOCAL to the target segment (-1: no admissible row) and, with return_distance, the f64
+    feature distances (+inf for -1).  No host wait."""
+    qf, ld_q = _rows(_dev(qf, torch.float32, "query features"), "query features")
+    tf, ld_t = _rows(_dev(tf, torch.float32, "target features"), "target features")
+    qxyz = _dev(qxyz, torch.float32, "query points").contiguous()
+    txyz = _dev(txyz, torch.float32, "target points").contiguous()
+    anchors = _dev(anchors, torch.int32, "anchors").contiguous()
+    if qf.shape[1] != tf.shape[1]:
+        raise ValueError("hardest_negatives: query and target widths differ")
+    if qxyz.shape != (qf.shape[0], 3) or txyz.shape != (tf.shape[0], 3):
+        raise ValueError("hardest_negatives: points must be [n, 3], one row per feature row")
+    if anchors.dim() != 1:
+        raise ValueError("hardest_negatives: anchors must be 1-D")
+    if qseg is None:
+        qseg = list(range(len(qoff) - 1))
+        tseg = list(range(len(toff) - 1))
+    if len(qseg) != len(tseg):
+        raise ValueError("hardest_negatives: qseg and tseg differ in length")
+    if qseg and (int(qoff[max(qseg) + 1]) > qf.shape[0] or int(toff[max(tseg) + 1]) > tf.shape[0]):
+        raise ValueError("hardest_negatives: the offset tables exceed the feature matrices")
+    n = anchors.shape[0]
+    idx = torch.empty(n, dtype=torch.int32, device=qf.device)
+    dist = torch.empty(n, dtype=torch.float64, device=qf.device) if return_distance else None
+    check(_lib.load().cs_hardest_negatives(ptr(qf), ld_q, ptr(qxyz), i64_array(qoff), ptr(tf), ld_t, ptr(txyz),
+                                           i64_array(toff), i32_array(qseg), i32_array(tseg), len(qseg),
+                                           int(qf.shape[1]), ptr(anchors), n, float(radius), ptr(idx), ptr(dist),
+                                           stream_ptr()))
+    return (idx, dist) if return_distance else idx
+
+
+def hardest_stats(reset=False):
+    """cs_hardest_stats: (anchors answered, of those recomputed exhaustively); counts only under CS_HARDNEG_STATS=1."""
+    out = (ctypes.c_uint64 * 2)()
+    _lib.load().cs_hardest_stats(out, 1 if reset else 0)
+    return int(out[0]), int(out[1])
+
+
 def chamfer_1dir(src, soff, tgt, toff, src_seg, tgt_seg, T):
     """Batched one-directional Chamfer; T f32 [n_prob,4,4] device.  Returns f64 [n_prob]."""
     src = _dev(src, torch.float32, "source").contiguous()

@@ -485,8 +485,7 @@ __global__ void k_knn_rescore16(const KnnWork* __restrict__ work, const float* _
 // the query is flagged and recomputed by the exhaustive kernel (k_knn_feat<16>, flagged tiles only).
 // The answer therefore equals the exhaustive kernel's for every query.
 // ------------------------------------------------------------------------------------------
-constexpr int KNF_PITCH = 56;   // halfs per image row (112 B): conflict-free ds_read_b128 fragments
-constexpr int KNF_ROWS = 192;   // target rows per LDS stage (6 MFMA row tiles, 21 KiB)
+// (KNF_PITCH, KNF_ROWS, the operand rows, the stage and tile helpers and the error budget: nn_common.h, shared with hardneg.hip)
 constexpr int KNF_NG = 2;       // 32-query groups per wave
 constexpr int KNF_QT = 4 * 32 * KNF_NG;  // queries per workgroup
 static_assert(KNF_QT == 256, "tiles of the f16 path and of the exhaustive fallback must coincide");
@@ -506,33 +505,12 @@ __global__ void k_knf_pack_targets(const float* __restrict__ tf, const int64_t* 
   float mx = 0.f;
   for (int64_t j = b + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; j < e; j += (int64_t)gridDim.x * blockDim.x) {
     const int32_t loc = torder ? torder[j] : (int32_t)(j - b);
-    const float* f = tf + (b + loc) * 16;
-    union {
-      _Float16 h[KNF_PITCH];
-      uint4 v[7];
-    } row;
-    double n2 = 0.0;
-#pragma unroll
-    for (int c = 0; c < 16; ++c) {
-      _Float16 hi, lo;
-      knf_split(f[c], &hi, &lo);
-      row.h[c] = hi;
-      row.h[16 + c] = lo;
-      row.h[32 + c] = hi;
-      n2 = fma((double)f[c], (double)f[c], n2);
-    }
-#pragma unroll
-    for (int c = 48; c < KNF_PITCH; ++c) row.h[c] = (_Float16)0.0f;
-    uint4* dst = reinterpret_cast<uint4*>(img + j * KNF_PITCH);
-#pragma unroll
-    for (int c = 0; c < 7; ++c) dst[c] = row.v[c];
+    const double n2 = knf_pack_target_row(tf + (b + loc) * 16, img + j * KNF_PITCH);
     tn32[j] = (float)n2;
     ti32[j] = loc;
     mx = fmaxf(mx, (float)n2 * 1.0000002f);
   }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
-  if ((threadIdx.x & 63) == 0 && mx > 0.f) atomicMax(&seg_t2max_bits[sg], __float_as_uint(mx));
+  knf_seg_max(mx, &seg_t2max_bits[sg]);
 }
 
 // query operand rows: [-2 qh(16) | -2 qh(16) | -2 ql(16)] (scaling by 2 is exact in f16 below the range limit)
@@ -540,24 +518,8 @@ __global__ void k_knf_pack_queries(const float* __restrict__ qf, int64_t n, _Flo
                                    float* __restrict__ qn32) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= n) return;
-  union {
-    _Float16 h[48];
-    uint4 v[6];
-  } row;
-  double n2 = 0.0;
-#pragma unroll
-  for (int c = 0; c < 16; ++c) {
-    _Float16 hi, lo;
-    knf_split(-2.0f * qf[i * 16 + c], &hi, &lo);
-    row.h[c] = hi;
-    row.h[16 + c] = hi;
-    row.h[32 + c] = lo;
-    n2 = fma((double)qf[i * 16 + c], (double)qf[i * 16 + c], n2);
-  }
+  const double n2 = knf_pack_query_row(qf + i * 16, qrows + i * 48);
   qn32[i] = (float)n2 * 1.0000002f;   // |q|^2, rounded up: error budget of the threshold pass
-  uint4* dst = reinterpret_cast<uint4*>(qrows + i * 48);
-#pragma unroll
-  for (int c = 0; c < 6; ++c) dst[c] = row.v[c];
 }
 
 // PASS = 1 (round 5): the THRESHOLD pass.  The shortlist kernel is bound by its hits, not by the matrix cores (MFMA busy
@@ -584,8 +546,7 @@ __global__ __launch_bounds__(256) void k_knn_f16(const KnnWork* __restrict__ wor
                                                  // PASS 1 writes thr0, PASS 0 starts from it (nullptr: from +inf)
                                                  float* __restrict__ thr0, const float* __restrict__ qn32,
                                                  const unsigned* __restrict__ seg_t2max_bits, int kq) {
-  constexpr int STAGE_BYTES = KNF_ROWS * KNF_PITCH * 2;  // 21504
-  constexpr int STAGE_KIB = STAGE_BYTES / 1024;
+  constexpr int STAGE_BYTES = KNF_STAGE_BYTES;
   __shared__ __attribute__((aligned(1024))) char lds[2 * STAGE_BYTES];
   __shared__ __attribute__((aligned(16))) float tn_s[2][KNF_ROWS];
   __shared__ int32_t wrange[2][4];
@@ -665,28 +626,10 @@ __global__ __launch_bounds__(256) void k_knn_f16(const KnnWork* __restrict__ wor
       float cd = pd[g][e];
       int32_t ci = pi[g][e];
       pd[g][e] = INFINITY;
-      if (cd < bd[g][KNF_KK - 1]) {
-        bool carry = false;
-#pragma unroll
-        for (int s2 = 0; s2 < KNF_KK; ++s2) {
-          if (carry || cd < bd[g][s2]) {
-            carry = true;
-            const float td = bd[g][s2];
-            const int32_t ti = bi[g][s2];
-            bd[g][s2] = cd;
-            bi[g][s2] = ci;
-            cd = td;
-            ci = ti;
-          }
-        }
-      }
+      if (cd < bd[g][KNF_KK - 1]) knf_insert(bd[g], bi[g], cd, ci);
     }
     pn[g] = 0;
-    // the two lanes of a query scan disjoint halves of every tile: either one's KNF_KK-th value bounds
-    // the query's KNF_KK-th best
-    float t = bd[g][KNF_KK - 1];
-    t = fminf(t, __shfl_xor(t, 32));
-    thr[g] = fminf(thr[g], t);   // (never above the threshold pass's bound while the lists are still filling)
+    thr[g] = fminf(thr[g], knf_pair_min(bd[g][KNF_KK - 1]));   // (never above the threshold pass's bound while the lists are still filling)
   };
   const char* gimg = reinterpret_cast<const char*>(img + (int64_t)wk.t0 * KNF_PITCH) + lane * 16;
   const unsigned lds_base = __builtin_amdgcn_readfirstlane(lds_addr_of(lds));
@@ -702,14 +645,7 @@ __global__ __launch_bounds__(256) void k_knn_f16(const KnnWork* __restrict__ wor
 #pragma unroll
     for (int g = 0; g < KNF_NG; ++g) thr_eff[g] = (!use_labels || want[g] == lab) ? thr[g] : -INFINITY;
     // (LDS-DMA as inline asm + |t|^2 / row ids loaded before it and stored after the stage's compute: see k_topk_f16)
-    auto issue_dma = [&](int b, int base) {
-      const char* gp = gimg + (int64_t)base * (KNF_PITCH * 2);
-#pragma unroll
-      for (int i = 0; i < (STAGE_KIB + 3) / 4; ++i) {
-        const int piece = wave + 4 * i;
-        if (piece < STAGE_KIB) lds_dma16(gp + piece * 1024, lds_base + b * STAGE_BYTES + piece * 1024);
-      }
-    };
+    auto issue_dma = [&](int b, int base) { knf_issue_dma(gimg, lds_base, wave, b, base); };
     auto load_rows = [&](int base, float& tn) {   // unconditional (clamped) loads
       int r = base + (tid % KNF_ROWS);
       r = r > t_hi - 1 ? t_hi - 1 : r;
@@ -737,19 +673,9 @@ __global__ __launch_bounds__(256) void k_knn_f16(const KnnWork* __restrict__ wor
 #pragma unroll 1
       for (int t = 0; t < KNF_ROWS / 32; ++t) {
         if (base + 32 * t >= t_hi) break;  // whole tile past the range (block-uniform)
-        const _Float16* arow =
-            reinterpret_cast<const _Float16*>(lds + buf * STAGE_BYTES) + (t * 32 + col) * KNF_PITCH + 8 * half;
-        const int32_t tile_pos = base + 32 * t + 4 * half;
         f16x8 a[3];
-#pragma unroll
-        for (int m = 0; m < 3; ++m) a[m] = *reinterpret_cast<const f16x8*>(arow + 16 * m);
-        // accumulator input: |t|^2 of the 16 rows this lane owns: (r & 3) + 8 (r >> 2) + 4 half
         f32x16 c16;
-#pragma unroll
-        for (int q4 = 0; q4 < 4; ++q4) {
-          const float4 v = *reinterpret_cast<const float4*>(&tn_s[buf][t * 32 + 8 * q4 + 4 * half]);
-          c16[4 * q4 + 0] = v.x; c16[4 * q4 + 1] = v.y; c16[4 * q4 + 2] = v.z; c16[4 * q4 + 3] = v.w;
-        }
+        knf_load_tile(lds + buf * STAGE_BYTES, tn_s[buf], t, col, half, a, c16);
 #pragma unroll
         for (int g = 0; g < KNF_NG; ++g) {
           f32x16 d = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0], bop[g][0], c16, 0, 0, 0);
@@ -773,8 +699,7 @@ __global__ __launch_bounds__(256) void k_knn_f16(const KnnWork* __restrict__ wor
             tb[g][5] = __builtin_amdgcn_fmed3f(o4, o5, m);
             continue;
           }
-          d = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1], bop[g][1], d, 0, 0, 0);
-          d = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[2], bop[g][2], d, 0, 0, 0);
+          d = knf_mfma_lo(a, bop[g], d);
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             // one compare + one scalar branch per value while no lane of the wave has a hit (three of four values
@@ -792,7 +717,7 @@ __global__ __launch_bounds__(256) void k_knn_f16(const KnnWork* __restrict__ wor
                   pi[g][e] = pi[g][e - 1];
                 }
                 pd[g][0] = d[r];
-                pi[g][0] = tile_pos + ((r & 3) + 8 * (r >> 2));   // position in the image; its row id is looked up at the end
+                pi[g][0] = base + knf_result_row(t, half, r);   // position in the image; its row id is looked up at the end
                 ++pn[g];
               }
               if (__any(pn[g] == KNF_PEND)) {
@@ -870,14 +795,7 @@ __global__ void k_knn_rescore_f16(const KnnWork* __restrict__ work, const float*
     const int32_t row = ci[c];
     if (row == 0x7fffffff) continue;
     ++n_cand;
-    const float* tp = tf + (wk.t0 + row) * 16;
-    double d = 0.0;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const double diff = q[e] - (double)tp[e];
-      d = fma(diff, diff, d);
-    }
-    double cd = d;
+    double cd = knf_chain16(q, tf + (wk.t0 + row) * 16);
     int32_t cr = row;
     bool carry = false;
 #pragma unroll
@@ -916,14 +834,14 @@ __global__ void k_knn_rescore_f16(const KnnWork* __restrict__ work, const float*
   // (tau = +inf) every target of the query's part is a candidate and nothing was dropped.
   const float tau = cand_tau[orow];
   const double t2max = (double)__uint_as_float(seg_t2max_bits[wk.pad]);
-  const double eps = 0x1.0p-15 * (qn2 + t2max);
+  const double eps = KNF_EPS_REL * (qn2 + t2max);
   bool ok = true;
   if (tau < INFINITY) {
     // need: exact k-th (as |t|^2 - 2 q.t = d - |q|^2) strictly below every dropped target's exact value;
     // equality would need the (distance, row) tie rule, which the shortlist does not know
     ok = n_cand >= k && (dk - qn2) < (double)tau - eps;
   }
-  if (!(qn2 < 1.0e8) || !(t2max < 1.0e8)) ok = false;  // outside the f16 range: not trusted at all
+  if (!(qn2 < KNF_RANGE) || !(t2max < KNF_RANGE)) ok = false;  // outside the f16 range: not trusted at all
   qflag[orow] = ok ? 0 : 1;
   if (!ok) atomicOr(&tile_flag[blockIdx.x], 1);
 }

@@ -2,7 +2,8 @@
 
 The reference ships the datasets and a checkpoint format with optimizer / scheduler / epoch entries
 (utils/ckpts.py:21-63) but no training loop.  A step here is: TripletSource.batch, three shim
-forwards (base, positive, negative), losses.corsair_loss, backward, SGD; the scheduler steps per epoch.
+forwards (base, positive, negative), losses.corsair_loss, backward, SGD; the scheduler steps per epoch.  With
+hardest_weight > 0 the step also mines FCGF's hardest negatives between the forward and the loss (losses.mine_hardest).
 
 A run is a pure function of (data, seed, hyper-parameters): the anchor order of an epoch comes from a Philox generator
 keyed by (seed, epoch), the batch seed of a step is a fixed function of (seed, epoch, step), the validation poses are
@@ -27,6 +28,8 @@ from . import losses, training as TR
 from .utils import ckpts
 
 TIMING_FIELDS = ("seconds", "triplets_per_s")   # the fields of an epoch record that differ from run to run
+PART_KEYS = ("pip", "pin", "nin", "triplet")
+HN_PART_KEYS = ("hn_bp", "hn_pb", "hn_bn")       # logged as well when hardest_weight > 0
 
 
 @dataclass
@@ -51,6 +54,8 @@ class TrainConfig:
     seed: int = 31
     val_period: int = 1              # validate every that many epochs (when there is a validation source)
     bn_momentum: float = 0.05
+    hardest_weight: float = 0.0      # > 0: mine hardest negatives every step, all three HN terms weighted by it
+    exclusion_radius: float = 0.1    # a row within that of the anchor (canonical frame) is no negative
 
 
 _VAL_TAG = 1 << 62
@@ -140,17 +145,36 @@ class Trainer:
             feats[k], embs[k] = out.F, self.head(feat)
         return feats, embs
 
-    def _loss(self, feats, embs, data):
+    @property
+    def mining(self):
+        return self.cfg.hardest_weight > 0
+
+    def _part_keys(self):
+        return PART_KEYS + (HN_PART_KEYS if self.mining else ())
+
+    def _loss(self, feats, embs, data, hardest=None):
         c = self.cfg
+        if hardest is None:
+            return losses.corsair_loss(feats, embs, data, c.pos_margin, c.neg_margin, tuple(c.pair_weights),
+                                       c.triplet_margin, c.triplet_weight)
         return losses.corsair_loss(feats, embs, data, c.pos_margin, c.neg_margin, tuple(c.pair_weights),
-                                   c.triplet_margin, c.triplet_weight)
+                                   c.triplet_margin, c.triplet_weight, hardest=hardest,
+                                   hardest_weights=(c.hardest_weight,) * 3)
+
+    def _batch(self, src, anchors, seed, **kw):
+        if self.mining:
+            kw["mining"] = True
+        return src.batch(anchors, seed, radius=self.cfg.radius, sample=self.cfg.sample, **kw)
+
+    def _mine(self, feats, data):
+        return losses.mine_hardest(feats, data, self.cfg.exclusion_radius) if self.mining else None
 
     def step(self, anchors, seed):
         """One training step on the anchors; returns (loss, parts) as detached device tensors (no host wait)."""
-        data = self.source.batch(anchors, seed, radius=self.cfg.radius, sample=self.cfg.sample)
+        data = self._batch(self.source, anchors, seed)
         with _deterministic():
             feats, embs = self._forward(data)
-            loss, parts = self._loss(feats, embs, data)
+            loss, parts = self._loss(feats, embs, data, self._mine(feats, data))
             self.opt.zero_grad()
             loss.backward()
             self.opt.step()
@@ -170,19 +194,21 @@ class Trainer:
             if len(anchors) < 2:   # the head's BatchNorm1d has no batch statistics of a single descriptor
                 continue
             loss, parts = self.step(anchors, step_seed(c.seed, epoch, s))
-            rows.append(torch.stack([loss.double()] + [parts[k].double() for k in ("pip", "pin", "nin", "triplet")]))
+            rows.append(torch.stack([loss.double()] + [parts[k].double() for k in self._part_keys()]))
             n_trip += len(anchors)
         self.sched.step()
-        mean = torch.stack(rows).mean(0).cpu().tolist() if rows else [float("nan")] * 5   # the epoch's host wait
+        keys = self._part_keys()
+        mean = torch.stack(rows).mean(0).cpu().tolist() if rows else [float("nan")] * (1 + len(keys))   # the epoch's host wait
         dt = time.perf_counter() - t0
         return {"epoch": int(epoch), "steps": len(rows), "loss": mean[0],
-                "parts": dict(zip(("pip", "pin", "nin", "triplet"), mean[1:])), "lr": lr,
+                "parts": dict(zip(keys, mean[1:])), "lr": lr,
                 "seconds": dt, "triplets_per_s": n_trip / dt if dt > 0 else 0.0}
 
     def validate(self):
         """The validation source's anchors in order, FIXED poses, eval mode, no grad: mean loss over the batches, mean
         feature distance over PiP and over PiN + NiN, and the share of slots with |e_b - e_p| < |e_b - e_n| on the
-        normalised descriptors."""
+        normalised descriptors.  With hardest_weight > 0 the loss includes the mined terms and val_hn_dist is the mean
+        feature distance of the mined HN_bp pairs."""
         src, c = self.val_source, self.cfg
         if src is None:
             raise ValueError("validate: the trainer has no validation source")
@@ -192,32 +218,38 @@ class Trainer:
         was = self.model.training, self.head.training
         self.model.eval()
         self.head.eval()
-        acc = torch.zeros(6, dtype=torch.float64, device=src.device)   # loss, d_pos, n_pos, d_neg, n_neg, correct
+        # loss, d_pos, n_pos, d_neg, n_neg, correct, d_hn, n_hn
+        acc = torch.zeros(8, dtype=torch.float64, device=src.device)
         batches = 0
         with torch.no_grad():
             for s, i0 in enumerate(range(0, n, c.batch_size)):
                 anchors = list(range(i0, min(n, i0 + c.batch_size)))
-                data = src.batch(anchors, step_seed(c.seed, 0xFFFFFFFF, s), transforms=self._val_T[anchors],
-                                 radius=c.radius, sample=c.sample)
+                data = self._batch(src, anchors, step_seed(c.seed, 0xFFFFFFFF, s), transforms=self._val_T[anchors])
                 feats, embs = self._forward(data)
-                loss, _ = self._loss(feats, embs, data)
+                hardest = self._mine(feats, data)
+                loss, _ = self._loss(feats, embs, data, hardest)
 
-                def dist(key, other):
-                    p = data[key].long()
+                def dist(key, other, lists=data):
+                    p = lists[key].long()
                     return (feats["base"][p[:, 0]] - feats[other][p[:, 1]]).norm(dim=1).double()
 
                 dp = dist("PiP_pairs", "pos")
                 dn = torch.cat([dist("PiN_pairs", "pos"), dist("NiN_pairs", "neg")])
                 e = {k: torch.nn.functional.normalize(v, dim=1) for k, v in embs.items()}
                 ok = (e["base"] - e["pos"]).norm(dim=1) < (e["base"] - e["neg"]).norm(dim=1)
+                dh = dist("HN_bp_pairs", "pos", hardest) if hardest is not None else dp.new_zeros(0)
                 acc += torch.stack([loss.double(), dp.sum(), dp.new_tensor(dp.numel()), dn.sum(),
-                                    dn.new_tensor(dn.numel()), ok.sum().double()])
+                                    dn.new_tensor(dn.numel()), ok.sum().double(), dh.sum(),
+                                    dh.new_tensor(dh.numel())])
                 batches += 1
         self.model.train(was[0])
         self.head.train(was[1])
         a = acc.cpu().tolist()
-        return {"val_loss": a[0] / max(batches, 1), "val_pos_dist": a[1] / max(a[2], 1.0),
-                "val_neg_dist": a[3] / max(a[4], 1.0), "val_triplet_acc": a[5] / max(n, 1)}
+        rec = {"val_loss": a[0] / max(batches, 1), "val_pos_dist": a[1] / max(a[2], 1.0),
+               "val_neg_dist": a[3] / max(a[4], 1.0), "val_triplet_acc": a[5] / max(n, 1)}
+        if self.mining:
+            rec["val_hn_dist"] = a[6] / max(a[7], 1.0)
+        return rec
 
     def fit(self, start_epoch, epochs, out_dir):
         """Epochs start_epoch .. start_epoch + epochs - 1.  After every epoch: epoch_%03d.pth and last.pth
@@ -229,7 +261,8 @@ class Trainer:
             if self.val_source is not None and self.cfg.val_period > 0 and (epoch + 1) % self.cfg.val_period == 0:
                 rec.update(self.validate())
             for name in ("epoch_%03d.pth" % epoch, "last.pth"):
-                ckpts.save_checkpoint(self.model, self.head, self.opt, self.sched, epoch, out_dir, name)
+                ckpts.save_checkpoint(self.model, self.head, self.opt, self.sched, epoch, out_dir, name,
+                                      config=dataclasses.asdict(self.cfg))
             line = json.dumps(rec)
             print(line, flush=True)
             with open(os.path.join(out_dir, "log.jsonl"), "a") as f:
@@ -274,6 +307,16 @@ def build_parser():
         else:
             ap.add_argument(flag, type=type(v), default=v)
     return ap
+
+
+def config_from_checkpoint(path):
+    """The TrainConfig a checkpoint of fit was written with (None when the file stores none)."""
+    d = ckpts.load_config(path)
+    if d is None:
+        return None
+    names = {f.name for f in dataclasses.fields(TrainConfig)}
+    kw = {k: tuple(v) if isinstance(v, list) else v for k, v in d.items() if k in names}
+    return TrainConfig(**kw)
 
 
 def config_from_args(a):

@@ -164,14 +164,18 @@ class TripletSource:
         B.sample_pairs(canon, out_off, base_seg, pos_seg, neg_seg, list(slots), row_base, row_ptr, tgt_idx, 1, seed,
                        rnd, radius, sample, out=bufs)
         counts = np.stack([np.minimum(n_pos, sample), h_counts[:, 2], h_counts[:, 3]], 1)
-        return {"ok": ok, "grid": grid, "origin": origin, "out_off": np.asarray(out_off, np.int64), "pairs": bufs[:3],
+        return {"ok": ok, "grid": grid, "origin": origin, "canon": canon, "out_off": np.asarray(out_off, np.int64), "pairs": bufs[:3],
                 "counts": counts, "n_pos": n_pos}
 
-    def batch(self, anchors, seed, transforms=None, radius=0.03, sample=1024):
+    def batch(self, anchors, seed, transforms=None, radius=0.03, sample=1024, mining=False):
         """One training batch with collate_pair_fn's keys (datasets/ChairDataset.py:130-237), all on the device.
 
         anchors: object indices (after filter_data); transforms None = train mode (random poses), else f64/f32
-        [B, 3, 4, 4] fixed poses (fix_trans[index] layout: base, positive, negative) used verbatim."""
+        [B, 3, 4, 4] fixed poses (fix_trans[index] layout: base, positive, negative) used verbatim.
+
+        mining=True adds what losses.mine_hardest needs: base_canon / pos_canon / neg_canon (f32 [n, 3] device: the
+        kept CANONICAL points, rows as *_coords) and base_off / pos_off / neg_off (host int64 [B + 1]: the row offsets
+        of the slots); every other entry is the same, and no host wait is added."""
         anchors = [int(a) for a in anchors]
         nb = len(anchors)
         if nb == 0:
@@ -209,13 +213,14 @@ class TripletSource:
                              f"{[anchors[b] for b in pending]}")
         self.last_stats = {"rounds": len(results), "host_waits": waits,
                            "slot_round": [done[b][0] for b in range(nb)]}
-        return self._assemble(results, done, nb, sample)
+        return self._assemble(results, done, nb, sample, mining)
 
-    def _assemble(self, results, done, nb, sample):
+    def _assemble(self, results, done, nb, sample, mining=False):
         dev = self.device
         row_off = np.concatenate([[0], np.cumsum([r["out_off"][-1] for r in results])]).astype(np.int64)
         grid = torch.cat([r["grid"] for r in results], 0)
         origin = torch.cat([r["origin"] for r in results], 0)
+        canon = torch.cat([r["canon"] for r in results], 0) if mining else None
         pair_off = np.concatenate([[0], np.cumsum([r["pairs"][0].shape[0] for r in results])]).astype(np.int64)
         rr = np.array([done[b][0] for b in range(nb)])
         qq = np.array([done[b][1] for b in range(nb)])
@@ -235,10 +240,15 @@ class TripletSource:
             data[name + "_coords"] = c
             data[name + "_feat"] = torch.ones((c.shape[0], 1), dtype=torch.float32, device=dev)
             data[name + "_origin"] = origin[idx]
+            if mining:
+                data[name + "_canon"] = canon[idx]
             data[name + "_T"] = torch.from_numpy(np.stack([done[b][3][k] for b in range(nb)]).astype(np.float32)).to(dev)
             data[name + "_idx"] = torch.from_numpy(
                 np.array([done[b][2][k] for b in range(nb)], np.int32)).to(dev)
             data[name + "_sym"] = torch.from_numpy(self.sym[[int(done[b][2][k]) for b in range(nb)]].astype(np.int32)).to(dev)
+        if mining:
+            for name in sizes:
+                data[name + "_off"] = np.concatenate([[0], np.cumsum(sizes[name])]).astype(np.int64)
         for li, (name, other) in enumerate((("PiP", "pos"), ("PiN", "pos"), ("NiN", "neg"))):
             buf = torch.cat([r["pairs"][li] for r in results], 0)
             cnt = np.array([results[r]["counts"][q, li] for r, q in zip(rr, qq)], np.int64)

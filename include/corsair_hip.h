@@ -434,10 +434,52 @@ int cs_pair_loss_bwd(int n_mat, const float* const* d_mat, const int64_t* h_rows
                      const float* d_grad_up, float* const* d_grad, const int32_t* h_ld_grad, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Hardest negatives in feature space: for every anchor row of a query cloud, the feature-nearest row of the
+ * problem's target cloud that is not a spatial neighbour of the anchor in the canonical frame.  FCGF trains the
+ * contrastive loss of cs_pair_loss_* with such negatives; the reference ships pair lists and no loss: this
+ * is the specification.
+ *   Features: d_qf f32 [nq, C] with leading dimension ld_q >= C, d_tf likewise with ld_t; 1 <= C <= 256.
+ *   Points: d_qxyz / d_txyz f32 [., 3] (contiguous), the canonical points, row-aligned with the features.
+ *   Segments and problems: segment tables h_qoff / h_toff, problem p searches target segment h_tseg[p] for the anchors
+ *     of query segment h_qseg[p], p < n_prob, as in cs_knn_feat.  A query segment may appear in at most one problem
+ *     (otherwise status < 0): an anchor has exactly one problem.
+ *   Anchors: d_anchor int32 [A], GLOBAL query rows in any order, duplicates allowed.  An anchor belongs to the problem
+ *     whose query segment contains its row; the library finds it on the device from the offsets it uploads once (no
+ *     per-problem anchor table).  Anchors live on the device and the call does not wait, so an anchor whose row is
+ *     outside [0, h_qoff[last]) or whose segment is in no problem cannot be refused by the status: it is answered
+ *     -1 / +inf.
+ *   Admissibility: target row j of the problem's target segment is admissible for anchor row i iff
+ *     NOT ((dx*dx + dy*dy) + dz*dz) < r*r   with d. = (double)q. - (double)t., every operation one f64 operation,
+ *     no contraction, r*r = radius * radius in f64 -- the PiP test of cs_radius_pairs itself.  radius <= 0 admits
+ *     every row.
+ *   Result: the admissible row of smallest f64 squared feature distance d = 0, d = fma(diff_c, diff_c, d) with
+ *     diff_c = (double)q_c - (double)t_c for c ascending from 0 (the canonical k-NN arithmetic); ties go to
+ *     the smaller row index.
+ *   Outputs: d_idx int32 [A] = that row LOCAL to the target segment, -1 when no row is admissible (an empty target
+ *     segment included); d_dist f64 [A], optional = sqrt(d), +inf for -1.  Entry a answers d_anchor[a].
+ *   Stream behaviour: everything is enqueued on `stream`; no host waits, no float atomics.  The result does not depend
+ *     on the order of the anchors or on the launch shape.  A = 0 and n_prob = 0 are legal.  Refused arguments
+ *     (status < 0, cs_last_error) leave the outputs untouched.
+ *   Paths: C = 16 ranks on the f16 matrix cores (hi / lo cut of every feature), evaluates the shortlisted rows with
+ *     the canonical chain and the exact admissibility test and accepts a winner only when every row that was not
+ *     evaluated exactly has a lower bound above the winner's exact distance (a tie counts as not vouched for); the
+ *     other anchors, every other C, and every anchor under CS_HARDNEG_MFMA=0 go through the exhaustive kernel.  All
+ *     return the same indices and distances.
+ *   cs_hardest_stats: out = {anchors answered, of those recomputed exhaustively}, counted only while the environment
+ *     variable CS_HARDNEG_STATS=1 (the count synchronises), as cs_knn_shortlist_stats.
+ * Profile family "hardneg".
+ * ---------------------------------------------------------------------------------------- */
+int cs_hardest_negatives(const float* d_qf, int ld_q, const float* d_qxyz, const int64_t* h_qoff, const float* d_tf,
+                         int ld_t, const float* d_txyz, const int64_t* h_toff, const int32_t* h_qseg,
+                         const int32_t* h_tseg, int n_prob, int C, const int32_t* d_anchor, int64_t A, double radius,
+                         int32_t* d_idx, double* d_dist, void* stream);
+void cs_hardest_stats(uint64_t out[2], int reset);
+
+/* ------------------------------------------------------------------------------------------
  * Profiling hooks for bench.py: when enabled the library brackets the launches of each named
  * kernel family with hipEvents on the launch stream and accumulates the elapsed time.
  * names: "conv", "ransac_eval", "ransac_pre", "ransac_hyp", "knn", "chamfer", "topk", "symcut",
- * "kmap", "loss".
+ * "kmap", "loss", "hardneg".
  * ---------------------------------------------------------------------------------------- */
 void cs_prof_enable(int on);
 void cs_prof_reset(void);
