@@ -6,7 +6,6 @@ device buffers and the stream.  No CPU fallback: inputs must be CUDA(HIP) tensor
 from __future__ import annotations
 
 import ctypes
-import os
 from ctypes import c_void_p
 
 import numpy as np
@@ -252,9 +251,6 @@ def conv_dgrad(kmap, rev_kmap, g, weight):
     (no kernel of its own).  rev_kmap: for a stride-1 map the map itself (None is accepted), for a strided map
     (fine -> coarse) the transposed map coarse -> fine, for a transposed map the strided map fine -> coarse;
     ignored for kmap None (1x1)."""
-    if os.environ.get("CS_CONV_SPLIT", "0") not in ("", "0"):
-        raise _lib.CorsairHipError("conv_dgrad: the CS_CONV_SPLIT experiment caches cut weights per pointer and would "
-                                   "hand back stale ones for the temporary permuted weights; unset it to train")
     wt = dgrad_weight(kmap, weight)
     if kmap is None:
         return conv_fwd(None, g, wt)

@@ -1,5 +1,5 @@
-// Sparse convolution forward (output-stationary gather -> f32 MFMA -> fused epilogue) and the
-// small dense row ops of the ResUNet (affine/ReLU/residual, row L2 normalise, per-sample max).
+// Sparse convolution forward (output-stationary gather -> f32 MFMA -> fused epilogue).  The small dense row ops
+// of the ResUNet (affine/ReLU/residual, row L2 normalise, per-sample max, instance norm) live in rowops.hip.
 //
 // Replaces MinkowskiConvolution / MinkowskiConvolutionTranspose / MinkowskiBatchNorm(eval) /
 // MEF.relu / SparseTensor.__iadd__ as used by model/resunet.py:207-280 and
@@ -23,28 +23,13 @@
 //   * epilogue (BN affine / bias, residual add, ReLU) is applied to the accumulators and written
 //     with an arbitrary leading dimension so decoder outputs land directly in the concat buffer.
 #include "common.h"
-#include <map>
-#include <mutex>
-#include <tuple>
-#include <type_traits>
-#include <vector>
+#include "conv_epilogue.h"
 #include <algorithm>
+#include <vector>
 
 namespace cs {
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
-
-__device__ __forceinline__ float epilogue(float v, int c, const float* __restrict__ scale,
-                                          const float* __restrict__ shift, const float* res_row,
-                                          int relu) {
-  if (scale)
-    v = __fmaf_rn(v, scale[c], shift[c]);
-  else if (shift)
-    v = v + shift[c];
-  if (res_row) v = v + res_row[c];
-  if (relu) v = fmaxf(v, 0.0f);
-  return v;
-}
 
 template <int WM, int WN, int NT>
 __global__ __launch_bounds__(256) void k_conv_mfma(
@@ -604,258 +589,6 @@ __global__ __launch_bounds__(256) void k_conv_dma(
   }
 }
 
-// ------------------------------------------------------------------------------------------------
-// EXPERIMENT, off by default (CS_CONV_SPLIT=3 or 2; SURVEY 8d: "bf16 only behind a parity-checked flag"):
-// the same convolutions on the bf16 matrix cores.  The exact chain above runs on the SIMD's f32 vector ALU (157 TF peak);
-// v_mfma_f32_32x32x16_bf16 is a true matrix-core instruction (16x the rate), so every f32 operand is cut into NS bf16
-// pieces (truncation: a = hi + mid + lo EXACTLY for NS = 3, every piece 8 significant bits) and the products whose
-// weight is above 2^-24 are accumulated in f32: NS = 3 keeps hi.hi, hi.mid, mid.hi, mid.mid, hi.lo, lo.hi (6 MFMAs per 16
-// channels, dropped terms <= 2^-23 |a||b|), NS = 2 keeps hi.hi, hi.lo, lo.hi (3 MFMAs, ~2^-16 |a||b|).  NOT bit-identical
-// to the oracle's fma chain (other summation order, other rounding): the default path and every parity test stay on
-// k_conv_dma; tools/conv_split_report.py reports speed and the feature / ranking differences of this path.
-//   * input rows: the same gathered f32 row image as k_conv_dma (LDS-DMA through a buffer descriptor, swizzled slots);
-//     a lane reads ITS 8 channels of a 16-channel step (two ds_read_b128) and cuts them in registers: v_perm_b32 packs the
-//     high halves of two values, v_and + v_sub give the exact remainder -- 5.5 VALU instructions per value for NS = 3.
-//   * weights: cut once per layer (k_split_weights, cached by pointer) into fragment order
-//     [offset][32-channel chunk][piece][step][lane half][cout][8 x bf16]: a B fragment is one ds_read_b128.
-// ------------------------------------------------------------------------------------------------
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-
-template <int NS>
-__global__ void k_split_weights(const float* __restrict__ w, int kvol, int cin, int cout, uint16_t* __restrict__ wq) {
-  // one thread per (offset, channel, cout)
-  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  const int64_t total = (int64_t)kvol * cin * cout;
-  if (i >= total) return;
-  const int col = (int)(i % cout);
-  const int ci = (int)((i / cout) % cin);
-  const int k = (int)(i / ((int64_t)cout * cin));
-  const int cc = ci >> 5, s = (ci >> 4) & 1, h = (ci >> 3) & 1, e = ci & 7;
-  float r = w[i];
-  const int64_t chunk = ((int64_t)k * (cin >> 5) + cc) * (NS * 4);
-#pragma unroll
-  for (int pl = 0; pl < NS; ++pl) {
-    unsigned bits;
-    if (pl == NS - 1 && NS == 2) {
-      // last piece of the two-piece form: round to nearest even instead of cutting
-      const unsigned u = __float_as_uint(r);
-      bits = (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-    } else {
-      bits = __float_as_uint(r) >> 16;
-    }
-    r = r - __uint_as_float(bits << 16);
-    const int seg = (pl * 2 + s) * 2 + h;
-    wq[((chunk + seg) * cout + col) * 8 + e] = (uint16_t)bits;
-  }
-}
-
-template <int RG, int CG, int NT, int NS, bool GATHER>
-__global__ __launch_bounds__(256) void k_conv_split(
-    const int32_t* __restrict__ nbr, const int32_t* __restrict__ rowlist, const uint32_t* __restrict__ gmask, int kvol,
-    int64_t n_out, const float* __restrict__ in, int ld_in, unsigned in_bytes, int cin, const uint16_t* __restrict__ wq, int cout,
-    unsigned wq_bytes, const float* __restrict__ scale, const float* __restrict__ shift,
-    const float* __restrict__ residual, int ld_res, int relu, float* __restrict__ out, int ld_out, int rev_order, int dbg) {
-  constexpr int TM = 32 * RG, TN = 32 * NT * CG;
-  static_assert(RG * CG == 4, "4 waves");
-  constexpr int A_PIECES = 4 / CG;
-  constexpr int SEGS = NS * 4;
-  constexpr int A_BYTES = TM * 128, B_BYTES = SEGS * TN * 16, STAGE_BYTES = A_BYTES + B_BYTES;
-  constexpr int NPB = B_BYTES / 1024;      // 1-KiB DMA instructions per weight stage
-  constexpr int B_PIECES = (NPB + 3) / 4;
-  constexpr int K_END = 32;
-  __shared__ __attribute__((aligned(128))) char lds[2 * STAGE_BYTES];
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int rg = wave / CG;
-  const int cg = wave % CG;
-  const int half = lane >> 5;
-  const int rl = lane & 31;
-  const int64_t row0 = (int64_t)(rev_order ? gridDim.x - 1 - blockIdx.x : blockIdx.x) * TM;
-  const int n0 = blockIdx.y * TN;
-  const int cchunks = cin / 32;
-
-  int32_t my_o = -1;
-  {
-    const int64_t t = row0 + rg * 32 + rl;
-    if (t < n_out) my_o = rowlist ? rowlist[t] : (int32_t)t;
-  }
-  unsigned mymask, kmask;
-  if (GATHER) {
-    const uint32_t* gm = gmask + row0 / 32;
-    mymask = gm[rg];
-    kmask = gm[0];
-#pragma unroll
-    for (int g = 1; g < RG; ++g) kmask |= gm[g];
-  } else {
-    mymask = row0 + rg * 32 < n_out ? 1u : 0u;
-    kmask = 1u;
-  }
-  mymask = __builtin_amdgcn_readfirstlane(mymask);
-  kmask = __builtin_amdgcn_readfirstlane(kmask);
-
-  unsigned a_nbr_off[A_PIECES];
-  unsigned a_c4b[A_PIECES];
-#pragma unroll
-  for (int i = 0; i < A_PIECES; ++i) {
-    const int r = (cg * A_PIECES + i) * 8 + (lane >> 3);
-    const int64_t t = row0 + rg * 32 + r;
-    // GATHER: byte offset of row rowlist[t] of the neighbour table (the table is in OUTPUT-ROW order, the tile in tiling
-    // order: the row index comes from the lane of this wave that holds tile slot r, loaded above as my_o)
-    const int32_t o_r = __shfl(my_o, r);
-    a_nbr_off[i] = GATHER ? (unsigned)(o_r >= 0 ? o_r : 0) * (unsigned)kvol * 4u : (unsigned)(t < n_out ? t : 0);
-    a_c4b[i] = (unsigned)(((lane & 7) ^ ((r >> 1) & 7)) * 16);
-  }
-  // weight stage = [SEGS][TN][16 B], linear in 16-B units u = piece * 64 + lane: segment u / TN, column u % TN
-  unsigned b_voff[B_PIECES];
-#pragma unroll
-  for (int j = 0; j < B_PIECES; ++j) {
-    const int u = (wave + 4 * j) * 64 + lane;
-    const int seg = u / TN, col = u - seg * TN;
-    b_voff[j] = (unsigned)(seg * cout + col) * 16u;
-  }
-  const i32x4 srd_a = make_srd(in, in_bytes);
-  const i32x4 srd_b = make_srd(wq + (size_t)n0 * 8, wq_bytes - (unsigned)n0 * 16u);
-  const unsigned ld_in_b = (unsigned)ld_in * 4u;
-  const unsigned absent_row = in_bytes / ld_in_b;          // = n_in (in_bytes = n_in * ld_in * 4)
-  const unsigned lds_base = __builtin_amdgcn_readfirstlane(lds_addr_of(lds));
-  const unsigned a_lds = lds_base + rg * 4096 + cg * A_PIECES * 1024;
-  const unsigned b_lds = lds_base + A_BYTES + wave * 1024;
-
-  auto step = [&](int& k, int& cc) {
-    const int c1 = cc + 1;
-    const bool wrap = c1 == cchunks;
-    const unsigned rest = k < 31 ? kmask >> (k + 1) : 0u;
-    const int knext = rest ? k + 1 + __builtin_ctz(rest) : K_END;
-    cc = wrap ? 0 : c1;
-    k = k >= K_END ? K_END : (wrap ? knext : k);
-  };
-  auto fetch_src = [&](int k, int32_t (&src)[A_PIECES]) {
-    const char* nbr_k = reinterpret_cast<const char*>(nbr + (k < kvol ? k : 0));
-#pragma unroll
-    for (int i = 0; i < A_PIECES; ++i)
-      src[i] = GATHER ? *reinterpret_cast<const int32_t*>(nbr_k + a_nbr_off[i]) : (int32_t)a_nbr_off[i];
-  };
-  auto stage = [&](int k, int cc, const int32_t (&src)[A_PIECES], int b) {
-    const unsigned a_so = __builtin_amdgcn_readfirstlane((unsigned)cc * 128u);
-    const unsigned b_so = __builtin_amdgcn_readfirstlane((unsigned)((k * cchunks + cc) * SEGS) * (unsigned)cout * 16u);
-    if ((mymask >> k) & 1u) {
-#pragma unroll
-      for (int i = 0; i < A_PIECES; ++i)
-        buf_dma16(__umul24(GATHER ? min((unsigned)src[i], absent_row) : (unsigned)src[i], ld_in_b) + a_c4b[i], srd_a, a_so,
-                  a_lds + b * STAGE_BYTES + i * 1024);
-    }
-#pragma unroll
-    for (int j = 0; j < B_PIECES; ++j)
-      if (wave + 4 * j < NPB) buf_dma16(b_voff[j], srd_b, b_so, b_lds + b * STAGE_BYTES + j * 4096);
-  };
-
-  f32x16 acc[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
-
-  int32_t orow[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) orow[i] = __shfl(my_o, (i & 3) + 8 * (i >> 2) + 4 * half);
-
-  int k = kmask ? __builtin_ctz(kmask) : K_END, cc = 0;
-  int nk = k, ncc = cc;
-  step(nk, ncc);
-  int32_t src_n[A_PIECES];   // neighbour rows of the chunk staged next
-  if (k < K_END) {
-    int32_t s0[A_PIECES];
-    fetch_src(k, s0);
-    fetch_src(nk, src_n);
-    stage(k, 0, s0, 0);
-  }
-  // slot of channel block q (4 channels) of row rl: q ^ ((rl >> 1) & 7); this lane reads blocks 4 s + 2 half + {0, 1}
-  const unsigned a_rd0 = rg * 4096 + rl * 128 + ((((rl >> 1) & 7) ^ (2 * half)) << 4);
-  const unsigned b_rd0 = A_BYTES + (half * TN + cg * 32 * NT + rl) * 16;
-  int buf = 0;
-  while (k < K_END) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    const bool active = (mymask >> k) & 1u;
-    if (nk < K_END && !(dbg & 1)) stage(nk, ncc, src_n, buf ^ 1);
-    int k2 = nk, cc2 = ncc;
-    step(k2, cc2);
-    fetch_src(k2, src_n);   // waited for by the vmcnt(0) of the next iteration, used by its stage()
-    if (active && !(dbg & 2)) {
-      const char* sb = lds + buf * STAGE_BYTES;
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const float4 v0 = *reinterpret_cast<const float4*>(sb + (a_rd0 ^ (unsigned)((4 * s) << 4)));
-        const float4 v1 = *reinterpret_cast<const float4*>(sb + (a_rd0 ^ (unsigned)((4 * s + 1) << 4)));
-        float r[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-        union {
-          unsigned u[4];
-          bf16x8 v;
-        } ap[NS];
-#pragma unroll
-        for (int pl = 0; pl < NS; ++pl) {
-#pragma unroll
-          for (int e2 = 0; e2 < 4; ++e2) {
-            const unsigned x = __float_as_uint(r[2 * e2]), y = __float_as_uint(r[2 * e2 + 1]);
-            if (pl == NS - 1 && NS == 2) {
-              unsigned pk;
-              asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(pk) : "v"(r[2 * e2]), "v"(r[2 * e2 + 1]));
-              ap[pl].u[e2] = pk;
-            } else {
-              ap[pl].u[e2] = __builtin_amdgcn_perm(y, x, 0x07060302u);
-              if (pl + 1 < NS) {
-                r[2 * e2] = r[2 * e2] - __uint_as_float(x & 0xffff0000u);
-                r[2 * e2 + 1] = r[2 * e2 + 1] - __uint_as_float(y & 0xffff0000u);
-              }
-            }
-          }
-        }
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-          bf16x8 bp[NS];
-#pragma unroll
-          for (int pl = 0; pl < NS; ++pl)
-            bp[pl] = *reinterpret_cast<const bf16x8*>(sb + b_rd0 + ((pl * 2 + s) * 2 * TN + t * 32) * 16);
-          // smallest products first
-#pragma unroll
-          for (int sum = NS - 1; sum >= 0; --sum)
-#pragma unroll
-            for (int pa = 0; pa <= sum; ++pa) {
-              const int pb = sum - pa;
-              if (pa < NS && pb < NS) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap[pa].v, bp[pb], acc[t], 0, 0, 0);
-            }
-        }
-      }
-    }
-    k = nk;
-    cc = ncc;
-    nk = k2;
-    ncc = cc2;
-    buf ^= 1;
-  }
-
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    const int col = n0 + cg * 32 * NT + t * 32 + (lane & 31);
-    const float sc = scale ? scale[col] : 1.f;
-    const float sh = shift ? shift[col] : 0.f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      if (orow[i] < 0) continue;
-      float v = acc[t][i];
-      if (scale)
-        v = __fmaf_rn(v, sc, sh);
-      else if (shift)
-        v = v + sh;
-      if (residual) v = v + residual[(int64_t)orow[i] * ld_res + col];
-      if (relu) v = fmaxf(v, 0.0f);
-      out[(int64_t)orow[i] * ld_out + col] = v;
-    }
-  }
-}
-
 // Cin = 1 (the 1 -> 32 stem, model/resunet.py:49-57): a 27-term fma chain per output.  A lane first
 // gathers the <= 27 scalar inputs of ITS row (27 independent loads in flight), the wave shares them
 // through LDS and then every lane owns one output channel (its 27 weights in registers) and walks the
@@ -923,8 +656,7 @@ __global__ __launch_bounds__(256) void k_conv_stem(const int32_t* __restrict__ n
   }
 }
 
-
-// Generic VALU path (any cin / cout / alignment; used for cin = 1, the 1 -> 32 stem conv).
+// Generic VALU path (any cin / cout / alignment: whatever neither matrix kernel nor k_conv_stem takes).
 // One thread per (out row, out channel); same canonical fma order.
 __global__ void k_conv_generic(const int32_t* __restrict__ nbr, int kvol, int64_t n_out,
                                const float* __restrict__ in, int ld_in, int cin,
@@ -948,187 +680,203 @@ __global__ void k_conv_generic(const int32_t* __restrict__ nbr, int kvol, int64_
   out[o * ld_out + co] = epilogue(acc, co, scale, shift, res_row, relu);
 }
 
-__global__ void k_affine_act(int64_t n, int c, const float* __restrict__ in, int ld_in,
-                             const float* __restrict__ scale, const float* __restrict__ shift,
-                             const float* __restrict__ residual, int ld_res, int relu,
-                             float* __restrict__ out, int ld_out) {
-  int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (; t < n * c; t += stride) {
-    int64_t r = t / c;
-    int col = (int)(t - r * c);
-    const float* res_row = residual ? residual + r * ld_res : nullptr;
-    out[r * ld_out + col] = epilogue(in[r * ld_in + col], col, scale, shift, res_row, relu);
-  }
-}
-
-// one wave per row; sequential-per-lane partial sums then a fixed xor-tree -> deterministic
-__global__ void k_row_l2norm(int64_t n, int c, const float* __restrict__ in, int ld_in, float eps,
-                             float* __restrict__ out, int ld_out) {
-  int64_t row = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
-  int lane = threadIdx.x & 63;
-  if (row >= n) return;
-  const float* x = in + row * ld_in;
-  float s = 0.0f;
-  for (int i = lane; i < c; i += 64) s = __fmaf_rn(x[i], x[i], s);
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
-  float nrm = sqrtf(s);
-  nrm = fmaxf(nrm, eps);
-  for (int i = lane; i < c; i += 64) out[row * ld_out + i] = x[i] / nrm;
-}
-
-// c <= 16 (the 16-channel voxel features): 16 lanes per row, four rows per wave.  The same butterfly as above from
-// offset 8 down -- the offsets 32 and 16 of the one-wave-per-row kernel only ever add the exact zeros of the lanes
-// beyond c -- so the same sums, bit for bit, with a quarter of the waves and whole 64-B rows per load.
-__global__ void k_row_l2norm16(int64_t n, int c, const float* __restrict__ in, int ld_in, float eps,
-                               float* __restrict__ out, int ld_out) {
-  const int64_t g = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  const int64_t row = g >> 4;
-  const int ch = (int)(g & 15);
-  const bool live = row < n && ch < c;
-  const float x = live ? in[row * ld_in + ch] : 0.0f;
-  float s = __fmaf_rn(x, x, 0.0f);
-#pragma unroll
-  for (int off = 8; off >= 1; off >>= 1) s += __shfl_xor(s, off);
-  float nrm = sqrtf(s);
-  nrm = fmaxf(nrm, eps);
-  if (live) out[row * ld_out + ch] = x / nrm;
-}
-
-__device__ __forceinline__ unsigned f2ord(float f) {
-  unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ord2f(unsigned u) {
-  return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u);
-}
-__global__ void k_segmax_init(unsigned* buf, int64_t n) {
-  int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (t < n) buf[t] = f2ord(-INFINITY);
-}
-// One atomic per RUN of rows of one sample (not one per row): a thread owns one column of a block
-// of SEGMAX_ROWS consecutive rows, keeps the running maximum while the batch index stays the same and flushes it when
-// it changes (rows grouped by sample, the usual case: 32 x fewer atomics; any other order is still correct).
-constexpr int SEGMAX_ROWS = 32;
-__global__ void k_segmax_runs(int64_t n, int c, const float* __restrict__ in, int ld_in,
-                              const int32_t* __restrict__ batch, int batch_ld, int n_batch, unsigned* obuf) {
-  const int col = blockIdx.y * blockDim.x + threadIdx.x;
-  if (col >= c) return;
-  const int64_t r0 = (int64_t)blockIdx.x * SEGMAX_ROWS;
-  const int64_t r1 = r0 + SEGMAX_ROWS < n ? r0 + SEGMAX_ROWS : n;
-  int cur = -1;
-  unsigned best = 0;
-  for (int64_t r = r0; r < r1; ++r) {
-    const int b = batch[r * batch_ld];
-    if (b != cur) {
-      if (cur >= 0 && cur < n_batch) atomicMax(&obuf[(int64_t)cur * c + col], best);
-      cur = b;
-      best = 0;   // f2ord maps every float above 0: the first value of the run replaces it
-    }
-    const unsigned v = f2ord(in[r * ld_in + col]);
-    best = v > best ? v : best;
-  }
-  if (cur >= 0 && cur < n_batch && r1 > r0) atomicMax(&obuf[(int64_t)cur * c + col], best);
-}
-__global__ void k_segmax_fin(unsigned* buf, int64_t n) {
-  int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (t < n) reinterpret_cast<float*>(buf)[t] = ord2f(buf[t]);
-}
-
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-// ------------------------------------------------------------------------------------------------
-// Instance normalisation (MinkowskiInstanceNorm of the IN network variants, model/common.py:23-24):
-// per sample and channel  out = (x - mean) / sqrt(var + eps) * weight + bias  with the biased variance.
-// Fixed summation order (the oracle restates it): a sample's rows in chunks of INORM_CHUNK consecutive
-// rows, f64 sequential sum inside a chunk, chunk sums added in chunk order.  mean and var are rounded to
-// f32, 1/sqrt in f64 rounded to f32, the affine part in f32 without contraction.
-// Rows must be grouped by sample (seg[b] .. seg[b+1], the collate order).
-// ------------------------------------------------------------------------------------------------
-constexpr int INORM_CHUNK = 256;
-constexpr int INORM_SLICES = 64;
-
-__device__ __forceinline__ int64_t inorm_slot(const int32_t* seg, int b) { return (int64_t)(seg[b] / INORM_CHUNK) + b; }
-
-// grid (INORM_SLICES, n_batch, channel groups of 256); thread = channel.  PASS 0: sum of x; PASS 1: sum of
-// (x - mean)^2 with the f32 mean of PASS 0.
-template <int PASS>
-__global__ __launch_bounds__(256) void k_inorm_partial(const float* __restrict__ x, int ld, int c,
-                                                       const int32_t* __restrict__ seg,
-                                                       const float* __restrict__ mean,
-                                                       double* __restrict__ partial) {
-  const int b = blockIdx.y;
-  const int ch = blockIdx.z * 256 + threadIdx.x;
-  if (ch >= c) return;
-  const int r0 = seg[b], r1 = seg[b + 1];
-  const int chunks = (r1 - r0 + INORM_CHUNK - 1) / INORM_CHUNK;
-  const float m = PASS ? mean[(int64_t)b * c + ch] : 0.f;
-  for (int k = blockIdx.x; k < chunks; k += gridDim.x) {
-    const int a = r0 + k * INORM_CHUNK, e = min(r1, a + INORM_CHUNK);
-    double acc = 0.0;
-    for (int r = a; r < e; ++r) {
-      const float v = x[(int64_t)r * ld + ch];
-      if (PASS) {
-        const float d = v - m;
-        acc += (double)d * (double)d;
-      } else {
-        acc += (double)v;
-      }
-    }
-    partial[(inorm_slot(seg, b) + k) * c + ch] = acc;
-  }
-}
-
-// one thread per (sample, channel): chunk sums in order.  PASS 0 -> mean; PASS 1 -> 1 / sqrt(var + eps)
-template <int PASS>
-__global__ void k_inorm_stat(const double* __restrict__ partial, int c, int n_batch,
-                             const int32_t* __restrict__ seg, float eps, float* __restrict__ stat) {
-  const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (t >= (int64_t)n_batch * c) return;
-  const int b = (int)(t / c), ch = (int)(t - (int64_t)b * c);
-  const int len = seg[b + 1] - seg[b];
-  const int chunks = (len + INORM_CHUNK - 1) / INORM_CHUNK;
-  double acc = 0.0;
-  for (int k = 0; k < chunks; ++k) acc += partial[(inorm_slot(seg, b) + k) * c + ch];
-  if (len == 0) {
-    stat[t] = 0.f;
-    return;
-  }
-  const float v = (float)(acc / (double)len);
-  stat[t] = PASS ? (float)(1.0 / sqrt((double)v + (double)eps)) : v;
-}
-
-__global__ void k_inorm_apply(const float* __restrict__ x, int ld_in, int c, int n_batch,
-                              const int32_t* __restrict__ seg, const float* __restrict__ mean,
-                              const float* __restrict__ inv_std, const float* __restrict__ weight,
-                              const float* __restrict__ bias, float* __restrict__ out, int ld_out) {
-  const int b = blockIdx.y;
-  const int r0 = seg[b], r1 = seg[b + 1];
-  const int64_t total = (int64_t)(r1 - r0) * c;
-  for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-    const int r = r0 + (int)(t / c), ch = (int)(t % c);
-    const float d = x[(int64_t)r * ld_in + ch] - mean[(int64_t)b * c + ch];
-    float v = d * inv_std[(int64_t)b * c + ch];
-    if (weight) v = v * weight[ch];
-    if (bias) v = v + bias[ch];
-    out[(int64_t)r * ld_out + ch] = v;
-  }
-}
-
 }  // namespace cs
 
 using namespace cs;
 
 namespace {
-struct SplitKey {
+
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// The validated arguments of one cs_conv_fwd call and the values derived from them.
+struct ConvCall {
+  const cs_kernelmap* km;             // nullptr: 1x1 convolution, row t reads row t
+  int64_t n_in, n_out;
+  const float* in;
+  int ld_in, cin;
   const float* w;
-  int kvol, cin, cout, ns;
-  bool operator<(const SplitKey& o) const {
-    return std::tie(w, kvol, cin, cout, ns) < std::tie(o.w, o.kvol, o.cin, o.cout, o.ns);
-  }
+  int cout;
+  const float *scale, *shift, *residual;
+  int ld_res, relu;
+  float* out;
+  int ld_out;
+  hipStream_t s;
+  int kvol = 1;
+  const int32_t* nbr = nullptr;
+  const int32_t* rowlist = nullptr;
+  const int32_t* nbr_t = nullptr;     // neighbour table (row order) when the tiling order + group masks exist (k_conv_dma)
+  const uint32_t* gmask = nullptr;
+  int64_t in_bytes = 0, w_bytes = 0;  // extent of the input tensor and of the weights
 };
-std::mutex g_split_mu;
-std::map<SplitKey, uint16_t*> g_split_w;   // pieces of a layer's weights (experiment; never freed: a handful of MB)
+
+// The environment knobs, read on EVERY call (tests and sweeps switch them while the library is loaded).
+struct ConvKnobs {
+  bool dma;         // CS_CONV_DMA=0 falls back to the round-1/2 register-staged kernel (k_conv_mfma)
+  int cfg;          // CS_CONV_CFG=<RG><CG><NT> forces one tile shape of k_conv_dma
+  bool rev_order;   // CS_CONV_FWD_ORDER=1: tiles front first instead of heaviest (last) first
+  bool trace;       // CS_CONV_TRACE=1: per-wave phase cycles of every k_conv_dma launch (diagnostics; synchronises)
+};
+
+bool env_starts(const char* name, char c) {
+  const char* v = getenv(name);
+  return v && v[0] == c;
+}
+
+ConvKnobs read_knobs() {
+  ConvKnobs kn;
+  kn.dma = !env_starts("CS_CONV_DMA", '0');
+  kn.cfg = getenv("CS_CONV_CFG") ? atoi(getenv("CS_CONV_CFG")) : 0;
+  kn.rev_order = !env_starts("CS_CONV_FWD_ORDER", '1');
+  kn.trace = env_starts("CS_CONV_TRACE", '1');
+  return kn;
+}
+
+enum class ConvPath { Stem, Dma, Mfma, Generic };
+
+ConvPath choose_path(const ConvCall& c, const ConvKnobs& kn) {
+  // the 1 -> 32 stem has a kernel of its own (CS_CONV_DMA=0 sends it to the generic kernel with the other fallbacks)
+  if (c.cin == 1 && c.cout == 32 && c.kvol == 27 && c.nbr && c.n_in >= 1 && kn.dma) return ConvPath::Stem;
+  const bool mfma_ok = (c.cin % 32 == 0) && (c.cout % 4 == 0) && (c.ld_in % 4 == 0) && aligned16(c.in) && aligned16(c.w);
+  // production path: LDS-DMA staged kernel with per-row-group offset skipping (k_conv_dma).
+  // The DMA kernel addresses rows and weights with 32-bit byte offsets below DMA_OOB and multiplies row
+  // indices as 24-bit integers
+  const bool dma_ok = kn.dma && mfma_ok && c.cout % 32 == 0 && c.kvol <= 27 && (!c.km || (c.nbr_t && c.gmask)) &&
+                      c.in_bytes < (1LL << 31) && c.w_bytes < (1LL << 31) && c.n_in < (1LL << 24) &&
+                      (int64_t)c.ld_in * 4 < (1LL << 24) && c.n_out * (int64_t)c.kvol * 4 < (1LL << 32);
+  if (dma_ok) return ConvPath::Dma;
+  return mfma_ok ? ConvPath::Mfma : ConvPath::Generic;
+}
+
+// Tile shape <RG><CG><NT> of k_conv_dma: the forced one where cout allows it, else the default.
+int dma_tile(int forced, int cout) {
+  int cfg = forced;
+  if ((cfg == 412 || cfg == 221) && cout % 64) cfg = 0;
+  if ((cfg == 222 || cfg == 141 || cfg == 414) && cout % 128) cfg = 0;
+  if (cfg) return cfg;
+  // measured per layer on the stress and chair batches (CS_CONV_CFG sweep, profiles/r3t_conv_cfg_sweep.txt):
+  // the shapes with the smallest LDS footprint win -- 64 x 64 (32 KB, 5 workgroups per CU) for Cout = 64 n
+  // (304 vs 347 us for 4 x 1 x 2 on the stride-2 64 -> 64 layers, 477 vs 525 at stride 1), 32 x 128 (40 KB) for
+  // Cout = 128 n (374 - 394 vs 446 us for 2 x 2 x 2): the kernel is limited by how many workgroups hide each
+  // other's barriers, prologues and epilogues, not by the MFMAs a DMA instruction feeds
+  return cout % 128 == 0 ? 141 : (cout % 64 == 0 ? 221 : 411);
+}
+
+void launch_stem(const ConvCall& c) {
+  hipLaunchKernelGGL((k_conv_stem<32>), dim3((unsigned)ceil_div(c.n_out, 256)), dim3(256), 0, c.s, c.nbr, c.n_out, c.in,
+                     c.ld_in, c.w, c.scale, c.shift, c.residual, c.ld_res, c.relu, c.out, c.ld_out);
+}
+
+template <int RG, int CG, int NT, bool GATHER, bool TRACE>
+void launch_dma_as(const ConvCall& c, unsigned long long* trace, int rev_order) {
+  const dim3 grid((unsigned)ceil_div(c.n_out, 32 * RG), (unsigned)(c.cout / (32 * NT * CG)));
+  hipLaunchKernelGGL((k_conv_dma<RG, CG, NT, GATHER, TRACE>), grid, dim3(256), 0, c.s, c.nbr_t, c.rowlist, c.gmask, c.kvol,
+                     c.n_out, c.in, c.ld_in, (unsigned)c.in_bytes, c.cin, c.w, c.cout, (unsigned)c.w_bytes, c.scale, c.shift,
+                     c.residual, c.ld_res, c.relu, c.out, c.ld_out, trace, rev_order);
+}
+
+// k_conv_dma of one tile shape: the traced kernel when a trace buffer is given, else the gathered or the 1x1 form
+template <int RG, int CG, int NT>
+void launch_dma(const ConvCall& c, unsigned long long* trace, int rev_order) {
+  if (trace)
+    launch_dma_as<RG, CG, NT, true, true>(c, trace, rev_order);
+  else if (c.nbr_t)
+    launch_dma_as<RG, CG, NT, true, false>(c, trace, rev_order);
+  else
+    launch_dma_as<RG, CG, NT, false, false>(c, trace, rev_order);
+}
+
+// k_conv_dma writes 8 counters per wave of every 32-row x 32-column piece of the output
+size_t trace_words(const ConvCall& c) { return (size_t)ceil_div(c.n_out, 32) * (size_t)(c.cout / 32) * 4 * 8; }
+
+// CS_CONV_TRACE=1: per-wave phase cycles of one launch, summed and printed (synchronises; frees `trace`)
+void trace_report(const ConvCall& c, int cfg, unsigned long long* trace) {
+  const size_t trace_n = trace_words(c);
+  std::vector<unsigned long long> h(trace_n);
+  (void)hipStreamSynchronize(c.s);
+  (void)hipMemcpy(h.data(), trace, trace_n * 8, hipMemcpyDeviceToHost);
+  (void)hipFree(trace);
+  double tot = 0, vm = 0, wt = 0, cp = 0, nc = 0, na = 0, nw = 0, td = 0, pro = 0, lp = 0, epi = 0;
+  unsigned long long rmin = ~0ULL, rmax = 0;
+  for (size_t i = 0; i + 8 <= trace_n; i += 8)
+    if (h[i]) {
+      tot += h[i]; vm += h[i + 1]; wt += h[i + 2]; cp += h[i + 3]; nc += h[i + 4]; na += h[i + 5]; nw += 1;
+      td += h[i + 6] & 0xffffffffffULL;
+      const unsigned long long b = h[i + 7] & 0xffffffffULL, p0 = (h[i + 7] >> 32) & 0xffff, l0 = h[i + 7] >> 48,
+                               e0 = h[i + 6] >> 40;
+      pro += p0; lp += l0; epi += e0;
+      rmin = std::min(rmin, b); rmax = std::max(rmax, b + p0 + l0 + e0);
+    }
+  fprintf(stderr, "[conv trace] wave lifetime (us): prologue %.2f loop %.2f epilogue %.2f; kernel span %.1f us; mean resident "
+          "workgroups per CU %.2f\n", pro / nw / 100, lp / nw / 100, epi / nw / 100, (rmax - rmin) / 100.0,
+          (pro + lp + epi) / 4 / (double)(rmax - rmin) / 256);
+  fprintf(stderr, "[conv trace] cfg %d n_out %lld %d->%d waves %.0f: per wave loop %.0f cyc = vmcnt %.0f + barrier %.0f + body %.0f; "
+          "chunks %.1f active %.1f; per chunk: vmcnt %.0f barrier %.0f offsets+fetch %.0f body %.0f\n",
+          cfg, (long long)c.n_out, c.cin, c.cout, nw, tot / nw, vm / nw, wt / nw, cp / nw, nc / nw, na / nw, vm / nc, wt / nc,
+          td / nc, cp / nc);
+}
+
+void run_dma(const ConvCall& c, const ConvKnobs& kn) {
+  unsigned long long* trace = nullptr;
+  if (c.nbr_t && kn.trace) {
+    if (hipMalloc(&trace, trace_words(c) * 8) != hipSuccess) trace = nullptr;
+    if (trace) (void)hipMemsetAsync(trace, 0, trace_words(c) * 8, c.s);
+  }
+  // (a persistent-workgroup variant with next-tile prefetch, k_conv_dma_p, was measured neutral in round 3 -- the
+  // registers the prefetch holds cost the resident workgroup per CU it was meant to make unnecessary -- and was
+  // removed in round 4: HISTORY.md 7c)
+  const int cfg = dma_tile(kn.cfg, c.cout);
+  switch (cfg) {
+    case 412: launch_dma<4, 1, 2>(c, trace, kn.rev_order); break;
+    case 414: launch_dma<4, 1, 4>(c, trace, kn.rev_order); break;
+    case 221: launch_dma<2, 2, 1>(c, trace, kn.rev_order); break;
+    case 222: launch_dma<2, 2, 2>(c, trace, kn.rev_order); break;
+    case 141: launch_dma<1, 4, 1>(c, trace, kn.rev_order); break;
+    default: launch_dma<4, 1, 1>(c, trace, kn.rev_order); break;
+  }
+  if (trace) trace_report(c, cfg, trace);
+}
+
+template <int WM, int WN, int NT>
+void launch_mfma_tile(const ConvCall& c) {
+  const dim3 grid((unsigned)ceil_div(c.n_out, 32 * WM), (unsigned)ceil_div(c.cout, 32 * NT * WN));
+  hipLaunchKernelGGL((k_conv_mfma<WM, WN, NT>), grid, dim3(256), 0, c.s, c.nbr, c.rowlist, c.kvol, c.n_in, c.n_out, c.in,
+                     c.ld_in, c.cin, c.w, c.cout, c.scale, c.shift, c.residual, c.ld_res, c.relu, c.out, c.ld_out);
+}
+
+// Register-staged fallback (k_conv_mfma): what the DMA kernel's addressing limits or CS_CONV_DMA=0 send here
+void launch_mfma(const ConvCall& c) {
+  if (c.cout % 128 == 0 && ceil_div(c.n_out, 64) * (c.cout / 128) <= 512)
+    // few rows (stride 4 / 8 levels of a 32-cloud batch): 32-row x 128-column tiles double the workgroups
+    // and narrow the union of offsets a tile has to walk (stride-4 layers 182 -> 165 us, conv4_tr 133 -> 100)
+    launch_mfma_tile<1, 4, 1>(c);
+  else if (c.cout % 128 == 0)
+    launch_mfma_tile<2, 2, 2>(c);   // 64 x 128 tiles
+  else if (c.cout > 32)
+    launch_mfma_tile<2, 2, 1>(c);
+  else
+    launch_mfma_tile<4, 1, 1>(c);
+}
+
+void launch_generic(const ConvCall& c) {
+  hipLaunchKernelGGL(k_conv_generic, dim3((unsigned)ceil_div(c.n_out * c.cout, 256)), dim3(256), 0, c.s, c.nbr, c.kvol,
+                     c.n_out, c.in, c.ld_in, c.cin, c.w, c.cout, c.scale, c.shift, c.residual, c.ld_res, c.relu, c.out,
+                     c.ld_out);
+}
+
+// profiling: work units = 2 x pairs x Cin x Cout.  The pair count of a freshly built map may still be on its way to the host:
+// waiting for it here stalled the host behind every map build (measured: 4 - 9 % of the profiled pass), so the map
+// collects the factor and delivers the units when the count is known (kernelmap_pairs, cs_kernelmap_free)
+double prof_flop(const ConvCall& c) {
+  const cs_kernelmap* km = c.km;
+  if (!prof_enabled()) return 0.0;
+  const double per_pair = 2.0 * (double)c.cin * (double)c.cout;
+  if (!km) return per_pair * (double)c.n_out;
+  if (km->num_pairs >= 0 || !km->cnt_ready || hipEventQuery(km->cnt_ready) == hipSuccess)
+    return per_pair * (double)kernelmap_pairs(km);
+  kernelmap_defer_prof(const_cast<cs_kernelmap*>(km), per_pair);
+  return 0.0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1146,315 +894,37 @@ int cs_conv_fwd(const cs_kernelmap* km, int64_t n_in, int64_t n_out, const float
   CS_REQUIRE(!d_residual || ld_res >= cout, CS_ERR_INVALID, "cs_conv_fwd: bad residual ld");
   CS_REQUIRE(n_in < (1LL << 31) && n_out < (1LL << 31), CS_ERR_INVALID,
              "cs_conv_fwd: too many rows");
-  int kvol = 1;
-  const int32_t* nbr = nullptr;
-  const int32_t* rowlist = nullptr;
-  const int32_t* nbr_t = nullptr;     // neighbour table (row order) when the tiling order + group masks exist (k_conv_dma)
-  const uint32_t* gmask = nullptr;
   if (km) {
     CS_REQUIRE(km->n_out == n_out && km->n_in == n_in, CS_ERR_INVALID,
                "cs_conv_fwd: kernel map is for %lld -> %lld rows, tensors have %lld -> %lld",
                (long long)km->n_in, (long long)km->n_out, (long long)n_in, (long long)n_out);
-    kvol = km->kvol;
-    nbr = km->d_nbr;
-    rowlist = km->d_rowlist;
-    nbr_t = (km->d_rowlist && km->d_gmask) ? km->d_nbr : nullptr;
-    gmask = km->d_gmask;
   } else {
     CS_REQUIRE(n_in == n_out, CS_ERR_INVALID, "cs_conv_fwd: 1x1 conv needs n_in == n_out");
   }
   if (n_out == 0) return CS_OK;
-  hipStream_t s = (hipStream_t)stream;
-  // profiling: work units = 2 x pairs x Cin x Cout.  The pair count of a freshly built map may still be on its way to the host:
-  // waiting for it here stalled the host behind every map build (measured: 4 - 9 % of the profiled pass), so the map
-  // collects the factor and delivers the units when the count is known (kernelmap_pairs, cs_kernelmap_free)
-  double flop = 0.0;
-  if (prof_enabled()) {
-    const double per_pair = 2.0 * (double)cin * (double)cout;
-    if (!km)
-      flop = per_pair * (double)n_out;
-    else if (km->num_pairs >= 0 || !km->cnt_ready || hipEventQuery(km->cnt_ready) == hipSuccess)
-      flop = per_pair * (double)kernelmap_pairs(km);
-    else
-      kernelmap_defer_prof(const_cast<cs_kernelmap*>(km), per_pair);
+
+  ConvCall c{km, n_in, n_out, d_in, ld_in, cin, d_w, cout, d_scale, d_shift, d_residual, ld_res, relu, d_out, ld_out,
+             (hipStream_t)stream};
+  if (km) {
+    c.kvol = km->kvol;
+    c.nbr = km->d_nbr;
+    c.rowlist = km->d_rowlist;
+    c.nbr_t = (km->d_rowlist && km->d_gmask) ? km->d_nbr : nullptr;
+    c.gmask = km->d_gmask;
   }
-  ProfScope prof("conv", s, flop);
-  const bool mfma_ok = (cin % 32 == 0) && (cout % 4 == 0) && (ld_in % 4 == 0) &&
-                       aligned16(d_in) && aligned16(d_w);
-  // production path: LDS-DMA staged kernel with per-row-group offset skipping (k_conv_dma); CS_CONV_DMA=0 falls
-  // back to the round-1/2 register-staged kernel (k_conv_mfma), CS_CONV_CFG=<RG><CG><NT> forces one tile shape
-  const bool dma_on = !(getenv("CS_CONV_DMA") && getenv("CS_CONV_DMA")[0] == '0');
-  const int dma_cfg = getenv("CS_CONV_CFG") ? atoi(getenv("CS_CONV_CFG")) : 0;
-  // the DMA kernel addresses rows and weights with 32-bit byte offsets below DMA_OOB and multiplies row
-  // indices as 24-bit integers
-  const int64_t in_bytes64 = n_in * (int64_t)ld_in * 4, w_bytes64 = (int64_t)kvol * cin * cout * 4;
-  const bool dma_ok = dma_on && mfma_ok && cout % 32 == 0 && kvol <= 27 && (!km || (nbr_t && gmask)) && in_bytes64 < (1LL << 31) &&
-                      w_bytes64 < (1LL << 31) && n_in < (1LL << 24) && (int64_t)ld_in * 4 < (1LL << 24) &&
-                      n_out * (int64_t)kvol * 4 < (1LL << 32);
-  const unsigned in_bytes = (unsigned)in_bytes64, w_bytes = (unsigned)w_bytes64;
-  // CS_CONV_SPLIT=3 / 2: the bf16-piece experiment (k_conv_split), read per call so that a report can switch it
-  const int split_ns = getenv("CS_CONV_SPLIT") ? atoi(getenv("CS_CONV_SPLIT")) : 0;
-  CS_REQUIRE(split_ns == 0 || split_ns == 2 || split_ns == 3, CS_ERR_INVALID, "cs_conv_fwd: CS_CONV_SPLIT must be 2 or 3");
-  if (cin == 1 && cout == 32 && kvol == 27 && nbr && n_in >= 1 && dma_on) {
-    hipLaunchKernelGGL((k_conv_stem<32>), dim3((unsigned)ceil_div(n_out, 256)), dim3(256), 0, s, nbr, n_out, d_in,
-                       ld_in, d_w, d_scale, d_shift, d_residual, ld_res, relu, d_out, ld_out);
-  } else if (dma_ok && split_ns && nbr_t) {   // (1x1 layers stay on the exact kernel: measured slower in pieces)
-    // experiment (see k_conv_split): bf16 matrix cores, weights cut once per layer and kept by pointer
-    const uint16_t* wq = nullptr;
-    const size_t wq_bytes64 = (size_t)kvol * cin * cout * split_ns * 2;
-    CS_REQUIRE(wq_bytes64 < (1ULL << 31), CS_ERR_INVALID, "cs_conv_fwd: split weights too large");
-    const int64_t w_total = (int64_t)kvol * cin * cout;
-    auto cut = [&](uint16_t* buf) {
-      if (split_ns == 3)
-        hipLaunchKernelGGL(k_split_weights<3>, dim3((unsigned)ceil_div(w_total, 256)), dim3(256), 0, s, d_w, kvol, cin, cout, buf);
-      else
-        hipLaunchKernelGGL(k_split_weights<2>, dim3((unsigned)ceil_div(w_total, 256)), dim3(256), 0, s, d_w, kvol, cin, cout, buf);
-    };
-    // default: the weights are cut on every call into stream-ordered scratch (~10 us).  CS_CONV_SPLIT_CACHE=1 keeps the
-    // pieces per weight POINTER for the life of the process -- only valid while the caller keeps those weights alive
-    // and unchanged (an engine's parameters; tools/conv_split_report.py) -- cs_conv_split_reset() drops them.
-    PoolBuf<uint16_t> wq_scratch;
-    if (getenv("CS_CONV_SPLIT_CACHE") && getenv("CS_CONV_SPLIT_CACHE")[0] == '1') {
-      std::lock_guard<std::mutex> lock(g_split_mu);
-      SplitKey key{d_w, kvol, cin, cout, split_ns};
-      auto it = g_split_w.find(key);
-      if (it == g_split_w.end()) {
-        uint16_t* buf = nullptr;
-        CS_HIP_CHECK(hipMalloc(&buf, wq_bytes64));
-        cut(buf);
-        CS_LAUNCH_CHECK();
-        CS_HIP_CHECK(hipStreamSynchronize(s));   // other streams may use the cached pieces right away
-        it = g_split_w.emplace(key, buf).first;
-      }
-      wq = it->second;
-    } else {
-      pool_use_stream(s);
-      CS_REQUIRE(wq_scratch.alloc(wq_bytes64 / 2), CS_ERR_HIP, "cs_conv_fwd: out of memory for the split weights");
-      cut(wq_scratch.p);
-      CS_LAUNCH_CHECK();
-      wq = wq_scratch.p;
-    }
-    const int rev_order = 1;
-    const int sdbg = getenv("CS_CONV_SPLIT_DBG") ? atoi(getenv("CS_CONV_SPLIT_DBG")) : 0;   // timing probes only (wrong results)
-    int cfg = getenv("CS_CONV_SPLIT_CFG") ? atoi(getenv("CS_CONV_SPLIT_CFG")) : 0;
-    if ((cfg == 412 || cfg == 221) && cout % 64) cfg = 0;
-    if ((cfg == 222 || cfg == 141) && cout % 128) cfg = 0;
-    // the tile shapes of the exact kernel (CS_CONV_SPLIT_CFG sweep on the stress batch, three pieces, whole forward: these
-    // 5.1 - 5.2 ms, 2x2x1 everywhere 4.9 - 5.1, 4x1x2 6.4, 4x1x1 6.6; exact chain 6.0: profiles/r4e_conv_split_cfg_sweep.txt)
-    if (!cfg) cfg = cout % 128 == 0 ? 141 : (cout % 64 == 0 ? 221 : 411);
-#define CS_SPLIT_LAUNCH(RG, CG, NT)                                                                            \
-  do {                                                                                                          \
-    const dim3 grid((unsigned)ceil_div(n_out, 32 * RG), (unsigned)(cout / (32 * NT * CG)));                     \
-    if (split_ns == 3)                                                                                          \
-      hipLaunchKernelGGL((k_conv_split<RG, CG, NT, 3, true>), grid, dim3(256), 0, s, nbr_t, rowlist, gmask, kvol, n_out, d_in, \
-                         ld_in, in_bytes, cin, wq, cout, (unsigned)wq_bytes64, d_scale, d_shift, d_residual, ld_res, relu, d_out, ld_out, rev_order, sdbg); \
-    else                                                                                                        \
-      hipLaunchKernelGGL((k_conv_split<RG, CG, NT, 2, true>), grid, dim3(256), 0, s, nbr_t, rowlist, gmask, kvol, n_out, d_in, \
-                         ld_in, in_bytes, cin, wq, cout, (unsigned)wq_bytes64, d_scale, d_shift, d_residual, ld_res, relu, d_out, ld_out, rev_order, sdbg); \
-  } while (0)
-    switch (cfg) {
-      case 412: CS_SPLIT_LAUNCH(4, 1, 2); break;
-      case 221: CS_SPLIT_LAUNCH(2, 2, 1); break;
-      case 222: CS_SPLIT_LAUNCH(2, 2, 2); break;
-      case 141: CS_SPLIT_LAUNCH(1, 4, 1); break;
-      default: CS_SPLIT_LAUNCH(4, 1, 1); break;
-    }
-#undef CS_SPLIT_LAUNCH
-  } else if (dma_ok) {
-#define CS_DMA_LAUNCH(RG, CG, NT)                                                                              \
-  do {                                                                                                          \
-    const dim3 grid((unsigned)ceil_div(n_out, 32 * RG), (unsigned)(cout / (32 * NT * CG)));                     \
-    if (trace)                                                                                                  \
-      hipLaunchKernelGGL((k_conv_dma<RG, CG, NT, true, true>), grid, dim3(256), 0, s, nbr_t, rowlist, gmask, kvol, n_out, d_in, \
-                         ld_in, in_bytes, cin, d_w, cout, w_bytes, d_scale, d_shift, d_residual, ld_res, relu, d_out, ld_out, trace, rev_order); \
-    else if (nbr_t)                                                                                             \
-      hipLaunchKernelGGL((k_conv_dma<RG, CG, NT, true, false>), grid, dim3(256), 0, s, nbr_t, rowlist, gmask, kvol, n_out, d_in, \
-                         ld_in, in_bytes, cin, d_w, cout, w_bytes, d_scale, d_shift, d_residual, ld_res, relu, d_out, ld_out, trace, rev_order); \
-    else                                                                                                        \
-      hipLaunchKernelGGL((k_conv_dma<RG, CG, NT, false, false>), grid, dim3(256), 0, s, nbr_t, rowlist, gmask, kvol, n_out, d_in, \
-                         ld_in, in_bytes, cin, d_w, cout, w_bytes, d_scale, d_shift, d_residual, ld_res, relu, d_out, ld_out, trace, rev_order); \
-  } while (0)
-    // CS_CONV_TRACE=1: per-wave phase cycles of this launch, summed and printed (diagnostics; synchronises)
-    unsigned long long* trace = nullptr;
-    const size_t trace_n = (size_t)ceil_div(n_out, 32) * (size_t)(cout / 32) * 4 * 8;
-    if (nbr_t && getenv("CS_CONV_TRACE") && getenv("CS_CONV_TRACE")[0] == '1') {
-      if (hipMalloc(&trace, trace_n * 8) != hipSuccess) trace = nullptr;
-      if (trace) (void)hipMemsetAsync(trace, 0, trace_n * 8, s);
-    }
-    // (a persistent-workgroup variant with next-tile prefetch, k_conv_dma_p, was measured neutral in round 3 -- the
-    // registers the prefetch holds cost the resident workgroup per CU it was meant to make unnecessary -- and was
-    // removed in round 4: HISTORY.md 7c)
-    const int rev_order = !(getenv("CS_CONV_FWD_ORDER") && getenv("CS_CONV_FWD_ORDER")[0] == '1');
-    int cfg = dma_cfg;
-    const int64_t t128 = ceil_div(n_out, 128), t64 = ceil_div(n_out, 64);
-    if (cfg == 412 && cout % 64) cfg = 0;
-    if ((cfg == 221) && cout % 64) cfg = 0;
-    if ((cfg == 222 || cfg == 141 || cfg == 414) && cout % 128) cfg = 0;
-    if (!cfg) {
-      // 128-row tiles (4 row groups share a weight slab) while they still give every CU several workgroups,
-      // 64- and 32-row tiles for the coarse levels
-      // measured per layer on the stress and chair batches (CS_CONV_CFG sweep, profiles/r3t_conv_cfg_sweep.txt):
-      // the shapes with the smallest LDS footprint win -- 64 x 64 (32 KB, 5 workgroups per CU) for Cout = 64 n
-      // (304 vs 347 us for 4 x 1 x 2 on the stride-2 64 -> 64 layers, 477 vs 525 at stride 1), 32 x 128 (40 KB) for
-      // Cout = 128 n (374 - 394 vs 446 us for 2 x 2 x 2): the kernel is limited by how many workgroups hide each
-      // other's barriers, prologues and epilogues, not by the MFMAs a DMA instruction feeds
-      (void)t128;
-      (void)t64;
-      if (cout % 128 == 0)
-        cfg = 141;
-      else if (cout % 64 == 0)
-        cfg = 221;
-      else
-        cfg = 411;
-    }
-    switch (cfg) {
-      case 412: CS_DMA_LAUNCH(4, 1, 2); break;
-      case 414: CS_DMA_LAUNCH(4, 1, 4); break;
-      case 221: CS_DMA_LAUNCH(2, 2, 1); break;
-      case 222: CS_DMA_LAUNCH(2, 2, 2); break;
-      case 141: CS_DMA_LAUNCH(1, 4, 1); break;
-      default: CS_DMA_LAUNCH(4, 1, 1); break;
-    }
-#undef CS_DMA_LAUNCH
-    if (trace) {
-      std::vector<unsigned long long> h(trace_n);
-      (void)hipStreamSynchronize(s);
-      (void)hipMemcpy(h.data(), trace, trace_n * 8, hipMemcpyDeviceToHost);
-      (void)hipFree(trace);
-      double tot = 0, vm = 0, wt = 0, cp = 0, nc = 0, na = 0, nw = 0, td = 0, pro = 0, lp = 0, epi = 0;
-      unsigned long long rmin = ~0ULL, rmax = 0;
-      for (size_t i = 0; i + 8 <= trace_n; i += 8)
-        if (h[i]) {
-          tot += h[i]; vm += h[i + 1]; wt += h[i + 2]; cp += h[i + 3]; nc += h[i + 4]; na += h[i + 5]; nw += 1;
-          td += h[i + 6] & 0xffffffffffULL;
-          const unsigned long long b = h[i + 7] & 0xffffffffULL, p0 = (h[i + 7] >> 32) & 0xffff, l0 = h[i + 7] >> 48,
-                                   e0 = h[i + 6] >> 40;
-          pro += p0; lp += l0; epi += e0;
-          rmin = std::min(rmin, b); rmax = std::max(rmax, b + p0 + l0 + e0);
-        }
-      fprintf(stderr, "[conv trace] wave lifetime (us): prologue %.2f loop %.2f epilogue %.2f; kernel span %.1f us; mean resident "
-              "workgroups per CU %.2f\n", pro / nw / 100, lp / nw / 100, epi / nw / 100, (rmax - rmin) / 100.0,
-              (pro + lp + epi) / 4 / (double)(rmax - rmin) / 256);
-      fprintf(stderr, "[conv trace] cfg %d n_out %lld %d->%d waves %.0f: per wave loop %.0f cyc = vmcnt %.0f + barrier %.0f + body %.0f; "
-              "chunks %.1f active %.1f; per chunk: vmcnt %.0f barrier %.0f offsets+fetch %.0f body %.0f\n",
-              cfg, (long long)n_out, cin, cout, nw, tot / nw, vm / nw, wt / nw, cp / nw, nc / nw, na / nw, vm / nc, wt / nc,
-              td / nc, cp / nc);
-    }
-  } else if (mfma_ok) {
-    // 64 x 128 tiles unless that leaves half of the 256 CUs without a workgroup (coarsest level)
-    const bool short_tiles = !(getenv("CS_CONV_TILE") && getenv("CS_CONV_TILE")[0] == '0');
-    if (cout % 128 == 0 && short_tiles && ceil_div(n_out, 64) * (cout / 128) <= 512) {
-      // few rows (stride 4 / 8 levels of a 32-cloud batch): 32-row x 128-column tiles double the workgroups
-      // and narrow the union of offsets a tile has to walk (stride-4 layers 182 -> 165 us, conv4_tr 133 -> 100;
-      // CS_CONV_TILE=0: the 64-row tiles)
-      dim3 grid((unsigned)ceil_div(n_out, 32), (unsigned)(cout / 128));
-      hipLaunchKernelGGL((k_conv_mfma<1, 4, 1>), grid, dim3(256), 0, s, nbr, rowlist, kvol, n_in, n_out,
-                         d_in, ld_in, cin, d_w, cout, d_scale, d_shift, d_residual, ld_res, relu,
-                         d_out, ld_out);
-    } else if (cout % 128 == 0 && ceil_div(n_out, 64) * (cout / 128) > 128) {
-      dim3 grid((unsigned)ceil_div(n_out, 64), (unsigned)(cout / 128));
-      hipLaunchKernelGGL((k_conv_mfma<2, 2, 2>), grid, dim3(256), 0, s, nbr, rowlist, kvol, n_in, n_out,
-                         d_in, ld_in, cin, d_w, cout, d_scale, d_shift, d_residual, ld_res, relu,
-                         d_out, ld_out);
-    } else if (cout > 32) {
-      dim3 grid((unsigned)ceil_div(n_out, 64), (unsigned)ceil_div(cout, 64));
-      hipLaunchKernelGGL((k_conv_mfma<2, 2, 1>), grid, dim3(256), 0, s, nbr, rowlist, kvol, n_in, n_out,
-                         d_in, ld_in, cin, d_w, cout, d_scale, d_shift, d_residual, ld_res, relu,
-                         d_out, ld_out);
-    } else {
-      dim3 grid((unsigned)ceil_div(n_out, 128), 1);
-      hipLaunchKernelGGL((k_conv_mfma<4, 1, 1>), grid, dim3(256), 0, s, nbr, rowlist, kvol, n_in, n_out,
-                         d_in, ld_in, cin, d_w, cout, d_scale, d_shift, d_residual, ld_res, relu,
-                         d_out, ld_out);
-    }
-  } else {
-    const int64_t total = n_out * cout;
-    hipLaunchKernelGGL(k_conv_generic, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, s, nbr,
-                       kvol, n_out, d_in, ld_in, cin, d_w, cout, d_scale, d_shift, d_residual,
-                       ld_res, relu, d_out, ld_out);
+  c.in_bytes = n_in * (int64_t)ld_in * 4;
+  c.w_bytes = (int64_t)c.kvol * cin * cout * 4;
+
+  ProfScope prof("conv", c.s, prof_flop(c));
+  const ConvKnobs kn = read_knobs();
+  switch (choose_path(c, kn)) {
+    case ConvPath::Stem: launch_stem(c); break;
+    case ConvPath::Dma: run_dma(c, kn); break;
+    case ConvPath::Mfma: launch_mfma(c); break;
+    case ConvPath::Generic: launch_generic(c); break;
   }
   CS_LAUNCH_CHECK();
   return CS_OK;
-}
-
-int cs_conv_split_reset(void) {
-  std::lock_guard<std::mutex> lock(g_split_mu);
-  for (auto& kv : g_split_w) (void)hipFree(kv.second);
-  g_split_w.clear();
-  return CS_OK;
-}
-
-int cs_affine_act(int64_t n, int c, const float* d_in, int ld_in, const float* d_scale,
-                  const float* d_shift, const float* d_residual, int ld_res, int relu,
-                  float* d_out, int ld_out, void* stream) {
-  CS_REQUIRE(d_in && d_out && c >= 1 && ld_in >= c && ld_out >= c, CS_ERR_INVALID,
-             "cs_affine_act: bad argument");
-  CS_REQUIRE(!d_scale || d_shift, CS_ERR_INVALID, "cs_affine_act: scale without shift");
-  if (n == 0) return CS_OK;
-  int64_t total = n * c;
-  unsigned g = (unsigned)(ceil_div(total, 256) < 4096 ? ceil_div(total, 256) : 4096);
-  hipLaunchKernelGGL(k_affine_act, dim3(g), dim3(256), 0, (hipStream_t)stream, n, c, d_in, ld_in,
-                     d_scale, d_shift, d_residual, ld_res, relu, d_out, ld_out);
-  CS_LAUNCH_CHECK();
-  return CS_OK;
-}
-
-int cs_row_l2_normalize(int64_t n, int c, const float* d_in, int ld_in, float eps, float* d_out,
-                        int ld_out, void* stream) {
-  CS_REQUIRE(d_in && d_out && c >= 1 && ld_in >= c && ld_out >= c, CS_ERR_INVALID,
-             "cs_row_l2_normalize: bad argument");
-  if (n == 0) return CS_OK;
-  if (c <= 16)
-    hipLaunchKernelGGL(k_row_l2norm16, dim3((unsigned)ceil_div(n * 16, 256)), dim3(256), 0, (hipStream_t)stream, n, c, d_in,
-                       ld_in, eps, d_out, ld_out);
-  else
-    hipLaunchKernelGGL(k_row_l2norm, dim3((unsigned)ceil_div(n, 4)), dim3(256), 0,
-                       (hipStream_t)stream, n, c, d_in, ld_in, eps, d_out, ld_out);
-  CS_LAUNCH_CHECK();
-  return CS_OK;
-}
-
-int cs_segmented_max(int64_t n, int c, const float* d_in, int ld_in, const int32_t* d_batch,
-                     int batch_ld, int n_batch, float* d_out, void* stream) {
-  CS_REQUIRE(d_in && d_batch && d_out && c >= 1 && n_batch >= 0 && batch_ld >= 1,
-             CS_ERR_INVALID, "cs_segmented_max: bad argument");
-  hipStream_t s = (hipStream_t)stream;
-  int64_t on = (int64_t)n_batch * c;
-  if (on == 0) return CS_OK;
-  unsigned* obuf = reinterpret_cast<unsigned*>(d_out);
-  hipLaunchKernelGGL(k_segmax_init, dim3((unsigned)ceil_div(on, 256)), dim3(256), 0, s, obuf, on);
-  if (n > 0)
-    hipLaunchKernelGGL(k_segmax_runs, dim3((unsigned)ceil_div(n, SEGMAX_ROWS), (unsigned)ceil_div(c, 256)), dim3(256), 0, s,
-                       n, c, d_in, ld_in, d_batch, batch_ld, n_batch, obuf);
-  hipLaunchKernelGGL(k_segmax_fin, dim3((unsigned)ceil_div(on, 256)), dim3(256), 0, s, obuf, on);
-  CS_LAUNCH_CHECK();
-  return CS_OK;
-}
-
-int cs_instance_norm(int64_t n, int c, const float* d_in, int ld_in, const int32_t* d_seg, int n_batch,
-                     const float* d_weight, const float* d_bias, float eps, float* d_out, int ld_out,
-                     void* stream) {
-  CS_REQUIRE(d_in && d_out && d_seg && c >= 1 && ld_in >= c && ld_out >= c && n_batch >= 0 && n >= 0 &&
-                 n < (1LL << 31) && eps >= 0.f,
-             CS_ERR_INVALID, "cs_instance_norm: bad argument");
-  if (n == 0 || n_batch == 0) return CS_OK;
-  hipStream_t s = (hipStream_t)stream;
-  pool_use_stream(s);
-  const int64_t slots = n / INORM_CHUNK + n_batch + 1;
-  PoolBuf<double> partial((size_t)slots * c);
-  PoolBuf<float> mean((size_t)n_batch * c), inv_std((size_t)n_batch * c);
-  CS_REQUIRE(partial.p && mean.p && inv_std.p, CS_ERR_HIP, "cs_instance_norm: scratch allocation failed");
-  const dim3 pg(INORM_SLICES, (unsigned)n_batch, (unsigned)ceil_div(c, 256));
-  const unsigned sg = (unsigned)ceil_div((int64_t)n_batch * c, 256);
-  hipLaunchKernelGGL(k_inorm_partial<0>, pg, dim3(256), 0, s, d_in, ld_in, c, d_seg, (const float*)nullptr,
-                     partial.p);
-  hipLaunchKernelGGL(k_inorm_stat<0>, dim3(sg), dim3(256), 0, s, partial.p, c, n_batch, d_seg, eps, mean.p);
-  hipLaunchKernelGGL(k_inorm_partial<1>, pg, dim3(256), 0, s, d_in, ld_in, c, d_seg, mean.p, partial.p);
-  hipLaunchKernelGGL(k_inorm_stat<1>, dim3(sg), dim3(256), 0, s, partial.p, c, n_batch, d_seg, eps, inv_std.p);
-  hipLaunchKernelGGL(k_inorm_apply, dim3(64, (unsigned)n_batch), dim3(256), 0, s, d_in, ld_in, c, n_batch,
-                     d_seg, mean.p, inv_std.p, d_weight, d_bias, d_out, ld_out);
-  CS_LAUNCH_CHECK();
-  return CS_OK;  // no synchronisation: the scratch returns to this thread's stream-ordered cache
 }
 
 }  // extern "C"

@@ -158,14 +158,6 @@ def test_dgrad_matches_f64(gpu, maps, name, cin, cout):
     assert np.all(np.abs(got - ref) <= 4e-5 * sc + 1e-30), (name, cin, cout)
 
 
-def test_dgrad_refuses_split_experiment(gpu, maps, monkeypatch):
-    from corsair_amd import _lib, backend as B
-
-    monkeypatch.setenv("CS_CONV_SPLIT", "3")
-    with pytest.raises(_lib.CorsairHipError, match="CS_CONV_SPLIT"):
-        B.conv_dgrad(maps.s1, None, torch.zeros((maps.s1.n_out, 32), device=gpu), torch.zeros((27, 32, 32), device=gpu))
-
-
 def _shim():
     sys.path.insert(0, os.path.join(ROOT, "shim"))
     import MinkowskiEngine as ME

@@ -12,7 +12,6 @@ tell kernels apart: which kernel ran is a matter for a kernel trace of this modu
   k_conv_dma       test_conv_lds_dma (gathered and 1x1 forms), test_conv_alignment_fallback (its contiguous calls),
                    test_conv_views[dma, 1x1], test_conv_epilogues[dma, 1x1]
   k_conv_stem      test_conv_stem_reads_a_column, test_conv_views[stem]
-  k_conv_split     off by default (an environment-variable experiment): tests/test_gpu_sparse.py bounds it
 and cs_conv_wgrad (conv_bwd.hip): k_wgrad_mfma by the (64, 64) cases, k_wgrad_valu by the (48, 20) cases of
 test_wgrad_slices_and_odd_leading_dimensions / test_wgrad_chunk_boundaries."""
 import zlib
@@ -28,8 +27,7 @@ from tests.test_gpu_conv_backward import _ref_wgrad
 
 pytestmark = pytest.mark.gpu
 
-CONV_ENV = ("CS_CONV_DMA", "CS_CONV_CFG", "CS_CONV_SPLIT", "CS_CONV_SPLIT_CFG", "CS_CONV_SPLIT_CACHE", "CS_CONV_TILE",
-            "CS_CONV_FWD_ORDER", "CS_CONV_TRACE")
+CONV_ENV = ("CS_CONV_DMA", "CS_CONV_CFG", "CS_CONV_FWD_ORDER", "CS_CONV_TRACE")
 FULL = ("scale+shift", True, True)
 
 
