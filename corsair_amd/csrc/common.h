@@ -164,7 +164,6 @@ struct cs_coordmap {
   // per-sample row segments (rows grouped by batch index), filled lazily for the LDS kernel-map path
   int32_t* d_seg = nullptr;      // [n_batch + 1]
   int n_batch = 0;
-  int max_seg = 0;
   int seg_state = 0;             // 0 unknown, 1 available, -1 rows are not grouped by sample
 };
 

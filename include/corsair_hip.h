@@ -42,8 +42,8 @@ extern "C" {
 #define CS_ERR_UNSUPPORTED (-5)
 #define CS_ERR_INTERNAL (-6) /* a self-check of the library failed (e.g. CS_RANSAC_CHECK) */
 
-typedef struct cs_coordmap cs_coordmap;   /* coordinates of one tensor stride + hash index */
-typedef struct cs_kernelmap cs_kernelmap; /* output-stationary neighbour table of one conv  */
+typedef struct cs_coordmap cs_coordmap;   /* coordinates of one tensor stride + hash index (csrc/coordmap.hip) */
+typedef struct cs_kernelmap cs_kernelmap; /* output-stationary neighbour table of one conv (csrc/kernelmap.hip) */
 
 const char* cs_last_error(void);
 int cs_version(void);

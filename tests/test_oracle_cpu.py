@@ -552,13 +552,13 @@ def test_checkpoint_round_trip(tmp_path):
 
 
 def test_tiling_mask_bit_order_is_centre_faces_edges_corners():
-    """coordmap.hip's KORDER (bit j of a row's tiling mask = kernel offset KORDER[j]): the 27 offsets k = (dx+1) + 3 (dy+1) +
+    """kernelmap.hip's KORDER (bit j of a row's tiling mask = kernel offset KORDER[j]): the 27 offsets k = (dx+1) + 3 (dy+1) +
     9 (dz+1) sorted by |d|_1 (centre, six faces, twelve edges, eight corners), then by k -- a permutation, and the table
     tools/exec_ratio_cpu.py evaluates is the same one."""
     import re
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = open(os.path.join(root, "corsair_amd", "csrc", "coordmap.hip")).read()
+    src = open(os.path.join(root, "corsair_amd", "csrc", "kernelmap.hip")).read()
     body = re.search(r"KORDER\[32\]\s*=\s*\{([^}]*)\}", src).group(1)
     table = [int(v) for v in body.split(",")]
     assert len(table) == 32 and table[27:] == [0] * 5

@@ -32,7 +32,7 @@ def inv_gray(m):
     return r
 
 
-# the tiling key of coordmap.hip (round 5): bit j of the mask = kernel offset KORDER[j] (centre, faces, edges, corners),
+# the tiling key of kernelmap.hip (round 5): bit j of the mask = kernel offset KORDER[j] (centre, faces, edges, corners),
 # then the Gray rank; ORDER=k on the command line (4th argument) evaluates the plain-k order of rounds 3-4
 OFFS = [(k % 3 - 1, (k // 3) % 3 - 1, k // 9 - 1) for k in range(27)]
 KORDER = sorted(range(27), key=lambda k: (sum(abs(v) for v in OFFS[k]), k))
