@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes
 from ctypes import c_void_p
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -469,6 +470,66 @@ def hausdorff_1dir(src, soff, tgt, toff, src_seg, tgt_seg, T):
                                         i32_array(src_seg), i32_array(tgt_seg), n_prob, ptr(T), ptr(out),
                                         stream_ptr()))
     return out
+
+
+class IcpResult(NamedTuple):
+    T: torch.Tensor          # f64 [n_prob,4,4]
+    T32: torch.Tensor        # f32 [n_prob,4,4], T cast once
+    fitness: torch.Tensor    # f64 [n_prob]
+    rmse: torch.Tensor       # f64 [n_prob]
+    iters: torch.Tensor      # int32 [n_prob] updates applied
+    ncorr: torch.Tensor      # int32 [n_prob]
+    corr: Optional[torch.Tensor]   # int32, problem-major (problem p at corr_off[p]): local target row or -1
+    corr_off: Optional[list]
+
+
+def icp_batch(src, soff, tgt, toff, src_seg, tgt_seg, T0, max_dist, max_iter=30, relative_fitness=1e-6,
+              relative_rmse=1e-6, return_corr=False):
+    """cs_icp_batch: point-to-point ICP of problem p = source segment src_seg[p] of `src` against target segment
+    tgt_seg[p] of `tgt` (f32 [n,3] device, host offset lists), started at T0[p] (f32 [n_prob,4,4] device).  The semantics
+    are the header comment of cs_icp_batch.  Returns an IcpResult; no host wait."""
+    src = _dev(src, torch.float32, "source").contiguous()
+    tgt = _dev(tgt, torch.float32, "target").contiguous()
+    T0 = _dev(T0, torch.float32, "initial transforms").contiguous()
+    n_prob = len(src_seg)
+    if len(tgt_seg) != n_prob:
+        raise ValueError("icp_batch: src_seg and tgt_seg differ in length")
+    if T0.numel() != 16 * n_prob:
+        raise ValueError("icp_batch: one 4x4 initial transform per problem")
+    if src.dim() != 2 or src.shape[1] != 3 or tgt.dim() != 2 or tgt.shape[1] != 3:
+        raise ValueError("icp_batch: points must be [n, 3]")
+    sane = all(0 <= int(s) < len(soff) - 1 for s in src_seg) and all(0 <= int(t) < len(toff) - 1 for t in tgt_seg)
+    if n_prob and sane and (int(soff[max(src_seg) + 1]) > src.shape[0] or int(toff[max(tgt_seg) + 1]) > tgt.shape[0]):
+        raise ValueError("icp_batch: the offset tables exceed the point arrays")
+    if n_prob and not sane and min(min(src_seg), min(tgt_seg)) >= 0:
+        raise ValueError("icp_batch: a segment id exceeds its offset table")
+    dev = src.device
+    T = torch.empty((n_prob, 4, 4), dtype=torch.float64, device=dev)
+    T32 = torch.empty((n_prob, 4, 4), dtype=torch.float32, device=dev)
+    fitness = torch.empty(n_prob, dtype=torch.float64, device=dev)
+    rmse = torch.empty(n_prob, dtype=torch.float64, device=dev)
+    iters = torch.empty(n_prob, dtype=torch.int32, device=dev)
+    ncorr = torch.empty(n_prob, dtype=torch.int32, device=dev)
+    corr = corr_off = None
+    if return_corr:
+        lens = [int(soff[s + 1]) - int(soff[s]) for s in src_seg] if sane else []
+        corr_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64).tolist()
+        corr = torch.full((max(corr_off[-1], 1),), -1, dtype=torch.int32, device=dev)
+    check(_lib.load().cs_icp_batch(ptr(src), i64_array(soff), ptr(tgt), i64_array(toff), i32_array(src_seg),
+                                   i32_array(tgt_seg), n_prob, ptr(T0), float(max_dist), int(max_iter),
+                                   float(relative_fitness), float(relative_rmse), ptr(T), ptr(T32), ptr(fitness),
+                                   ptr(rmse), ptr(iters), ptr(ncorr), ptr(corr), stream_ptr()))
+    if corr is not None:
+        corr = corr[:corr_off[-1]]
+    return IcpResult(T, T32, fitness, rmse, iters, ncorr, corr, corr_off)
+
+
+def icp_stats(reset=False):
+    """cs_icp_stats: (256-source workgroups answered by the f16 association, of those recomputed exhaustively), summed
+    over the rounds; counts only under CS_ICP_STATS=1."""
+    out = (ctypes.c_uint64 * 2)()
+    _lib.load().cs_icp_stats(out, 1 if reset else 0)
+    return int(out[0]), int(out[1])
 
 
 def ransac_batch(src, tgt, offsets, max_corr, ransac_n=10, max_iter=100000, confidence=0.999, seed=0):

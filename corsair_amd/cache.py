@@ -13,6 +13,10 @@ NAMES = ("Ts_est_ransac", "Ts_est_best", "t_losses_ransac", "t_losses_sym", "r_l
 DTYPES = {"Ts_est_ransac": np.float32, "Ts_est_best": np.float32, "t_losses_ransac": np.float32,
           "t_losses_sym": np.float32, "r_losses_ransac": np.float64, "r_losses_sym": np.float64,
           "sym_ransac_success": np.bool_, "chamfer_dist_ransac": np.float64, "chamfer_dist_sym": np.float64}
+# the extra arrays of a run with ICP refinement (Config.icp_max_iter > 0): written beside the nine, which keep their format
+ICP_NAMES = ("Ts_est_icp", "t_losses_icp", "r_losses_icp", "chamfer_dist_icp", "icp_iters")
+ICP_DTYPES = {"Ts_est_icp": np.float32, "t_losses_icp": np.float32, "r_losses_icp": np.float64,
+              "chamfer_dist_icp": np.float64, "icp_iters": np.int32}
 
 
 def _suffix(register_top1):
@@ -20,22 +24,23 @@ def _suffix(register_top1):
 
 
 def save_results(cache_dir, category, register_top1, results):
-    """results: dict with the NAMES keys; transforms as [Q,4,4] (stored flattened [Q,16] f32)."""
+    """results: dict with the NAMES keys (and the ICP_NAMES keys of a run with ICP refinement); transforms as [Q,4,4]
+    (stored flattened [Q,16] f32)."""
     os.makedirs(cache_dir, exist_ok=True)
     suf = _suffix(register_top1)
-    for name in NAMES:
+    for name in NAMES + tuple(n for n in ICP_NAMES if n in results):
         data = np.asarray(results[name])
         if name.startswith("Ts_est"):
             data = data.reshape(len(data), 16).astype(np.float32)
         np.save(os.path.join(cache_dir, f"{name}_{category}{suf}"), data)
 
 
-def load_results(cache_dir, category, register_top1):
+def load_results(cache_dir, category, register_top1, icp=False):
     """Returns the dict, or None when any of the nine files is missing (the reference then
-    recomputes, evaluation.py:287)."""
+    recomputes, evaluation.py:287).  icp: the ICP_NAMES files are wanted too; a cache without them is a miss."""
     suf = _suffix(register_top1)
     out = {}
-    for name in NAMES:
+    for name in NAMES + (ICP_NAMES if icp else ()):
         path = os.path.join(cache_dir, f"{name}_{category}{suf}")
         if not os.path.exists(path):
             return None

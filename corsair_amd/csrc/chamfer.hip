@@ -195,10 +195,7 @@ __global__ __launch_bounds__(256) void k_chamfer_mfma(const ChamferWork* __restr
 // k_chamfer_mfma (flag array, no host decision).  Coordinates are scaled by 2^9 before the cut so that the lo parts stay
 // normal f16 numbers; |coordinate| >= 60 does not fit and takes the f64 kernel as well.  Results: the same canonical
 // distances as the other two kernels (tests/test_gpu_post.py::test_chamfer_matches_oracle, all three paths).
-constexpr int CHF_PITCH = 24;     // halfs per image row (48 B: conflict-free ds_read_b128 fragments)
-constexpr int CHF_ROWS = 256;     // target rows per LDS stage (8 MFMA row tiles)
-constexpr int CHF_NG = 2;         // 32-source groups per wave
-constexpr float CHF_SCALE = 512.0f;
+// (CHF_PITCH, CHF_ROWS, CHF_NG, CHF_SCALE: nn_common.h -- the ICP's association kernel reads the same image)
 static_assert(4 * 32 * CHF_NG == CHM_ST, "the f16 kernel and its f64 fallback share the work items");
 
 // target image: row j = [th(3) | tl(3) | th(3) | 0(7) | pad(8)] of the scaled coordinates, tn32[j] = |S t|^2 (f64 chain,
@@ -418,6 +415,11 @@ __global__ __launch_bounds__(256) void k_chamfer_f16(const ChamferWork* __restri
   }
 }
 
+void chamfer_pack16(const float* d_tgt, int64_t n, int64_t n_pad, _Float16* img, float* tn32, float4* t4f, hipStream_t s) {
+  hipLaunchKernelGGL(k_chamfer_pack16, dim3((unsigned)ceil_div(n_pad, 256)), dim3(256), 0, s, d_tgt, n, n_pad, img, tn32,
+                     t4f);
+}
+
 __global__ void k_chamfer_finish(const double* __restrict__ partial,
                                  const int32_t* __restrict__ slot_begin,
                                  const int64_t* __restrict__ src_count, int n_prob, int reduce_max,
@@ -484,8 +486,7 @@ static int chamfer_rank(const ChamferOptions& opt, const ChamferWork* d_work, un
   PoolBuf<float4> t4f((size_t)(nt_rows ? nt_rows : 1));
   PoolBuf<int32_t> wflag(n_work);
   CS_REQUIRE(img16.p && tn16.p && wflag.p && t4f.p, CS_ERR_HIP, "cs_chamfer_1dir: scratch allocation failed");
-  hipLaunchKernelGGL(k_chamfer_pack16, dim3((unsigned)ceil_div(n_pad, 256)), dim3(256), 0, s, d_tgt, nt_rows, n_pad,
-                     img16.p, tn16.p, t4f.p);
+  chamfer_pack16(d_tgt, nt_rows, n_pad, img16.p, tn16.p, t4f.p, s);
   hipLaunchKernelGGL(k_chamfer_f16, grid, dim3(256), 0, s, d_work, d_src, t4f.p, img16.p, tn16.p, d_T, reduce_max,
                      partial, wflag.p);
   hipLaunchKernelGGL(k_chamfer_mfma, grid, dim3(256), 0, s, d_work, d_src, d_tgt, t4g.p, d_T, reduce_max, partial,

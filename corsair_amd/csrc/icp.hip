@@ -1,0 +1,706 @@
+// Batched point-to-point ICP.  The specification is the comment of cs_icp_batch in include/corsair_hip.h;
+// tests/icp_ref.py restates it bit for bit.
+//
+// One call = one target preparation + (max_iter + 1) rounds, all enqueued without a host wait:
+//   k_icp_frame    per problem: the bounding box of its target segment (exact min / max), the origin and the
+//                  power-of-two scales of its fixed-point sums
+//   chamfer_pack16 the f16 hi / lo image, |S t|^2 and the float4 rows of every target, once per call
+//   round r:       k_icp_f16 (+ k_icp_exact for the workgroups it flags) or k_icp_exact alone -- association of the posed
+//                  ORIGINAL sources under the current T, 17 order-free 64-bit integer sums per problem;
+//                  k_icp_step -- one lane per problem: fitness / rmse of that association, the stop rule, Horn's fit
+//                  from the sums, T <- U T.
+// A problem that has stopped raises its device flag; its workgroups leave on it in every later round.
+#include <math.h>
+
+#include <algorithm>
+
+#include "horn.h"
+#include "nn_common.h"
+
+namespace cs {
+namespace {
+
+constexpr int ICP_ST = 4 * 32 * CHF_NG;   // sources per workgroup (both association kernels)
+constexpr int ICP_TT = 512;               // target rows per LDS stage of the exact kernel
+constexpr int ICP_NSUM = 17;              // count, sum p' (3), sum q' (3), sum p' q'^T (9), sum d^2
+
+// Fixed-point sums.  A kept pair has |p - q|^2 < max_dist^2 and q inside the bounding box of the target segment, so
+// relative to the box's midpoint o every coordinate obeys |q'_c| <= h_c and |p'_c| <= h_c + max_dist, h = the box's
+// half-extent.  With M = max_c h_c + max_dist < 2^eM (eM from frexp, clamped to [ICP_EM_MIN, ICP_EM_MAX]) and
+// n_src <= 2^eN:
+//   linear terms    |p'_c|, |q'_c|          < 2^eM      scale 2^s1, s1 = 61 - eN - eM      -> each < 2^(61 - eN)
+//   quadratic terms |p'_a q'_b|, d^2        < 2^(2 eM)  scale 2^s2, s2 = 61 - eN - 2 eM    -> each < 2^(61 - eN)
+// and a sum of at most 2^eN of them stays below 2^61 in magnitude: a factor of two inside 2^62, which also covers the
+// rounding of p, of the subtraction of o and of the product (each relative 2^-53).  Every scaled term is clamped to
+// +-2^(61 - eN) before the conversion, so the bound holds for ANY input (a box that is not finite, an absurd max_dist):
+// those sums then carry no meaning, but they are defined and the same in every run.
+// eM in [-100, 400] and eN in [0, 31] keep both scales and their inverses normal f64 powers of two (s1 in [-370, 161],
+// s2 in [-770, 261]), so scaling is exact.
+constexpr int ICP_EM_MIN = -100;
+constexpr int ICP_EM_MAX = 400;
+constexpr int ICP_SUM_BITS = 61;
+
+struct IcpProb {
+  int64_t s0, t0;   // first source / target row (global)
+  int64_t c0;       // first entry of the problem in d_corr
+  int32_t sn, tn;
+};
+struct IcpWork {
+  int64_t s0;       // first source row of this workgroup (global)
+  int64_t c0;       // its first entry in d_corr
+  int32_t sn;       // source rows (<= ICP_ST)
+  int32_t prob;
+};
+struct IcpFrame {
+  double o[3];      // origin: midpoint of the target segment's bounding box
+  double sc1, sc2;  // 2^s1, 2^s2
+  double inv1, inv2;
+  double clamp;     // 2^(61 - eN)
+};
+struct IcpCriteria {
+  double thr2;      // max_dist * max_dist
+  double rel_fitness, rel_rmse;
+};
+
+__global__ __launch_bounds__(256) void k_icp_frame(const IcpProb* __restrict__ probs, const float* __restrict__ tgt,
+                                                   double max_dist, IcpFrame* __restrict__ frame) {
+  __shared__ float red[2][3][4];
+  const IcpProb pr = probs[blockIdx.x];
+  const int tid = threadIdx.x;
+  float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+  for (int64_t j = tid; j < pr.tn; j += 256) {
+    const float* t = tgt + (pr.t0 + j) * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      mn[c] = fminf(mn[c], t[c]);
+      mx[c] = fmaxf(mx[c], t[c]);
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+      mn[c] = fminf(mn[c], __shfl_xor(mn[c], off));
+      mx[c] = fmaxf(mx[c], __shfl_xor(mx[c], off));
+    }
+    if ((tid & 63) == 0) {
+      red[0][c][tid >> 6] = mn[c];
+      red[1][c][tid >> 6] = mx[c];
+    }
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  IcpFrame f;
+  double hmax = 0.0;
+  bool finite = pr.tn > 0;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const double lo = (double)fminf(fminf(red[0][c][0], red[0][c][1]), fminf(red[0][c][2], red[0][c][3]));
+    const double hi = (double)fmaxf(fmaxf(red[1][c][0], red[1][c][1]), fmaxf(red[1][c][2], red[1][c][3]));
+    f.o[c] = 0.5 * (lo + hi);
+    const double h = 0.5 * (hi - lo);
+    hmax = fmax(hmax, h);
+    finite = finite && isfinite(f.o[c]) && isfinite(h);
+  }
+  if (!finite) {
+    f.o[0] = f.o[1] = f.o[2] = 0.0;
+    hmax = 0.0;
+  }
+  const double M = hmax + max_dist;
+  int eM = 0;
+  (void)frexp(M, &eM);                       // M = m 2^eM, 0.5 <= m < 1: M < 2^eM
+  if (!isfinite(M)) eM = ICP_EM_MAX;
+  eM = min(max(eM, ICP_EM_MIN), ICP_EM_MAX);
+  const int eN = pr.sn <= 1 ? 0 : 32 - __clz(pr.sn - 1);   // n_src <= 2^eN
+  const int s1 = ICP_SUM_BITS - eN - eM, s2 = ICP_SUM_BITS - eN - 2 * eM;
+  f.sc1 = ldexp(1.0, s1);
+  f.inv1 = ldexp(1.0, -s1);
+  f.sc2 = ldexp(1.0, s2);
+  f.inv2 = ldexp(1.0, -s2);
+  f.clamp = ldexp(1.0, ICP_SUM_BITS - eN);
+  frame[blockIdx.x] = f;
+}
+
+__device__ __forceinline__ long long icp_fix(double v, double scale, double clamp) {
+  const double x = fmin(fmax(v * scale, -clamp), clamp);   // (NaN becomes -clamp: never reached by a kept pair)
+  return (long long)x;                                     // truncates toward zero
+}
+
+// The 17 sums of one workgroup: thread = one source (kept or not), wave shuffle, LDS across the four waves, then ONE
+// 64-bit integer atomic per sum.  Integer addition: the same total in any order.
+__device__ __forceinline__ void icp_block_sums(bool kept, double px, double py, double pz, float qx, float qy, float qz,
+                                               double d2, const IcpFrame& fr, unsigned long long* __restrict__ sums,
+                                               unsigned long long (*part)[ICP_NSUM]) {
+  const int tid = threadIdx.x;
+  long long v[ICP_NSUM];
+#pragma unroll
+  for (int k = 0; k < ICP_NSUM; ++k) v[k] = 0;
+  if (kept) {
+    const double p[3] = {px - fr.o[0], py - fr.o[1], pz - fr.o[2]};
+    const double q[3] = {(double)qx - fr.o[0], (double)qy - fr.o[1], (double)qz - fr.o[2]};
+    v[0] = 1;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      v[1 + c] = icp_fix(p[c], fr.sc1, fr.clamp);
+      v[4 + c] = icp_fix(q[c], fr.sc1, fr.clamp);
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+      for (int b = 0; b < 3; ++b) {
+        const double prod = p[a] * q[b];   // rounded product (no contraction)
+        v[7 + 3 * a + b] = icp_fix(prod, fr.sc2, fr.clamp);
+      }
+    v[16] = icp_fix(d2, fr.sc2, fr.clamp);
+  }
+#pragma unroll
+  for (int k = 0; k < ICP_NSUM; ++k) {
+    unsigned long long s = (unsigned long long)v[k];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) s += __shfl_down(s, off);
+    if ((tid & 63) == 0) part[tid >> 6][k] = s;
+  }
+  __syncthreads();
+  if (tid < ICP_NSUM) {
+    const unsigned long long s = (part[0][tid] + part[1][tid]) + (part[2][tid] + part[3][tid]);
+    if (s) atomicAdd(&sums[tid], s);
+  }
+}
+
+__device__ __forceinline__ void icp_pose(const double* __restrict__ Tp, const float* __restrict__ sp, double& px,
+                                         double& py, double& pz) {
+  const double x = sp[0], y = sp[1], z = sp[2];
+  px = fma(Tp[0], x, fma(Tp[1], y, fma(Tp[2], z, Tp[3])));
+  py = fma(Tp[4], x, fma(Tp[5], y, fma(Tp[6], z, Tp[7])));
+  pz = fma(Tp[8], x, fma(Tp[9], y, fma(Tp[10], z, Tp[11])));
+}
+
+// Exhaustive association, one source per thread: the canonical chain over every target row in ascending order with a
+// strict comparison, i.e. the minimum by (distance, row).  The whole path under CS_ICP_F16=0, and the recomputation of
+// the workgroups k_icp_f16 flags.
+__global__ __launch_bounds__(256) void k_icp_exact(const IcpWork* __restrict__ work, const IcpProb* __restrict__ probs,
+                                                   const float* __restrict__ src, const float* __restrict__ tgt,
+                                                   const double* __restrict__ T, const IcpFrame* __restrict__ frame,
+                                                   const int32_t* __restrict__ done, double thr2,
+                                                   unsigned long long* __restrict__ sums, int32_t* __restrict__ corr,
+                                                   const int32_t* __restrict__ only_flagged) {
+  __shared__ float t_lds[ICP_TT * 3];
+  __shared__ unsigned long long part[4][ICP_NSUM];
+  if (only_flagged && !only_flagged[blockIdx.x]) return;
+  const IcpWork wk = work[blockIdx.x];
+  if (done[wk.prob]) return;
+  const IcpProb pr = probs[wk.prob];
+  const int tid = threadIdx.x;
+  const bool active = tid < wk.sn;
+  double px = 0, py = 0, pz = 0;
+  if (active) icp_pose(T + (int64_t)wk.prob * 16, src + (wk.s0 + tid) * 3, px, py, pz);
+  double best = INFINITY;
+  int bidx = -1;
+  for (int tbase = 0; tbase < pr.tn; tbase += ICP_TT) {
+    const int tcount = min(ICP_TT, pr.tn - tbase);
+    __syncthreads();
+    for (int i = tid; i < tcount * 3; i += 256) t_lds[i] = tgt[(pr.t0 + tbase) * 3 + i];
+    __syncthreads();
+    if (!active) continue;
+    for (int j = 0; j < tcount; ++j) {
+      const double dx = px - (double)t_lds[3 * j + 0];
+      const double dy = py - (double)t_lds[3 * j + 1];
+      const double dz = pz - (double)t_lds[3 * j + 2];
+      const double d = fma(dz, dz, fma(dy, dy, dx * dx));
+      if (d < best) {
+        best = d;
+        bidx = tbase + j;
+      }
+    }
+  }
+  const bool kept = active && bidx >= 0 && best < thr2;
+  float qx = 0.f, qy = 0.f, qz = 0.f;
+  if (kept) {
+    const float* tp = tgt + (pr.t0 + bidx) * 3;
+    qx = tp[0];
+    qy = tp[1];
+    qz = tp[2];
+  }
+  if (corr && active) corr[wk.c0 + tid] = kept ? bidx : -1;
+  icp_block_sums(kept, px, py, pz, qx, qy, qz, best, frame[wk.prob], sums + (int64_t)wk.prob * ICP_NSUM, part);
+}
+
+// The association on the f16 matrix cores: k_chamfer_f16's ranking (same image, same operand layout, same error budget;
+// chamfer.hip and DESIGN 3 / 12) keeping (distance, row) of the evaluated rows and vouching STRICTLY: the result stands only
+// when it lies below the smallest unevaluated tile minimum minus the error budget, so a row that was not evaluated can
+// neither beat nor tie it.  A workgroup with a source that fails the test, or with coordinates outside the f16 range,
+// adds nothing and raises its flag; k_icp_exact recomputes it.
+__global__ __launch_bounds__(256) void k_icp_f16(const IcpWork* __restrict__ work, const IcpProb* __restrict__ probs,
+                                                 const float* __restrict__ src, const float4* __restrict__ t4f,
+                                                 const _Float16* __restrict__ img, const float* __restrict__ tn32,
+                                                 const double* __restrict__ T, const IcpFrame* __restrict__ frame,
+                                                 const int32_t* __restrict__ done, double thr2,
+                                                 unsigned long long* __restrict__ sums, int32_t* __restrict__ corr,
+                                                 int32_t* __restrict__ flag, unsigned long long* __restrict__ stats) {
+  __shared__ __attribute__((aligned(16))) _Float16 a_s[2][CHF_ROWS * CHF_PITCH];
+  __shared__ __attribute__((aligned(16))) float tn_s[2][CHF_ROWS];
+  __shared__ unsigned long long part[4][ICP_NSUM];
+  __shared__ float wmax[4];
+  __shared__ int wg_bad;
+  const IcpWork wk = work[blockIdx.x];
+  const int tid = threadIdx.x;
+  if (done[wk.prob]) {
+    if (tid == 0) flag[blockIdx.x] = 0;
+    return;
+  }
+  const IcpProb pr = probs[wk.prob];
+  const int tn = pr.tn;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int half = lane >> 5;
+  const int col = lane & 31;
+  const double* Tp = T + (int64_t)wk.prob * 16;
+  if (tid == 0) wg_bad = 0;
+  double px[CHF_NG], py[CHF_NG], pz[CHF_NG];
+  f16x8 bop[CHF_NG];
+  float b1[CHF_NG], b2[CHF_NG], b3[CHF_NG];
+  int t1[CHF_NG], t2[CHF_NG];
+  bool in_range = true;
+#pragma unroll
+  for (int g = 0; g < CHF_NG; ++g) {
+    const int sloc = wave * 32 * CHF_NG + 32 * g + col;
+    icp_pose(Tp, src + (wk.s0 + (sloc < wk.sn ? sloc : 0)) * 3, px[g], py[g], pz[g]);
+    const float pf[3] = {(float)px[g] * CHF_SCALE, (float)py[g] * CHF_SCALE, (float)pz[g] * CHF_SCALE};
+    _Float16 hi[3], lo[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      knf_split(-2.0f * pf[c], &hi[c], &lo[c]);
+      in_range = in_range && fabsf(pf[c]) < 60.0f * CHF_SCALE;   // (NaN fails too)
+    }
+    // B rows k: 0..2 = -2 ph (x th), 3..5 = -2 ph (x tl), 6..8 = -2 pl (x th), 9..15 = 0; this lane holds k = 8 half .. + 7
+    const _Float16 z0 = (_Float16)0.0f;
+    if (half == 0)
+      bop[g] = f16x8{hi[0], hi[1], hi[2], hi[0], hi[1], hi[2], lo[0], lo[1]};
+    else
+      bop[g] = f16x8{lo[2], z0, z0, z0, z0, z0, z0, z0};
+    b1[g] = b2[g] = b3[g] = INFINITY;
+    t1[g] = t2[g] = -1;
+  }
+  // register-staged double buffer of the 12-KiB image stages, as in k_chamfer_f16
+  const uint4* gimg = reinterpret_cast<const uint4*>(img + pr.t0 * CHF_PITCH);
+  constexpr int U4_PER_STAGE = CHF_ROWS * CHF_PITCH * 2 / 16;
+  static_assert(U4_PER_STAGE == 3 * 256, "three 16-byte pieces per thread");
+  uint4 st0, st1, st2;
+  float stn;
+  float tmax2 = 0.0f;
+  auto load_stage = [&](int base) {
+    const uint4* g = gimg + (int64_t)base * (CHF_PITCH * 2 / 16) + tid;
+    st0 = g[0];
+    st1 = g[256];
+    st2 = g[512];
+    const int r = base + tid;
+    stn = r < tn ? tn32[pr.t0 + r] : INFINITY;   // rows past the segment (another problem's rows) never win
+    if (r < tn) tmax2 = fmaxf(tmax2, stn);
+  };
+  auto store_stage = [&](int b) {
+    uint4* d = reinterpret_cast<uint4*>(a_s[b]) + tid;
+    d[0] = st0;
+    d[256] = st1;
+    d[512] = st2;
+    tn_s[b][tid] = stn;
+  };
+  if (tn > 0) {
+    load_stage(0);
+    store_stage(0);
+  }
+  int buf = 0;
+  for (int base = 0; base < tn; base += CHF_ROWS) {
+    __syncthreads();
+    const bool more = base + CHF_ROWS < tn;
+    if (more) load_stage(base + CHF_ROWS);
+#pragma unroll 1
+    for (int t = 0; t < CHF_ROWS / 32; ++t) {
+      if (base + 32 * t >= tn) break;   // whole tile past the range (block-uniform)
+      const f16x8 a = *reinterpret_cast<const f16x8*>(a_s[buf] + (t * 32 + col) * CHF_PITCH + 8 * half);
+      f32x16 c16;
+#pragma unroll
+      for (int q4 = 0; q4 < 4; ++q4) {
+        const float4 v = *reinterpret_cast<const float4*>(&tn_s[buf][t * 32 + 8 * q4 + 4 * half]);
+        c16[4 * q4 + 0] = v.x; c16[4 * q4 + 1] = v.y; c16[4 * q4 + 2] = v.z; c16[4 * q4 + 3] = v.w;
+      }
+      const int tile = base / 32 + t;
+#pragma unroll
+      for (int g = 0; g < CHF_NG; ++g) {
+        const f32x16 d = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, bop[g], c16, 0, 0, 0);
+        float m = fminf(fminf(d[0], d[1]), d[2]);
+        m = fminf(fminf(m, d[3]), d[4]);
+        m = fminf(fminf(m, d[5]), d[6]);
+        m = fminf(fminf(m, d[7]), d[8]);
+        m = fminf(fminf(m, d[9]), d[10]);
+        m = fminf(fminf(m, d[11]), d[12]);
+        m = fminf(fminf(m, d[13]), d[14]);
+        m = fminf(m, d[15]);
+        const float o1 = b1[g], o2 = b2[g];
+        const bool lt1 = m < o1, lt2 = m < o2;
+        b1[g] = fminf(o1, m);
+        b2[g] = __builtin_amdgcn_fmed3f(o1, o2, m);
+        b3[g] = __builtin_amdgcn_fmed3f(o2, b3[g], m);
+        t2[g] = lt1 ? t1[g] : (lt2 ? tile : t2[g]);
+        t1[g] = lt1 ? tile : t1[g];
+      }
+    }
+    if (more) store_stage(buf ^ 1);
+    buf ^= 1;
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) tmax2 = fmaxf(tmax2, __shfl_xor(tmax2, off));
+  if (lane == 0) wmax[wave] = tmax2;
+  __syncthreads();
+  const double tmax = sqrt((double)fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]))) / (double)CHF_SCALE;
+  bool bad = !in_range || !(tmax < 60.0);
+  const float4* trow = t4f + pr.t0;
+  // canonical distances of this lane's 16 rows of a tile, ascending rows, strict <: the smallest by (distance, row)
+  auto eval_tile = [&](int g, int tile, double& e, int& er) {
+    e = INFINITY;
+    er = 0x7fffffff;
+    if (tile >= 0) {
+      float4 v[16];
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const int row = tile * 32 + 4 * half + (i & 3) + 8 * (i >> 2);
+        v[i] = trow[row < tn ? row : 0];
+      }
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const int row = tile * 32 + 4 * half + (i & 3) + 8 * (i >> 2);
+        const double dx = px[g] - (double)v[i].x, dy = py[g] - (double)v[i].y, dz = pz[g] - (double)v[i].z;
+        const double d = fma(dz, dz, fma(dy, dy, dx * dx));
+        if (row < tn && d < e) {
+          e = d;
+          er = row;
+        }
+      }
+    }
+  };
+  // (distance, row) minimum of the two lanes of a source
+  auto pair_min = [&](double& e, int& er) {
+    const double oe = __shfl_xor(e, 32);
+    const int orow = __shfl_xor(er, 32);
+    if (oe < e || (oe == e && orow < er)) {
+      e = oe;
+      er = orow;
+    }
+  };
+  double my_e = INFINITY;
+  int my_row = 0x7fffffff;
+#pragma unroll
+  for (int g = 0; g < CHF_NG; ++g) {
+    // error budget: the derivation in k_chamfer_f16 (the ranking value and its operands are the same)
+    const double pn2 = fma(pz[g], pz[g], fma(py[g], py[g], px[g] * px[g]));
+    const double S = (double)CHF_SCALE, PT = S * (sqrt(pn2) + tmax);
+    const double eps = 0x1.0p-19 * PT * PT + 0x1.0p-10 * PT;
+    double e;
+    int er;
+    eval_tile(g, t1[g], e, er);
+    pair_min(e, er);
+    float rest = fminf(b2[g], __shfl_xor(b2[g], 32));     // smallest unevaluated tile minimum of the source
+    bool ok = rest == INFINITY || (e - pn2) * S * S < (double)rest - eps;
+    if (__any(!ok)) {
+      double e2 = INFINITY;
+      int er2 = 0x7fffffff;
+      if (!ok) eval_tile(g, t2[g], e2, er2);
+      pair_min(e2, er2);
+      if (!ok) {
+        if (e2 < e || (e2 == e && er2 < er)) {
+          e = e2;
+          er = er2;
+        }
+        rest = fminf(b3[g], __shfl_xor(b3[g], 32));
+        ok = rest == INFINITY || (e - pn2) * S * S < (double)rest - eps;
+      }
+    }
+    const int sloc = wave * 32 * CHF_NG + 32 * g + col;
+    if (sloc < wk.sn && !ok) bad = true;
+    if (g == half) {       // both lanes of a source hold its result: lane `half` carries the source of group `half`
+      my_e = e;
+      my_row = er;
+    }
+  }
+  static_assert(CHF_NG == 2, "one source per thread in the sums: group g is carried by the lanes of half g");
+  if (__any(bad) && lane == 0) atomicOr(&wg_bad, 1);
+  __syncthreads();
+  const int wbad = wg_bad;
+  if (tid == 0) {
+    flag[blockIdx.x] = wbad;
+    if (stats) {
+      atomicAdd(&stats[0], 1ULL);
+      if (wbad) atomicAdd(&stats[1], 1ULL);
+    }
+  }
+  if (wbad) return;   // block-uniform
+  const double mpx = half ? px[1] : px[0], mpy = half ? py[1] : py[0], mpz = half ? pz[1] : pz[0];
+  const bool active = tid < wk.sn;   // sloc of (wave, g = half, col) = tid
+  const bool kept = active && my_row != 0x7fffffff && my_e < thr2;
+  float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (kept) q = trow[my_row];
+  if (corr && active) corr[wk.c0 + tid] = kept ? my_row : -1;
+  icp_block_sums(kept, mpx, mpy, mpz, q.x, q.y, q.z, my_e, frame[wk.prob], sums + (int64_t)wk.prob * ICP_NSUM, part);
+}
+
+__device__ __forceinline__ bool icp_all_finite(const double* v, int n) {
+  bool f = true;
+  for (int i = 0; i < n; ++i) f = f && isfinite(v[i]);
+  return f;
+}
+
+// One lane per problem: the evaluation of the association just made, the stop rule, the update.  last = the round after
+// the max_iter-th update (or the only one when max_iter = 0): nothing is fitted, the f32 copy of T is written.
+__global__ void k_icp_step(const IcpProb* __restrict__ probs, int n_prob, const IcpFrame* __restrict__ frame,
+                           IcpCriteria crit, int round, int last, unsigned long long* __restrict__ sums,
+                           int32_t* __restrict__ done, double* __restrict__ T, float* __restrict__ T32,
+                           double* __restrict__ fitness, double* __restrict__ rmse, int32_t* __restrict__ iters,
+                           int32_t* __restrict__ ncorr) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n_prob) return;
+  double* Tp = T + (int64_t)p * 16;
+  if (!done[p]) {
+    const IcpProb pr = probs[p];
+    const IcpFrame fr = frame[p];
+    unsigned long long* S = sums + (int64_t)p * ICP_NSUM;
+    const long long n = (long long)S[0];
+    const double dn = (double)n;
+    const double fit = pr.sn > 0 ? dn / (double)pr.sn : 0.0;
+    const double sd2 = (double)(long long)S[16] * fr.inv2;
+    const double rm = n > 0 ? sqrt(sd2 / dn) : 0.0;
+    const double pfit = fitness[p], prm = rmse[p];
+    fitness[p] = fit;
+    rmse[p] = rm;
+    ncorr[p] = (int32_t)n;
+    bool stop = last != 0;
+    if (round > 0 && fabs(fit - pfit) < crit.rel_fitness && fabs(rm - prm) < crit.rel_rmse) stop = true;
+    if (n < 3 || !isfinite(fit) || !isfinite(rm)) stop = true;
+    if (!stop) {
+      double sp[3], sq[3], mp[3], mq[3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        sp[c] = (double)(long long)S[1 + c] * fr.inv1;
+        sq[c] = (double)(long long)S[4 + c] * fr.inv1;
+        mp[c] = sp[c] / dn;
+        mq[c] = sq[c] / dn;
+      }
+      // cross-covariance about the means, source index first (the RANSAC's S): sum p'_a q'_b - (sum p'_a) mean q'_b
+      double Sm[3][3], N[4][4], V[4][4];
+#pragma unroll
+      for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) Sm[a][b] = fma(-sp[a], mq[b], (double)(long long)S[7 + 3 * a + b] * fr.inv2);
+      N[0][0] = Sm[0][0] + Sm[1][1] + Sm[2][2];
+      N[0][1] = Sm[1][2] - Sm[2][1];
+      N[0][2] = Sm[2][0] - Sm[0][2];
+      N[0][3] = Sm[0][1] - Sm[1][0];
+      N[1][1] = Sm[0][0] - Sm[1][1] - Sm[2][2];
+      N[1][2] = Sm[0][1] + Sm[1][0];
+      N[1][3] = Sm[2][0] + Sm[0][2];
+      N[2][2] = -Sm[0][0] + Sm[1][1] - Sm[2][2];
+      N[2][3] = Sm[1][2] + Sm[2][1];
+      N[3][3] = -Sm[0][0] - Sm[1][1] + Sm[2][2];
+      N[1][0] = N[0][1];
+      N[2][0] = N[0][2];
+      N[3][0] = N[0][3];
+      N[2][1] = N[1][2];
+      N[3][1] = N[1][3];
+      N[3][2] = N[2][3];
+      double qv[4];
+      if (!horn_qcp(Sm, N, qv)) {
+        jacobi4(N, V);
+        // eigenvector of the largest eigenvalue (ties -> lowest index), as the RANSAC selects it
+        double best = N[0][0];
+        qv[0] = V[0][0]; qv[1] = V[1][0]; qv[2] = V[2][0]; qv[3] = V[3][0];
+#pragma unroll
+        for (int c = 1; c < 4; ++c) {
+          if (N[c][c] > best) {
+            best = N[c][c];
+            qv[0] = V[0][c];
+            qv[1] = V[1][c];
+            qv[2] = V[2][c];
+            qv[3] = V[3][c];
+          }
+        }
+      }
+      double qw = qv[0], qx = qv[1], qy = qv[2], qz = qv[3];
+      const double qn = sqrt(qw * qw + qx * qx + qy * qy + qz * qz);
+      qw = qw / qn;
+      qx = qx / qn;
+      qy = qy / qn;
+      qz = qz / qn;
+      double R[3][3];
+      R[0][0] = 1.0 - 2.0 * (qy * qy + qz * qz);
+      R[0][1] = 2.0 * (qx * qy - qw * qz);
+      R[0][2] = 2.0 * (qx * qz + qw * qy);
+      R[1][0] = 2.0 * (qx * qy + qw * qz);
+      R[1][1] = 1.0 - 2.0 * (qx * qx + qz * qz);
+      R[1][2] = 2.0 * (qy * qz - qw * qx);
+      R[2][0] = 2.0 * (qx * qz - qw * qy);
+      R[2][1] = 2.0 * (qy * qz + qw * qx);
+      R[2][2] = 1.0 - 2.0 * (qx * qx + qy * qy);
+      // t = q_mean - R p_mean on the unprimed means; T <- U T
+      double pm[3], qm[3], Tn[12];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        pm[c] = mp[c] + fr.o[c];
+        qm[c] = mq[c] + fr.o[c];
+      }
+#pragma unroll
+      for (int a = 0; a < 3; ++a) {
+        const double t = qm[a] - fma(R[a][2], pm[2], fma(R[a][1], pm[1], R[a][0] * pm[0]));
+#pragma unroll
+        for (int b = 0; b < 3; ++b)
+          Tn[4 * a + b] = fma(R[a][0], Tp[b], fma(R[a][1], Tp[4 + b], R[a][2] * Tp[8 + b]));
+        Tn[4 * a + 3] = fma(R[a][0], Tp[3], fma(R[a][1], Tp[7], fma(R[a][2], Tp[11], t)));
+      }
+      if (icp_all_finite(Tn, 12)) {
+#pragma unroll
+        for (int i = 0; i < 12; ++i) Tp[i] = Tn[i];
+        iters[p] = iters[p] + 1;
+#pragma unroll
+        for (int k = 0; k < ICP_NSUM; ++k) S[k] = 0;
+      } else {
+        stop = true;
+      }
+    }
+    if (stop) done[p] = 1;
+  }
+  if (last && T32) {
+    for (int i = 0; i < 16; ++i) T32[(int64_t)p * 16 + i] = (float)Tp[i];
+  }
+}
+
+__global__ void k_icp_init(const float* __restrict__ T0, int n_prob, double* __restrict__ T, double* __restrict__ fitness,
+                           double* __restrict__ rmse, int32_t* __restrict__ iters, int32_t* __restrict__ ncorr,
+                           int32_t* __restrict__ done) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n_prob) return;
+  for (int i = 0; i < 16; ++i) T[(int64_t)p * 16 + i] = (double)T0[(int64_t)p * 16 + i];
+  fitness[p] = 0.0;
+  rmse[p] = 0.0;
+  iters[p] = 0;
+  ncorr[p] = 0;
+  done[p] = 0;
+}
+
+std::atomic<unsigned long long> g_icp_stats[2];
+
+}  // namespace
+}  // namespace cs
+
+using namespace cs;
+
+extern "C" {
+
+void cs_icp_stats(uint64_t out[2], int reset) { read_stats(g_icp_stats, out, reset); }
+
+int cs_icp_batch(const float* d_src, const int64_t* h_soff, const float* d_tgt, const int64_t* h_toff,
+                 const int32_t* h_src_seg, const int32_t* h_tgt_seg, int n_prob, const float* d_T0, double max_dist,
+                 int max_iter, double relative_fitness, double relative_rmse, double* d_T, float* d_T32,
+                 double* d_fitness, double* d_rmse, int32_t* d_iters, int32_t* d_ncorr, int32_t* d_corr, void* stream) {
+  CS_REQUIRE(h_soff && h_toff && h_src_seg && h_tgt_seg, CS_ERR_INVALID, "cs_icp_batch: NULL table");
+  CS_REQUIRE(n_prob >= 0, CS_ERR_INVALID, "cs_icp_batch: negative problem count");
+  CS_REQUIRE(max_dist > 0.0 && std::isfinite(max_dist), CS_ERR_INVALID, "cs_icp_batch: max_dist must be positive and finite");
+  CS_REQUIRE(max_iter >= 0 && max_iter <= 1000, CS_ERR_UNSUPPORTED, "cs_icp_batch: max_iter outside [0, 1000]");
+  CS_REQUIRE(!std::isnan(relative_fitness) && !std::isnan(relative_rmse), CS_ERR_INVALID,
+             "cs_icp_batch: a convergence threshold is NaN");
+  if (n_prob == 0) return CS_OK;
+  CS_REQUIRE(d_T0 && d_T && d_fitness && d_rmse && d_iters && d_ncorr, CS_ERR_INVALID, "cs_icp_batch: NULL argument");
+  std::vector<IcpProb> probs(n_prob);
+  std::vector<IcpWork> work;
+  int64_t nt_rows = 0, n_corr_rows = 0;
+  double flop = 0.0;
+  for (int p = 0; p < n_prob; ++p) {
+    const int ss = h_src_seg[p], ts = h_tgt_seg[p];
+    CS_REQUIRE(ss >= 0 && ts >= 0, CS_ERR_INVALID, "cs_icp_batch: negative segment id in problem %d", p);
+    const int64_t sn = h_soff[ss + 1] - h_soff[ss], tn = h_toff[ts + 1] - h_toff[ts];
+    CS_REQUIRE(sn >= 0 && tn >= 0, CS_ERR_INVALID, "cs_icp_batch: bad segment in problem %d", p);
+    CS_REQUIRE(sn < (1LL << 31) && tn < (1LL << 31), CS_ERR_UNSUPPORTED,
+               "cs_icp_batch: a segment of problem %d has 2^31 rows or more", p);
+    IcpProb& pr = probs[p];
+    pr.s0 = h_soff[ss];
+    pr.t0 = h_toff[ts];
+    pr.c0 = n_corr_rows;
+    pr.sn = (int32_t)sn;
+    pr.tn = (int32_t)tn;
+    if (tn > 0) nt_rows = std::max<int64_t>(nt_rows, h_toff[ts + 1]);
+    for (int64_t q = 0; q < sn; q += ICP_ST) {
+      IcpWork w;
+      w.s0 = pr.s0 + q;
+      w.c0 = pr.c0 + q;
+      w.sn = (int32_t)std::min<int64_t>(sn - q, ICP_ST);
+      w.prob = p;
+      work.push_back(w);
+    }
+    n_corr_rows += sn;
+    flop += 8.0 * (double)sn * (double)tn;
+  }
+  CS_REQUIRE(work.empty() || d_src, CS_ERR_INVALID, "cs_icp_batch: NULL source array");
+  CS_REQUIRE(nt_rows == 0 || d_tgt, CS_ERR_INVALID, "cs_icp_batch: NULL target array");
+  hipStream_t s = (hipStream_t)stream;
+  pool_use_stream(s);
+  const bool use_f16 = !env_first_is("CS_ICP_F16", '0');
+  const bool want_stats = use_f16 && env_first_is("CS_ICP_STATS", '1');
+  const unsigned n_work = (unsigned)work.size();
+  PoolBuf<IcpProb> dprob;
+  PoolBuf<IcpWork> dwork;
+  PoolBuf<IcpFrame> frame((size_t)n_prob);
+  PoolBuf<unsigned long long> sums((size_t)n_prob * ICP_NSUM + 2);   // + the two statistics counters
+  PoolBuf<int32_t> done((size_t)n_prob);
+  CS_REQUIRE(frame.p && sums.p && done.p, CS_ERR_HIP, "cs_icp_batch: scratch allocation failed");
+  int rc = upload(dprob, probs, s);
+  if (!rc) rc = upload(dwork, work, s);
+  if (rc) return rc;
+  unsigned long long* dstats = sums.p + (size_t)n_prob * ICP_NSUM;
+  ProfScope prof("icp", s, flop * (double)(max_iter + 1));
+  CS_HIP_CHECK(hipMemsetAsync(sums.p, 0, sizeof(unsigned long long) * ((size_t)n_prob * ICP_NSUM + 2), s));
+  const dim3 pgrid((unsigned)ceil_div(n_prob, 64));
+  hipLaunchKernelGGL(k_icp_init, pgrid, dim3(64), 0, s, d_T0, n_prob, d_T, d_fitness, d_rmse, d_iters, d_ncorr, done.p);
+  hipLaunchKernelGGL(k_icp_frame, dim3((unsigned)n_prob), dim3(256), 0, s, dprob.p, d_tgt, max_dist, frame.p);
+  // the targets do not move: one image for every round
+  PoolBuf<_Float16> img16;
+  PoolBuf<float> tn16;
+  PoolBuf<float4> t4f;
+  PoolBuf<int32_t> wflag;
+  if (use_f16 && n_work) {
+    const int64_t n_pad = nt_rows + CHF_ROWS;   // the last stage of the last segment reads past its end
+    img16.alloc((size_t)n_pad * CHF_PITCH);
+    tn16.alloc((size_t)n_pad);
+    t4f.alloc((size_t)(nt_rows ? nt_rows : 1));
+    wflag.alloc(n_work);
+    CS_REQUIRE(img16.p && tn16.p && t4f.p && wflag.p, CS_ERR_HIP, "cs_icp_batch: scratch allocation failed");
+    chamfer_pack16(d_tgt, nt_rows, n_pad, img16.p, tn16.p, t4f.p, s);
+  }
+  CS_LAUNCH_CHECK();
+  IcpCriteria crit;
+  crit.thr2 = max_dist * max_dist;
+  crit.rel_fitness = relative_fitness;
+  crit.rel_rmse = relative_rmse;
+  for (int round = 0; round <= max_iter; ++round) {
+    if (n_work) {
+      if (use_f16) {
+        hipLaunchKernelGGL(k_icp_f16, dim3(n_work), dim3(256), 0, s, dwork.p, dprob.p, d_src, t4f.p, img16.p, tn16.p,
+                           (const double*)d_T, frame.p, done.p, crit.thr2, sums.p, d_corr, wflag.p,
+                           want_stats ? dstats : (unsigned long long*)nullptr);
+        hipLaunchKernelGGL(k_icp_exact, dim3(n_work), dim3(256), 0, s, dwork.p, dprob.p, d_src, d_tgt, (const double*)d_T,
+                           frame.p, done.p, crit.thr2, sums.p, d_corr, (const int32_t*)wflag.p);
+      } else {
+        hipLaunchKernelGGL(k_icp_exact, dim3(n_work), dim3(256), 0, s, dwork.p, dprob.p, d_src, d_tgt, (const double*)d_T,
+                           frame.p, done.p, crit.thr2, sums.p, d_corr, (const int32_t*)nullptr);
+      }
+    }
+    hipLaunchKernelGGL(k_icp_step, pgrid, dim3(64), 0, s, dprob.p, n_prob, frame.p, crit, round, round == max_iter ? 1 : 0,
+                       sums.p, done.p, d_T, d_T32, d_fitness, d_rmse, d_iters, d_ncorr);
+  }
+  CS_LAUNCH_CHECK();
+  if (want_stats) {
+    unsigned long long h[2] = {0, 0};
+    CS_HIP_CHECK(download_async(h, dstats, sizeof(h), s));
+    CS_HIP_CHECK(download_sync(s));
+    g_icp_stats[0] += h[0];
+    g_icp_stats[1] += h[1];
+  }
+  return CS_OK;
+}
+
+}  // extern "C"

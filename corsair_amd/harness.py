@@ -39,6 +39,14 @@ class Config:
     embed_batch_size: int = 128
     ransac_max_iter: int = 100000
     ransac_confidence: float = 0.999
+    # point-to-point ICP refinement of the kept pose (registration.sym_pose_batch, cs_icp_batch): updates at most; 0 = off,
+    # the reference's behaviour.  icp_max_dist = 0.0 means 2 * voxel_size -- a plausible radius for voxel centres one cell
+    # apart that NOBODY HAS TUNED; set it explicitly for real data
+    icp_max_iter: int = 0
+    icp_max_dist: float = 0.0
+
+    def icp_distance(self):
+        return self.icp_max_dist if self.icp_max_dist > 0 else 2.0 * self.voxel_size
 
 
 @dataclass
@@ -156,7 +164,7 @@ class Pipeline:
         return R.sym_pose_batch(queries.F, queries.origin, queries.offsets, cads.F, cads.origin,
                                 cads.offsets, syms, c.k_nn, c.max_corr, 0, anchor_ids, 100,
                                 c.ransac_max_iter, c.ransac_confidence, use_symmetry, force_gate,
-                                query_anchors)
+                                query_anchors, c.icp_max_iter, c.icp_distance() if c.icp_max_iter > 0 else None)
 
 
 def concat_sets(sets):
@@ -212,6 +220,7 @@ class EvalResult:
     sym_success_rate: float
     from_cache: bool
     report: str                     # the log block of evaluation.py:359-383
+    icp: dict = None                # aggregate() of the ICP-refined poses (+ iters_mean) when the refinement ran
 
 
 def _report(ransac, sym, rate):
@@ -228,6 +237,13 @@ def _report(ransac, sym, rate):
     return (block("vanilla ransac", ransac, "") +
             block("sym ransac", sym, "\n==================================================================\n") +
             f"\nsym success rate: {rate}")
+
+
+def _icp_report(a):
+    return (f"\nicp refinement:\ntranslation error: {a['rte_mean']},\n"
+            f"rte 0.02: {a['rte_002']}, rte 0.05: {a['rte_005']}, rte 0.10: {a['rte_010']}, rte 0.15: {a['rte_015']}\n"
+            f"rotation error: {a['rre_mean_rad']},\nrre 5: {a['rre_5']}, rre 15: {a['rre_15']}, rre 45: {a['rre_45']},\n"
+            f"chamfer distance: {a['chamfer_mean']}\nmean icp updates: {a['iters_mean']}")
 
 
 def run_eval(pipe, catalog, queries, best_match, table, base_T, lib_T, syms, category="chair",
@@ -257,7 +273,8 @@ def run_eval(pipe, catalog, queries, best_match, table, base_T, lib_T, syms, cat
     syms = np.asarray(syms)
     stat = retrieval_stat(pipe, qs.desc, cat.desc, best_match, table)
 
-    per_query = None if (ignore_cache or cache_dir is None) else C_.load_results(cache_dir, category, register_top1)
+    per_query = None if (ignore_cache or cache_dir is None) else \
+        C_.load_results(cache_dir, category, register_top1, icp=cfg.icp_max_iter > 0)
     from_cache = per_query is not None
     if per_query is None:
         pos_idx = np.asarray(stat["top1_predict" if register_top1 else "gt"], dtype=np.int64)
@@ -306,7 +323,8 @@ def register_queries(pipe, qs, query_ids, cat, pos_idx, syms, base_T, lib_T, for
     """The registration loop of evaluation.py:297-331 over the embedded queries `qs`, whose GLOBAL query numbers are
     `query_ids` (they seed the anchor draws, so a query gives the same result whichever rank or batch it lands in):
     sym_pose against CAD pos_idx[q] and eval_pose of both estimates, batched.  Returns the nine arrays of
-    evaluation.py:421-441 (cache.NAMES) for these queries, in the order of `query_ids`.
+    evaluation.py:421-441 (cache.NAMES) for these queries, in the order of `query_ids`; with ICP refinement on
+    (pipe.cfg.icp_max_iter > 0) also the arrays of cache.ICP_NAMES.
     in_flight > 1: that many batches at a time, each on its own host thread and HIP stream (batches are independent;
     the library's scratch cache is per thread and stream-ordered) -- same results, the host work of one batch hides
     behind the kernels of the others (bench.py's `batches_in_flight`)."""
@@ -314,8 +332,11 @@ def register_queries(pipe, qs, query_ids, cat, pos_idx, syms, base_T, lib_T, for
 
     bs = batch_size or pipe.cfg.batch_size
     query_ids = np.asarray(query_ids, dtype=np.int64)
+    icp_on = getattr(pipe.cfg, "icp_max_iter", 0) > 0
+    names = C_.NAMES + (C_.ICP_NAMES if icp_on else ())
+    dtypes = dict(C_.DTYPES, **C_.ICP_DTYPES)
     if not len(query_ids):
-        return {k: np.zeros((0, 4, 4) if k.startswith("Ts_est") else 0, C_.DTYPES[k]) for k in C_.NAMES}
+        return {k: np.zeros((0, 4, 4) if k.startswith("Ts_est") else 0, dtypes[k]) for k in names}
     batches = [np.arange(s, min(len(query_ids), s + bs)) for s in range(0, len(query_ids), bs)]
 
     def one(loc):
@@ -330,9 +351,15 @@ def register_queries(pipe, qs, query_ids, cat, pos_idx, syms, base_T, lib_T, for
         T1 = [lib_T[j] for j in pos_idx[ids]]
         t_r, r_r = pose_losses(Tr, T0, T1, cad_sym)
         t_s, r_s = pose_losses(Tb, T0, T1, cad_sym)
-        return {"Ts_est_ransac": Tr, "Ts_est_best": Tb, "t_losses_ransac": t_r, "t_losses_sym": t_s,
-                "r_losses_ransac": r_r, "r_losses_sym": r_s, "sym_ransac_success": np.asarray(res.ok),
-                "chamfer_dist_ransac": cdr, "chamfer_dist_sym": cdb}
+        out = {"Ts_est_ransac": Tr, "Ts_est_best": Tb, "t_losses_ransac": t_r, "t_losses_sym": t_s,
+               "r_losses_ransac": r_r, "r_losses_sym": r_s, "sym_ransac_success": np.asarray(res.ok),
+               "chamfer_dist_ransac": cdr, "chamfer_dist_sym": cdb}
+        if icp_on:
+            Ti, cdi, iti = (t.cpu().numpy() for t in (res.T_icp, res.cd_icp, res.icp_iters))
+            t_i, r_i = pose_losses(Ti, T0, T1, cad_sym)
+            extra = {"Ts_est_icp": Ti, "t_losses_icp": t_i, "r_losses_icp": r_i, "chamfer_dist_icp": cdi, "icp_iters": iti}
+            out.update({k: np.asarray(v, dtypes[k]) for k, v in extra.items()})
+        return out
 
     depth = min(int(in_flight), len(batches))
     on_gpu = torch.device(getattr(pipe, "device", "cpu")).type == "cuda"
@@ -361,7 +388,7 @@ def register_queries(pipe, qs, query_ids, cat, pos_idx, syms, base_T, lib_T, for
         else:
             for f in [_worker(w).submit(work, w) for w in range(depth)]:
                 f.result()               # surfaces worker failures
-    return {k: np.concatenate([np.asarray(d[k]) for d in done]) for k in C_.NAMES}
+    return {k: np.concatenate([np.asarray(d[k]) for d in done]) for k in names}
 
 
 def finish_eval(stat, per_query, from_cache):
@@ -371,7 +398,14 @@ def finish_eval(stat, per_query, from_cache):
     for a, r in ((ransac, per_query["r_losses_ransac"]), (sym, per_query["r_losses_sym"])):
         a["rre_mean_rad"] = float(np.mean(np.asarray(r, np.float64)))
     rate = float(np.mean(per_query["sym_ransac_success"]))
-    return EvalResult(stat, per_query, ransac, sym, rate, from_cache, _report(ransac, sym, rate))
+    res = EvalResult(stat, per_query, ransac, sym, rate, from_cache, _report(ransac, sym, rate))
+    if "r_losses_icp" in per_query:
+        icp = aggregate(per_query["r_losses_icp"], per_query["t_losses_icp"], per_query["chamfer_dist_icp"])
+        icp["rre_mean_rad"] = float(np.mean(np.asarray(per_query["r_losses_icp"], np.float64)))
+        icp["iters_mean"] = float(np.mean(per_query["icp_iters"]))
+        res.icp = icp
+        res.report += _icp_report(icp)
+    return res
 
 
 # ---- synthetic Scan2CAD-shaped workload ---------------------------------------------------------------
@@ -486,6 +520,10 @@ def build_parser():
     ap.add_argument("--embed-batch-size", type=int, default=128,
                     help="clouds per forward of the network (the reference's DataLoader: 32; the rows do not depend on it)")
     ap.add_argument("--ransac-max-iter", type=int, default=100000)
+    ap.add_argument("--icp-iters", type=int, default=0,
+                    help="refine every kept pose with at most N point-to-point ICP updates (0 = off, the reference's behaviour)")
+    ap.add_argument("--icp-max-dist", type=float, default=0.0,
+                    help="ICP correspondence distance; 0 = 2 * voxel size (an untuned default)")
     ap.add_argument("--in-flight", type=int, default=3, help="registration batches in flight (host threads x HIP streams)")
     ap.add_argument("--device", default="cuda", choices=["cuda"], help="there is no CPU path")
     return ap
@@ -506,7 +544,7 @@ def main(argv=None):
     if esd is None:
         raise SystemExit("checkpoint has no embedding_state_dict: retrieval needs the descriptor head (evaluation.py:199)")
     cfg = Config(n_points=a.n_points, batch_size=a.batch_size, embed_batch_size=a.embed_batch_size,
-                 ransac_max_iter=a.ransac_max_iter)
+                 ransac_max_iter=a.ransac_max_iter, icp_max_iter=a.icp_iters, icp_max_dist=a.icp_max_dist)
     pipe = Pipeline(sd, esd, device=a.device, config=cfg)
     cad_names, catalog = load_cloud_dir(a.catalog_dir, a.n_points, "catalog")
     _, queries = load_cloud_dir(a.query_dir, a.n_points, "queries")

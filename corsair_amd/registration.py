@@ -54,6 +54,12 @@ class SymPoseResult:
     prob_pair: list = None          # pair of problem j
     prob_cfg: list = None           # part assignment of problem j (None = vanilla)
     best: np.ndarray = None         # int64 [P] problem kept per pair (first strict Chamfer minimum)
+    # ICP refinement of T_best (sym_pose_batch(icp_max_iter > 0)); None when it is off
+    T_icp: torch.Tensor = None      # f32 [P,4,4]
+    cd_icp: torch.Tensor = None     # f64 [P] one-directional Chamfer under T_icp (cs_chamfer_1dir)
+    icp_fitness: torch.Tensor = None    # f64 [P]
+    icp_rmse: torch.Tensor = None       # f64 [P]
+    icp_iters: torch.Tensor = None      # int32 [P] updates applied
 
     def hypotheses(self, p):
         """Problems of pair p in evaluation order."""
@@ -144,13 +150,18 @@ def part_configs(K, pos_sym):
 
 def sym_pose_batch(baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_nn=5, max_corr=0.20, seed=0,
                    anchor_ids=None, n_anchor=100, max_iter=100000, confidence=0.999,
-                   use_symmetry=True, force_gate=False, query_anchors=None):
+                   use_symmetry=True, force_gate=False, query_anchors=None, icp_max_iter=0, icp_max_dist=None):
     """baseF f32 [N0,16], xyz0 f32 [N0,3] (query voxels of all pairs, segment p = off0[p]:off0[p+1]);
     posF/xyz1/off1 likewise for the CAD side; pos_syms: symmetry label per pair.
     anchor_ids[p] = (counter0, counter1) seeds the anchor draw of pair p (default (2p, 2p+1)).
     query_anchors: the query-side draws (draw_anchors(n0[p], n_anchor, anchor_ids[p][0]) for every p)
     when the caller has already made them -- e.g. while the embedding kernels were still running; the
-    ~1 ms of host work would otherwise sit between the 5-NN and the part-cut launches."""
+    ~1 ms of host work would otherwise sit between the 5-NN and the part-cut launches.
+    icp_max_iter > 0: T_best of every pair is refined by point-to-point ICP (cs_icp_batch: source = the query's voxels,
+    target = the CAD's voxels, the direction of stage 5; correspondence distance icp_max_dist, required then) and the
+    result's T_icp / cd_icp / icp_* fields are filled; with the default 0 nothing is launched."""
+    if icp_max_iter > 0 and not (icp_max_dist is not None and icp_max_dist > 0):
+        raise ValueError("sym_pose_batch: icp_max_iter > 0 needs a positive icp_max_dist")
     dev = baseF.device
     P = len(off0) - 1
     off0 = [int(v) for v in off0]
@@ -299,6 +310,14 @@ def sym_pose_batch(baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_nn=5, max_co
         if cd_h[best[p]] > cd_h[j]:
             best[p] = j
     best_t = torch.from_numpy(best).to(dev)
-    return SymPoseResult(T_best=T[best_t], cd_best=cd[best_t], T_ransac=T[:P], cd_ransac=cd[:P],
-                         ok=ok, iters=iters, n_problems=len(prob_pair), T_all=T, cd_all=cd, inliers=inl,
-                         prob_pair=prob_pair, prob_cfg=prob_cfg, best=best)
+    res = SymPoseResult(T_best=T[best_t], cd_best=cd[best_t], T_ransac=T[:P], cd_ransac=cd[:P],
+                        ok=ok, iters=iters, n_problems=len(prob_pair), T_all=T, cd_all=cd, inliers=inl,
+                        prob_pair=prob_pair, prob_cfg=prob_cfg, best=best)
+
+    # ---- 7. optional refinement of the kept estimate on the geometry itself (Open3D: registration_icp) ----
+    if icp_max_iter > 0:
+        pairs = list(range(P))
+        r = B.icp_batch(xyz0, off0, xyz1, off1, pairs, pairs, res.T_best, icp_max_dist, icp_max_iter)
+        res.T_icp, res.icp_fitness, res.icp_rmse, res.icp_iters = r.T32, r.fitness, r.rmse, r.iters
+        res.cd_icp = B.chamfer_1dir(xyz0, off0, xyz1, off1, pairs, pairs, r.T32)
+    return res

@@ -238,6 +238,9 @@ def run_eval_sharded(pipe, dist, rank, world, catalog, queries, best_match, tabl
         return H.run_eval(pipe, catalog, queries, best_match, table, base_T, lib_T, syms, category, register_top1,
                           cache_dir, True, force_gate, batch_size, in_flight)
     cfg = pipe.cfg
+    if getattr(cfg, "icp_max_iter", 0) > 0:
+        raise ValueError("run_eval_sharded: ICP refinement (Config.icp_max_iter > 0) is not gathered over the ranks yet; "
+                         "run it on one rank (harness.run_eval) or set icp_max_iter = 0")
     bs = batch_size or cfg.batch_size
     dev = pipe.device
     Q = len(queries)

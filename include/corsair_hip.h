@@ -468,10 +468,75 @@ int cs_hardest_negatives(const float* d_qf, int ld_q, const float* d_qxyz, const
 void cs_hardest_stats(uint64_t out[2], int reset);
 
 /* ------------------------------------------------------------------------------------------
+ * cs_icp_batch: batched point-to-point ICP, the refinement behind a global registration.  It follows Open3D's
+ * registration_icp with TransformationEstimationPointToPoint(with_scaling = false) and
+ * ICPConvergenceCriteria(relative_fitness, relative_rmse, max_iteration); the reference has no such step, so this comment
+ * is the specification (tests/icp_ref.py restates it bit for bit).  Every operation below is ONE IEEE f64 operation
+ * unless a fused fma(a, b, c) is written; nothing is contracted.
+ *   Problems: problem p < n_prob owns source segment h_src_seg[p] of d_src (f32 [n,3], offsets h_soff) and target segment
+ *     h_tgt_seg[p] of d_tgt (offsets h_toff), selected as in cs_chamfer_1dir; segments may be shared between problems.
+ *     d_T0 f32 [n_prob,16]: the initial transforms, row-major 4x4 as cs_ransac_batch writes them, widened to f64 (T).
+ *   Pose: every round poses the ORIGINAL source rows (x, y, z) with the current T (row c = T_c0..T_c3):
+ *       p_c = fma(T_c0, x, fma(T_c1, y, fma(T_c2, z, T_c3)))      -- the chain of cs_chamfer_1dir.
+ *     (Open3D transforms the cloud cumulatively and so accumulates the roundings of every iteration; deliberate difference.)
+ *   Association: for a source the target row j of its segment with the smallest canonical squared distance
+ *       d2 = fma(dz, dz, fma(dy, dy, dx * dx)),  d. = p. - (double)t.,
+ *     ties to the smaller row.  The pair is kept iff d2 < max_dist * max_dist, strictly ([O3D-knowledge]: Open3D's
+ *     hybrid search keeps a neighbour AT the radius; a strict threshold is the choice cs_ransac_batch made for max_corr).
+ *     A source whose distances are all NaN / +inf has no pair.
+ *   Evaluation: n_corr = kept pairs; fitness = n_corr / n_src (0 for an empty source segment);
+ *     rmse = sqrt(sum_d2 / n_corr) (0 when n_corr = 0), sum_d2 from the fixed-point sum below.
+ *   Sums: per problem 17 signed 64-bit integer sums over the kept pairs (p, q = (double) target row), relative to the origin
+ *     o_c = 0.5 * (min_c + max_c) of the target segment's bounding box (f32 min / max widened to f64; o = 0 when the segment
+ *     is empty or the box is not finite), p' = p - o, q' = q - o:
+ *       count;  I(p'_c * 2^s1), I(q'_c * 2^s1) for c = x, y, z;  I((p'_a * q'_b) * 2^s2) for a, b in x, y, z;  I(d2 * 2^s2),
+ *     I(v) = (int64) of v clamped to +-2^(61 - eN), truncating toward zero.  With h = max_c 0.5 * (max_c - min_c) (0 like o),
+ *     M = h + max_dist = m * 2^eM (frexp: 0.5 <= m < 1; eM clamped to [-100, 400]) and eN the smallest integer with
+ *     n_src <= 2^eN:  s1 = 61 - eN - eM,  s2 = 61 - eN - 2 eM.  Every kept pair has |p'_c|, |q'_c| <= M, so no term reaches
+ *     the clamp and no sum leaves 2^61.  Integer sums: the same in any order.
+ *   Update (one problem, from its sums, n = count): sp_c = (double)Sp_c * 2^-s1, sq_c likewise, mp = sp / n, mq = sq / n;
+ *     S_ab = fma(-sp_a, mq_b, (double)Spq_ab * 2^-s2) (the cross-covariance about the means, source index first);
+ *     Horn's N from S, its largest eigenvector by horn_qcp with jacobi4 as fallback (corsair_amd/csrc/horn.h, the
+ *     RANSAC's solver and selection rules), the quaternion normalised by division, R as in cs_ransac_batch;
+ *     pm = mp + o, qm = mq + o, t_a = qm_a - fma(R_a2, pm_2, fma(R_a1, pm_1, R_a0 * pm_0));  T <- U T with
+ *       T'_ab = fma(R_a0, T_0b, fma(R_a1, T_1b, R_a2 * T_2b))  (b < 3),
+ *       T'_a3 = fma(R_a0, T_03, fma(R_a1, T_13, fma(R_a2, T_23, t_a)));  the last row of T stays that of T0.
+ *   Loop: evaluate T0; then repeat { update; evaluate } and stop after the evaluation in which |fitness - previous fitness| <
+ *     relative_fitness AND |rmse - previous rmse| < relative_rmse, or after max_iter updates.  A problem stops at once, keeping
+ *     its current T, when an evaluation has n_corr < 3 or a non-finite value, or an update would make T non-finite.
+ *     max_iter = 0 evaluates T0 only (Open3D's evaluate_registration).
+ *   Outputs: d_T f64 [n_prob,16]; d_T32 f32 [n_prob,16], optional = d_T cast once at the end; d_fitness, d_rmse f64 and
+ *     d_ncorr int32 [n_prob] of the LAST evaluation (the one of the returned T); d_iters int32 [n_prob] = updates applied;
+ *     d_corr int32, optional, one entry per source row of every problem, problem-major (problem p starts at the sum of the
+ *     source counts of the problems before it): the target row LOCAL to its segment of the last evaluation, -1 = no pair.
+ *   Independence: a problem's result depends on that problem alone -- not on its batch neighbours, on the order of the
+ *     source rows inside its segment, on the launch shape or on the run.
+ *   Empty source or target segment: answered with fitness 0, rmse 0, T = T0, 0 iterations.  n_prob = 0 is legal.
+ *   Refused (CS_ERR_INVALID): NULL tables or outputs, negative segment ids or sizes, max_dist <= 0 or not finite, NaN
+ *     thresholds; (CS_ERR_UNSUPPORTED): max_iter outside [0, 1000], a segment of 2^31 rows or more.
+ *   Stream behaviour: everything is enqueued on `stream`, max_iter + 1 rounds; convergence is a per-problem device flag on
+ *     which the workgroups of a finished problem leave -- no host wait (CS_ICP_STATS=1 adds one at the end).  Scratch comes
+ *     from the calling thread's pool; no float atomics.
+ *   Paths: the association ranks by |t|^2 - 2 p.t on the f16 matrix cores over the image cs_chamfer_1dir uses (built once
+ *     per call), evaluates the rows of a lane's best tiles with the canonical chain keeping (distance, row), and accepts a
+ *     result only when it lies STRICTLY below the smallest unevaluated tile minimum minus the error budget; workgroups it
+ *     cannot vouch for, or with coordinates outside the f16 range (|c| >= 60), are recomputed by the exhaustive kernel,
+ *     which is the whole path under CS_ICP_F16=0.  Both return the same bits.
+ *   cs_icp_stats: out = {256-source workgroups answered by the f16 path, of those recomputed}, summed over the rounds,
+ *     counted only while CS_ICP_STATS=1.
+ * Profile family "icp".
+ * ---------------------------------------------------------------------------------------- */
+int cs_icp_batch(const float* d_src, const int64_t* h_soff, const float* d_tgt, const int64_t* h_toff,
+                 const int32_t* h_src_seg, const int32_t* h_tgt_seg, int n_prob, const float* d_T0, double max_dist,
+                 int max_iter, double relative_fitness, double relative_rmse, double* d_T, float* d_T32,
+                 double* d_fitness, double* d_rmse, int32_t* d_iters, int32_t* d_ncorr, int32_t* d_corr, void* stream);
+void cs_icp_stats(uint64_t out[2], int reset);
+
+/* ------------------------------------------------------------------------------------------
  * Profiling hooks for bench.py: when enabled the library brackets the launches of each named
  * kernel family with hipEvents on the launch stream and accumulates the elapsed time.
  * names: "conv", "ransac_eval", "ransac_pre", "ransac_hyp", "knn", "chamfer", "topk", "symcut",
- * "kmap", "loss", "hardneg".
+ * "kmap", "loss", "hardneg", "icp".
  * ---------------------------------------------------------------------------------------- */
 void cs_prof_enable(int on);
 void cs_prof_reset(void);

@@ -1,0 +1,210 @@
+"""Batched ICP at the chair registration shape: `python tools/icp_bench.py [--json PATH]`.
+
+32 (query, CAD) pairs of 10 000-point synthetic clouds (corsair_amd.synth, the construction of
+harness.SyntheticScan2CAD) voxelised at 0.03; source = the query's voxels, target = the CAD's; T0 = the true pose
+perturbed by --deg degrees and --trans; at most 30 updates, max_dist = 2 voxels.  Median of --reps repetitions after
+warm-up, device events (wall time next to it):
+ (a) backend.icp_batch (one cs_icp_batch call, no host wait inside);
+ (b) the stand-in a user would write today from existing calls, per iteration: pose with torch in f64,
+     backend.knn_feat on the 3-d points (k = 1), gather, batched Kabsch by torch.linalg.svd, and the host wait of the
+     convergence test (it stops when every problem has converged);
+ (c) for information: max_iter + 1 calls of backend.chamfer_1dir on the same problems -- the cost of the search alone
+     with its target packers re-run every time.
+Also the updates (a) and (b) actually applied, the share of workgroups the f16 association handed to the exhaustive kernel
+(CS_ICP_STATS=1, a run of its own), the library's own time of the call (profile family "icp"), and -- information only --
+one registration step (embed 32 queries, sym_pose_batch against their CADs) with icp_max_iter = 0 and 30 in this process.
+Prints one JSON line."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from corsair_amd import _lib, backend as B, harness as H, synth  # noqa: E402
+
+N_PAIRS, N_POINTS, VOXEL, MAX_ITER = 32, 10000, 0.03, 30
+
+
+def timed(fn, reps, warmup=3):
+    """(median device ms, median wall ms)."""
+    for _ in range(warmup):
+        fn()
+    dev, wall = [], []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        wall.append((time.perf_counter() - t0) * 1e3)
+        dev.append(e0.elapsed_time(e1))
+    return round(float(np.median(dev)), 4), round(float(np.median(wall)), 4)
+
+
+def perturbed(T, deg, trans, rng):
+    ax = rng.standard_normal(3)
+    ax /= np.linalg.norm(ax)
+    a = np.deg2rad(deg)
+    K = np.array([[0, -ax[2], ax[1]], [ax[2], 0, -ax[0]], [-ax[1], ax[0], 0]])
+    D = np.eye(4)
+    D[:3, :3] = np.eye(3) + np.sin(a) * K + (1 - np.cos(a)) * (K @ K)
+    D[:3, 3] = rng.uniform(-trans, trans, 3)
+    return D @ T
+
+
+def problems(dev, deg, trans):
+    """Voxelised query / CAD clouds and the perturbed true poses (query -> CAD)."""
+    rng = np.random.default_rng(31)
+    cads = [synth.make_cloud(c, 15000)[:N_POINTS] for c in range(N_PAIRS)]
+    poses = [synth.random_pose(c, max_trans=0.0) for c in range(N_PAIRS)]
+    queries = [synth.apply_pose(synth.make_cloud(c, 15000)[15000 - N_POINTS:], poses[c], np.float32) for c in range(N_PAIRS)]
+    raw_off = (np.arange(N_PAIRS + 1) * N_POINTS).tolist()
+    out = []
+    for clouds in (queries, cads):
+        xyz = torch.from_numpy(np.concatenate(clouds)).to(dev)
+        keep, _, off = B.voxelize(xyz, raw_off, VOXEL)
+        out += [xyz[keep].contiguous(), [int(o) for o in off]]
+    truth = np.stack([np.linalg.inv(T) for T in poses])
+    T0 = np.stack([perturbed(T, deg, trans, rng) for T in truth]).astype(np.float32)
+    return out[0], out[1], out[2], out[3], torch.from_numpy(T0).to(dev), truth, queries, cads
+
+
+def torch_icp(x0, off0, x1, off1, T0, max_dist, max_iter, rf=1e-6, rr=1e-6):
+    """The stand-in (b).  Returns (T f64 [P,4,4], updates applied per problem as a list)."""
+    dev = x0.device
+    P = len(off0) - 1
+    lens = torch.tensor(np.diff(off0), device=dev)
+    seg = torch.repeat_interleave(torch.arange(P, device=dev), lens, output_size=off0[-1])
+    tstart = torch.tensor(off1[:-1], device=dev)[seg]
+    x0d, x1d = x0.double(), x1.double()
+    nsrc = lens.double()
+    T = T0.double().clone()
+    thr2 = max_dist * max_dist
+
+    def evaluate(T):
+        p = torch.bmm(T[seg, :3, :3], x0d[:, :, None])[:, :, 0] + T[seg, :3, 3]
+        idx = B.knn_feat(p.float(), off0, x1, off1, 1)[:, 0].long() + tstart
+        q = x1d[idx]
+        d2 = ((p - q) ** 2).sum(1)
+        w = (d2 < thr2).double()
+        n = torch.zeros(P, dtype=torch.float64, device=dev).index_add_(0, seg, w)
+        sd = torch.zeros(P, dtype=torch.float64, device=dev).index_add_(0, seg, w * d2)
+        return p, q, w, n, n / nsrc, torch.sqrt(sd / n.clamp(min=1))
+
+    p, q, w, n, fit, rm = evaluate(T)
+    active = n >= 3
+    iters = torch.zeros(P, dtype=torch.int32, device=dev)
+    eye = torch.eye(4, dtype=torch.float64, device=dev)
+    for _ in range(max_iter):
+        mp = torch.zeros(P, 3, dtype=torch.float64, device=dev).index_add_(0, seg, w[:, None] * p) / n.clamp(min=1)[:, None]
+        mq = torch.zeros(P, 3, dtype=torch.float64, device=dev).index_add_(0, seg, w[:, None] * q) / n.clamp(min=1)[:, None]
+        dp, dq = (p - mp[seg]) * w[:, None], q - mq[seg]
+        Hm = torch.zeros(P, 3, 3, dtype=torch.float64, device=dev).index_add_(0, seg, dp[:, :, None] * dq[:, None, :])
+        U, _, Vt = torch.linalg.svd(Hm)
+        V = Vt.transpose(1, 2)
+        sgn = torch.sign(torch.linalg.det(V @ U.transpose(1, 2)))
+        D = torch.diag_embed(torch.stack([torch.ones_like(sgn), torch.ones_like(sgn), sgn], 1))
+        R = V @ D @ U.transpose(1, 2)
+        Up = eye.repeat(P, 1, 1)
+        Up[:, :3, :3] = R
+        Up[:, :3, 3] = mq - torch.bmm(R, mp[:, :, None])[:, :, 0]
+        T = torch.where(active[:, None, None], Up @ T, T)
+        iters += active.int()
+        pf, pr = fit, rm
+        p, q, w, n, fit, rm = evaluate(T)
+        active = active & ~(((fit - pf).abs() < rf) & ((rm - pr).abs() < rr)) & (n >= 3)
+        if not bool(active.any().item()):          # the host wait of the convergence test
+            break
+    return T, iters.tolist()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--json", default=None)
+    ap.add_argument("--reps", type=int, default=15)
+    ap.add_argument("--deg", type=float, default=3.0)
+    ap.add_argument("--trans", type=float, default=0.01)
+    ap.add_argument("--no-step", action="store_true", help="skip the registration-step timing (it builds the network)")
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    x0, off0, x1, off1, T0, truth, queries, cads = problems(dev, a.deg, a.trans)
+    pairs = list(range(N_PAIRS))
+    max_dist = 2 * VOXEL
+    res = {"device": torch.cuda.get_device_name(dev), "hip": torch.version.hip, "pairs": N_PAIRS, "voxel": VOXEL,
+           "source_rows": off0[-1], "target_rows": off1[-1], "max_dist": max_dist, "max_iter": MAX_ITER,
+           "perturbation": {"deg": a.deg, "trans": a.trans}}
+
+    def hip():
+        return B.icp_batch(x0, off0, x1, off1, pairs, pairs, T0, max_dist, MAX_ITER)
+
+    res["icp_hip_ms"], res["icp_hip_wall_ms"] = timed(hip, a.reps)
+    res["icp_torch_ms"], res["icp_torch_wall_ms"] = timed(lambda: torch_icp(x0, off0, x1, off1, T0, max_dist, MAX_ITER),
+                                                          a.reps)
+    res["torch_over_hip"] = round(res["icp_torch_ms"] / res["icp_hip_ms"], 2)
+    res["chamfer_x%d_ms" % (MAX_ITER + 1)], _ = timed(
+        lambda: [B.chamfer_1dir(x0, off0, x1, off1, pairs, pairs, T0) for _ in range(MAX_ITER + 1)], a.reps)
+    r = hip()
+    Tt, it_t = torch_icp(x0, off0, x1, off1, T0, max_dist, MAX_ITER)
+    it_h = r.iters.cpu().numpy()
+    res["updates_hip"] = {"mean": round(float(it_h.mean()), 2), "min": int(it_h.min()), "max": int(it_h.max())}
+    res["updates_torch"] = {"mean": round(float(np.mean(it_t)), 2), "min": int(min(it_t)), "max": int(max(it_t))}
+    res["max_abs_T_diff_vs_torch"] = float((r.T - Tt).abs().max())
+    res["icp_hip_ms_per_round"] = round(res["icp_hip_ms"] / (float(it_h.max()) + 1), 4)
+
+    def errs(T):
+        T = T.cpu().numpy().astype(np.float64)
+        rre = [np.degrees(np.arccos(np.clip((np.trace(T[p, :3, :3] @ truth[p, :3, :3].T) - 1) / 2, -1, 1))) for p in pairs]
+        rte = [np.linalg.norm(T[p, :3, 3] - truth[p, :3, 3]) for p in pairs]
+        return round(float(np.mean(rre)), 4), round(float(np.mean(rte)), 5)
+
+    res["rre_deg_rte_before"], res["rre_deg_rte_after"] = errs(T0), errs(r.T)
+    res["fitness_mean"] = round(float(r.fitness.mean()), 4)
+    _lib.prof_enable(True)
+    _lib.prof_reset()
+    for _ in range(a.reps):
+        hip()
+    torch.cuda.synchronize()
+    ms, n, flop = _lib.prof_get("icp")
+    _lib.prof_enable(False)
+    res["icp_family_ms_per_call"] = round(ms / a.reps, 4)
+    os.environ["CS_ICP_STATS"] = "1"
+    B.icp_stats(reset=True)
+    hip()
+    st = B.icp_stats(reset=True)
+    del os.environ["CS_ICP_STATS"]
+    res["f16_workgroups"], res["fallback_share"] = st[0], round(st[1] / max(st[0], 1), 5)
+    os.environ["CS_ICP_F16"] = "0"
+    res["icp_hip_exhaustive_ms"], _ = timed(hip, max(a.reps // 3, 3))
+    del os.environ["CS_ICP_F16"]
+
+    # ---- information only: one registration step with and without the refinement ----------------------------------------
+    if not a.no_step:
+        sd, emb = synth.make_state_dicts(31)
+        q64 = [c.astype(np.float64) for c in queries]
+        for iters in (0, MAX_ITER):
+            pipe = H.Pipeline(sd, emb, device=dev, config=H.Config(icp_max_iter=iters))
+            cat = pipe.embed_clouds(cads)
+            qx = torch.from_numpy(np.concatenate(q64)).to(dev)
+            qoff = (np.arange(N_PAIRS + 1) * N_POINTS).tolist()
+
+            def step():
+                pipe.register(pipe.embed_batch(qx, qoff), cat, np.ones(N_PAIRS, np.int32), force_gate=True)
+
+            res["register_step_ms_icp%d" % iters], res["register_step_wall_ms_icp%d" % iters] = timed(step, 5, 2)
+        res["register_step_icp_over_plain"] = round(res["register_step_ms_icp%d" % MAX_ITER] / res["register_step_ms_icp0"], 4)
+    print(json.dumps(res))
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
