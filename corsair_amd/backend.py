@@ -483,11 +483,25 @@ class IcpResult(NamedTuple):
     corr_off: Optional[list]
 
 
+def estimate_normals(xyz, offsets, k=16):
+    """cs_estimate_normals: one normal per row (f32 [n,3] device) from the k nearest rows of the row's own segment
+    (host offset list); 3 <= k <= 32.  The semantics are the header comment of cs_estimate_normals.  No host wait."""
+    xyz = _dev(xyz, torch.float32, "points").contiguous()
+    if xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise ValueError("estimate_normals: points must be [n, 3]")
+    if len(offsets) < 1 or int(offsets[-1]) > xyz.shape[0]:
+        raise ValueError("estimate_normals: the offset table exceeds the point array")
+    out = torch.empty_like(xyz)
+    check(_lib.load().cs_estimate_normals(ptr(xyz), i64_array(offsets), len(offsets) - 1, int(k), ptr(out), stream_ptr()))
+    return out
+
+
 def icp_batch(src, soff, tgt, toff, src_seg, tgt_seg, T0, max_dist, max_iter=30, relative_fitness=1e-6,
-              relative_rmse=1e-6, return_corr=False):
+              relative_rmse=1e-6, return_corr=False, tgt_normals=None):
     """cs_icp_batch: point-to-point ICP of problem p = source segment src_seg[p] of `src` against target segment
     tgt_seg[p] of `tgt` (f32 [n,3] device, host offset lists), started at T0[p] (f32 [n_prob,4,4] device).  The semantics
-    are the header comment of cs_icp_batch.  Returns an IcpResult; no host wait."""
+    are the header comment of cs_icp_batch.  tgt_normals (f32, the shape of `tgt`; estimate_normals): point-to-plane
+    estimation instead, cs_icp_plane_batch.  Returns an IcpResult; no host wait."""
     src = _dev(src, torch.float32, "source").contiguous()
     tgt = _dev(tgt, torch.float32, "target").contiguous()
     T0 = _dev(T0, torch.float32, "initial transforms").contiguous()
@@ -515,10 +529,16 @@ def icp_batch(src, soff, tgt, toff, src_seg, tgt_seg, T0, max_dist, max_iter=30,
         lens = [int(soff[s + 1]) - int(soff[s]) for s in src_seg] if sane else []
         corr_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64).tolist()
         corr = torch.full((max(corr_off[-1], 1),), -1, dtype=torch.int32, device=dev)
-    check(_lib.load().cs_icp_batch(ptr(src), i64_array(soff), ptr(tgt), i64_array(toff), i32_array(src_seg),
-                                   i32_array(tgt_seg), n_prob, ptr(T0), float(max_dist), int(max_iter),
-                                   float(relative_fitness), float(relative_rmse), ptr(T), ptr(T32), ptr(fitness),
-                                   ptr(rmse), ptr(iters), ptr(ncorr), ptr(corr), stream_ptr()))
+    tail = (i64_array(toff), i32_array(src_seg), i32_array(tgt_seg), n_prob, ptr(T0), float(max_dist), int(max_iter),
+            float(relative_fitness), float(relative_rmse), ptr(T), ptr(T32), ptr(fitness), ptr(rmse), ptr(iters),
+            ptr(ncorr), ptr(corr), stream_ptr())
+    if tgt_normals is None:
+        check(_lib.load().cs_icp_batch(ptr(src), i64_array(soff), ptr(tgt), *tail))
+    else:
+        nrm = _dev(tgt_normals, torch.float32, "target normals").contiguous()
+        if nrm.shape != tgt.shape:
+            raise ValueError("icp_batch: tgt_normals must have the shape of the target points")
+        check(_lib.load().cs_icp_plane_batch(ptr(src), i64_array(soff), ptr(tgt), ptr(nrm), *tail))
     if corr is not None:
         corr = corr[:corr_off[-1]]
     return IcpResult(T, T32, fitness, rmse, iters, ncorr, corr, corr_off)

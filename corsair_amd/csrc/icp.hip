@@ -1,14 +1,16 @@
-// Batched point-to-point ICP.  The specification is the comment of cs_icp_batch in include/corsair_hip.h;
-// tests/icp_ref.py restates it bit for bit.
+// Batched ICP: point-to-point (cs_icp_batch) and point-to-plane (cs_icp_plane_batch).  The specifications
+// are the comments of the two entries in include/corsair_hip.h; tests/icp_ref.py and tests/icp_plane_ref.py restate them bit
+// for bit.  The estimation is a compile-time parameter EST (0 = point, 1 = plane) of the sums at the end of the association
+// kernels and of the update; pose chain, association, evaluation, loop and stop rule are one code.
 //
 // One call = one target preparation + (max_iter + 1) rounds, all enqueued without a host wait:
 //   k_icp_frame    per problem: the bounding box of its target segment (exact min / max), the origin and the
 //                  power-of-two scales of its fixed-point sums
 //   chamfer_pack16 the f16 hi / lo image, |S t|^2 and the float4 rows of every target, once per call
 //   round r:       k_icp_f16 (+ k_icp_exact for the workgroups it flags) or k_icp_exact alone -- association of the posed
-//                  ORIGINAL sources under the current T, 17 order-free 64-bit integer sums per problem;
-//                  k_icp_step -- one lane per problem: fitness / rmse of that association, the stop rule, Horn's fit
-//                  from the sums, T <- U T.
+//                  ORIGINAL sources under the current T, 17 (point) or 29 (plane) order-free 64-bit integer sums per
+//                  problem; k_icp_step -- one lane per problem: fitness / rmse of that association, the stop rule, Horn's
+//                  fit (point) or the 6x6 normal equations by Cholesky (plane) from the sums, T <- U T.
 // A problem that has stopped raises its device flag; its workgroups leave on it in every later round.
 #include <math.h>
 
@@ -23,6 +25,12 @@ namespace {
 constexpr int ICP_ST = 4 * 32 * CHF_NG;   // sources per workgroup (both association kernels)
 constexpr int ICP_TT = 512;               // target rows per LDS stage of the exact kernel
 constexpr int ICP_NSUM = 17;              // count, sum p' (3), sum q' (3), sum p' q'^T (9), sum d^2
+constexpr int ICP_NSUM_PLANE = 29;        // count, sum J_i J_j (i <= j, 21), sum J_i r (6), sum d^2
+constexpr int ICP_POINT = 0, ICP_PLANE = 1;
+template <int EST>
+constexpr int icp_nsum() {
+  return EST == ICP_PLANE ? ICP_NSUM_PLANE : ICP_NSUM;
+}
 
 // Fixed-point sums.  A kept pair has |p - q|^2 < max_dist^2 and q inside the bounding box of the target segment, so
 // relative to the box's midpoint o every coordinate obeys |q'_c| <= h_c and |p'_c| <= h_c + max_dist, h = the box's
@@ -36,6 +44,19 @@ constexpr int ICP_NSUM = 17;              // count, sum p' (3), sum q' (3), sum 
 // those sums then carry no meaning, but they are defined and the same in every run.
 // eM in [-100, 400] and eN in [0, 31] keep both scales and their inverses normal f64 powers of two (s1 in [-370, 161],
 // s2 in [-770, 261]), so scaling is exact.
+//
+// Point-to-plane (EST = 1).  Per kept pair n = the widened normal row of the matched target, e = p - q, r = e . n,
+// a = p' x n, J = (a, n).  With |p'_c| <= M < 2^eM as above, |n_c| <= 1 (a unit normal cast to f32) and |e| < max_dist <= M:
+//   |a_c| = |p'_b n_c - p'_c n_b| <= 2 M,  |r| <= |e| |n| < max_dist  -- each up to a few roundings of relative 2^-53
+//   (and of 2^-24 in |n| for a normal normalised in f32), for which every class below gets ONE extra bit:
+//   rot x rot     |a_i a_j| <= 4 M^2        < 2^(2 eM + 2)   scale 2^(61 - eN - 2 eM - 3)
+//   rot x trans   |a_i n_j| <= 2 M          < 2^(eM + 1)     scale 2^(61 - eN - eM - 2)
+//   trans x trans |n_i n_j| <= 1                             scale 2^(61 - eN - 1)
+//   rot x r       |a_i r|   <  2 M max_dist < 2^(2 eM + 1)   scale 2^(61 - eN - 2 eM - 2)
+//   trans x r     |n_i r|   <  max_dist     < 2^eM           scale 2^(61 - eN - eM - 1)
+// so every scaled term is below 2^(61 - eN) and every sum below 2^61, as for the point sums; d^2 keeps the scale 2^s2.
+// The clamp makes that hold for ANY normals a caller passes (length 10^3, NaN): such sums are defined, not meaningful.
+// The exponents stay inside [-773, 260]: normal f64 powers of two, exact scaling.
 constexpr int ICP_EM_MIN = -100;
 constexpr int ICP_EM_MAX = 400;
 constexpr int ICP_SUM_BITS = 61;
@@ -57,13 +78,17 @@ struct IcpFrame {
   double inv1, inv2;
   double clamp;     // 2^(61 - eN)
 };
+struct IcpPlaneFrame {   // 2^s and 2^-s of the five product classes of the plane sums
+  double sc_rr, inv_rr, sc_rt, inv_rt, sc_tt, inv_tt, sc_rd, inv_rd, sc_td, inv_td;
+};
 struct IcpCriteria {
   double thr2;      // max_dist * max_dist
   double rel_fitness, rel_rmse;
 };
 
 __global__ __launch_bounds__(256) void k_icp_frame(const IcpProb* __restrict__ probs, const float* __restrict__ tgt,
-                                                   double max_dist, IcpFrame* __restrict__ frame) {
+                                                   double max_dist, IcpFrame* __restrict__ frame,
+                                                   IcpPlaneFrame* __restrict__ pframe) {
   __shared__ float red[2][3][4];
   const IcpProb pr = probs[blockIdx.x];
   const int tid = threadIdx.x;
@@ -119,6 +144,21 @@ __global__ __launch_bounds__(256) void k_icp_frame(const IcpProb* __restrict__ p
   f.inv2 = ldexp(1.0, -s2);
   f.clamp = ldexp(1.0, ICP_SUM_BITS - eN);
   frame[blockIdx.x] = f;
+  if (pframe) {
+    const int b = ICP_SUM_BITS - eN;
+    IcpPlaneFrame g;
+    g.sc_rr = ldexp(1.0, b - 2 * eM - 3);
+    g.inv_rr = ldexp(1.0, -(b - 2 * eM - 3));
+    g.sc_rt = ldexp(1.0, b - eM - 2);
+    g.inv_rt = ldexp(1.0, -(b - eM - 2));
+    g.sc_tt = ldexp(1.0, b - 1);
+    g.inv_tt = ldexp(1.0, -(b - 1));
+    g.sc_rd = ldexp(1.0, b - 2 * eM - 2);
+    g.inv_rd = ldexp(1.0, -(b - 2 * eM - 2));
+    g.sc_td = ldexp(1.0, b - eM - 1);
+    g.inv_td = ldexp(1.0, -(b - eM - 1));
+    pframe[blockIdx.x] = g;
+  }
 }
 
 __device__ __forceinline__ long long icp_fix(double v, double scale, double clamp) {
@@ -126,16 +166,46 @@ __device__ __forceinline__ long long icp_fix(double v, double scale, double clam
   return (long long)x;                                     // truncates toward zero
 }
 
-// The 17 sums of one workgroup: thread = one source (kept or not), wave shuffle, LDS across the four waves, then ONE
-// 64-bit integer atomic per sum.  Integer addition: the same total in any order.
+// The sums of one workgroup (17 for the point estimation, 29 for the plane one): thread = one source (kept or not), wave
+// shuffle, LDS across the four waves, then ONE 64-bit integer atomic per sum.  Integer addition: the same total in any
+// order.  nrow: the normal row of the matched target (plane estimation, kept pairs only).
+template <int EST>
 __device__ __forceinline__ void icp_block_sums(bool kept, double px, double py, double pz, float qx, float qy, float qz,
-                                               double d2, const IcpFrame& fr, unsigned long long* __restrict__ sums,
-                                               unsigned long long (*part)[ICP_NSUM]) {
+                                               double d2, const IcpFrame& fr, const IcpPlaneFrame* __restrict__ pfr,
+                                               const float* __restrict__ nrow, unsigned long long* __restrict__ sums,
+                                               unsigned long long (*part)[icp_nsum<EST>()]) {
+  constexpr int NS = icp_nsum<EST>();
   const int tid = threadIdx.x;
-  long long v[ICP_NSUM];
+  long long v[NS];
 #pragma unroll
-  for (int k = 0; k < ICP_NSUM; ++k) v[k] = 0;
-  if (kept) {
+  for (int k = 0; k < NS; ++k) v[k] = 0;
+  if constexpr (EST == ICP_PLANE) {
+    if (kept) {
+      const IcpPlaneFrame g = *pfr;
+      const double p[3] = {px - fr.o[0], py - fr.o[1], pz - fr.o[2]};
+      const double n[3] = {(double)nrow[0], (double)nrow[1], (double)nrow[2]};
+      const double e[3] = {px - (double)qx, py - (double)qy, pz - (double)qz};
+      const double r = fma(e[2], n[2], fma(e[1], n[1], e[0] * n[0]));
+      const double J[6] = {fma(p[1], n[2], -(p[2] * n[1])), fma(p[2], n[0], -(p[0] * n[2])),
+                           fma(p[0], n[1], -(p[1] * n[0])), n[0], n[1], n[2]};
+      v[0] = 1;
+      int at = 1;
+#pragma unroll
+      for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = i; j < 6; ++j) {
+          const double prod = J[i] * J[j];   // rounded product (no contraction)
+          const double sc = j < 3 ? g.sc_rr : (i < 3 ? g.sc_rt : g.sc_tt);
+          v[at++] = icp_fix(prod, sc, fr.clamp);
+        }
+#pragma unroll
+      for (int i = 0; i < 6; ++i) {
+        const double prod = J[i] * r;
+        v[22 + i] = icp_fix(prod, i < 3 ? g.sc_rd : g.sc_td, fr.clamp);
+      }
+      v[28] = icp_fix(d2, fr.sc2, fr.clamp);
+    }
+  } else if (kept) {
     const double p[3] = {px - fr.o[0], py - fr.o[1], pz - fr.o[2]};
     const double q[3] = {(double)qx - fr.o[0], (double)qy - fr.o[1], (double)qz - fr.o[2]};
     v[0] = 1;
@@ -154,14 +224,14 @@ __device__ __forceinline__ void icp_block_sums(bool kept, double px, double py, 
     v[16] = icp_fix(d2, fr.sc2, fr.clamp);
   }
 #pragma unroll
-  for (int k = 0; k < ICP_NSUM; ++k) {
+  for (int k = 0; k < NS; ++k) {
     unsigned long long s = (unsigned long long)v[k];
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) s += __shfl_down(s, off);
     if ((tid & 63) == 0) part[tid >> 6][k] = s;
   }
   __syncthreads();
-  if (tid < ICP_NSUM) {
+  if (tid < NS) {
     const unsigned long long s = (part[0][tid] + part[1][tid]) + (part[2][tid] + part[3][tid]);
     if (s) atomicAdd(&sums[tid], s);
   }
@@ -178,14 +248,17 @@ __device__ __forceinline__ void icp_pose(const double* __restrict__ Tp, const fl
 // Exhaustive association, one source per thread: the canonical chain over every target row in ascending order with a
 // strict comparison, i.e. the minimum by (distance, row).  The whole path under CS_ICP_F16=0, and the recomputation of
 // the workgroups k_icp_f16 flags.
+template <int EST>
 __global__ __launch_bounds__(256) void k_icp_exact(const IcpWork* __restrict__ work, const IcpProb* __restrict__ probs,
                                                    const float* __restrict__ src, const float* __restrict__ tgt,
-                                                   const double* __restrict__ T, const IcpFrame* __restrict__ frame,
+                                                   const float* __restrict__ tnrm, const double* __restrict__ T,
+                                                   const IcpFrame* __restrict__ frame,
+                                                   const IcpPlaneFrame* __restrict__ pframe,
                                                    const int32_t* __restrict__ done, double thr2,
                                                    unsigned long long* __restrict__ sums, int32_t* __restrict__ corr,
                                                    const int32_t* __restrict__ only_flagged) {
   __shared__ float t_lds[ICP_TT * 3];
-  __shared__ unsigned long long part[4][ICP_NSUM];
+  __shared__ unsigned long long part[4][icp_nsum<EST>()];
   if (only_flagged && !only_flagged[blockIdx.x]) return;
   const IcpWork wk = work[blockIdx.x];
   if (done[wk.prob]) return;
@@ -222,7 +295,9 @@ __global__ __launch_bounds__(256) void k_icp_exact(const IcpWork* __restrict__ w
     qz = tp[2];
   }
   if (corr && active) corr[wk.c0 + tid] = kept ? bidx : -1;
-  icp_block_sums(kept, px, py, pz, qx, qy, qz, best, frame[wk.prob], sums + (int64_t)wk.prob * ICP_NSUM, part);
+  icp_block_sums<EST>(kept, px, py, pz, qx, qy, qz, best, frame[wk.prob], EST == ICP_PLANE ? pframe + wk.prob : nullptr,
+                      EST == ICP_PLANE && kept ? tnrm + (pr.t0 + bidx) * 3 : nullptr,
+                      sums + (int64_t)wk.prob * icp_nsum<EST>(), part);
 }
 
 // The association on the f16 matrix cores: k_chamfer_f16's ranking (same image, same operand layout, same error budget;
@@ -230,16 +305,19 @@ __global__ __launch_bounds__(256) void k_icp_exact(const IcpWork* __restrict__ w
 // when it lies below the smallest unevaluated tile minimum minus the error budget, so a row that was not evaluated can
 // neither beat nor tie it.  A workgroup with a source that fails the test, or with coordinates outside the f16 range,
 // adds nothing and raises its flag; k_icp_exact recomputes it.
+template <int EST>
 __global__ __launch_bounds__(256) void k_icp_f16(const IcpWork* __restrict__ work, const IcpProb* __restrict__ probs,
                                                  const float* __restrict__ src, const float4* __restrict__ t4f,
                                                  const _Float16* __restrict__ img, const float* __restrict__ tn32,
-                                                 const double* __restrict__ T, const IcpFrame* __restrict__ frame,
+                                                 const float* __restrict__ tnrm, const double* __restrict__ T,
+                                                 const IcpFrame* __restrict__ frame,
+                                                 const IcpPlaneFrame* __restrict__ pframe,
                                                  const int32_t* __restrict__ done, double thr2,
                                                  unsigned long long* __restrict__ sums, int32_t* __restrict__ corr,
                                                  int32_t* __restrict__ flag, unsigned long long* __restrict__ stats) {
   __shared__ __attribute__((aligned(16))) _Float16 a_s[2][CHF_ROWS * CHF_PITCH];
   __shared__ __attribute__((aligned(16))) float tn_s[2][CHF_ROWS];
-  __shared__ unsigned long long part[4][ICP_NSUM];
+  __shared__ unsigned long long part[4][icp_nsum<EST>()];
   __shared__ float wmax[4];
   __shared__ int wg_bad;
   const IcpWork wk = work[blockIdx.x];
@@ -439,7 +517,10 @@ __global__ __launch_bounds__(256) void k_icp_f16(const IcpWork* __restrict__ wor
   float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
   if (kept) q = trow[my_row];
   if (corr && active) corr[wk.c0 + tid] = kept ? my_row : -1;
-  icp_block_sums(kept, mpx, mpy, mpz, q.x, q.y, q.z, my_e, frame[wk.prob], sums + (int64_t)wk.prob * ICP_NSUM, part);
+  icp_block_sums<EST>(kept, mpx, mpy, mpz, q.x, q.y, q.z, my_e, frame[wk.prob],
+                      EST == ICP_PLANE ? pframe + wk.prob : nullptr,
+                      EST == ICP_PLANE && kept ? tnrm + (pr.t0 + my_row) * 3 : nullptr,
+                      sums + (int64_t)wk.prob * icp_nsum<EST>(), part);
 }
 
 __device__ __forceinline__ bool icp_all_finite(const double* v, int n) {
@@ -448,24 +529,186 @@ __device__ __forceinline__ bool icp_all_finite(const double* v, int n) {
   return f;
 }
 
+// R of the quaternion (w, x, y, z), normalised by division: cs_ransac_batch's formula.
+__device__ __forceinline__ void icp_quat_rotation(double qw, double qx, double qy, double qz, double (&R)[3][3]) {
+  const double qn = sqrt(qw * qw + qx * qx + qy * qy + qz * qz);
+  qw = qw / qn;
+  qx = qx / qn;
+  qy = qy / qn;
+  qz = qz / qn;
+  R[0][0] = 1.0 - 2.0 * (qy * qy + qz * qz);
+  R[0][1] = 2.0 * (qx * qy - qw * qz);
+  R[0][2] = 2.0 * (qx * qz + qw * qy);
+  R[1][0] = 2.0 * (qx * qy + qw * qz);
+  R[1][1] = 1.0 - 2.0 * (qx * qx + qz * qz);
+  R[1][2] = 2.0 * (qy * qz - qw * qx);
+  R[2][0] = 2.0 * (qx * qz - qw * qy);
+  R[2][1] = 2.0 * (qy * qz + qw * qx);
+  R[2][2] = 1.0 - 2.0 * (qx * qx + qy * qy);
+}
+
+// Tn = U T, U = (R, t): the first three rows of the 4x4.
+__device__ __forceinline__ void icp_compose(const double (&R)[3][3], const double (&t)[3], const double* __restrict__ Tp,
+                                            double (&Tn)[12]) {
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+#pragma unroll
+    for (int b = 0; b < 3; ++b) Tn[4 * a + b] = fma(R[a][0], Tp[b], fma(R[a][1], Tp[4 + b], R[a][2] * Tp[8 + b]));
+    Tn[4 * a + 3] = fma(R[a][0], Tp[3], fma(R[a][1], Tp[7], fma(R[a][2], Tp[11], t[a])));
+  }
+}
+
+// The point-to-point update from the 17 sums: Horn's fit about the means.
+__device__ __forceinline__ void icp_update_point(const unsigned long long* __restrict__ S, double dn, const IcpFrame& fr,
+                                                 const double* __restrict__ Tp, double (&Tn)[12]) {
+  double sp[3], sq[3], mp[3], mq[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    sp[c] = (double)(long long)S[1 + c] * fr.inv1;
+    sq[c] = (double)(long long)S[4 + c] * fr.inv1;
+    mp[c] = sp[c] / dn;
+    mq[c] = sq[c] / dn;
+  }
+  // cross-covariance about the means, source index first (the RANSAC's S): sum p'_a q'_b - (sum p'_a) mean q'_b
+  double Sm[3][3], N[4][4], V[4][4];
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b) Sm[a][b] = fma(-sp[a], mq[b], (double)(long long)S[7 + 3 * a + b] * fr.inv2);
+  N[0][0] = Sm[0][0] + Sm[1][1] + Sm[2][2];
+  N[0][1] = Sm[1][2] - Sm[2][1];
+  N[0][2] = Sm[2][0] - Sm[0][2];
+  N[0][3] = Sm[0][1] - Sm[1][0];
+  N[1][1] = Sm[0][0] - Sm[1][1] - Sm[2][2];
+  N[1][2] = Sm[0][1] + Sm[1][0];
+  N[1][3] = Sm[2][0] + Sm[0][2];
+  N[2][2] = -Sm[0][0] + Sm[1][1] - Sm[2][2];
+  N[2][3] = Sm[1][2] + Sm[2][1];
+  N[3][3] = -Sm[0][0] - Sm[1][1] + Sm[2][2];
+  N[1][0] = N[0][1];
+  N[2][0] = N[0][2];
+  N[3][0] = N[0][3];
+  N[2][1] = N[1][2];
+  N[3][1] = N[1][3];
+  N[3][2] = N[2][3];
+  double qv[4];
+  if (!horn_qcp(Sm, N, qv)) {
+    jacobi4(N, V);
+    // eigenvector of the largest eigenvalue (ties -> lowest index), as the RANSAC selects it
+    double best = N[0][0];
+    qv[0] = V[0][0]; qv[1] = V[1][0]; qv[2] = V[2][0]; qv[3] = V[3][0];
+#pragma unroll
+    for (int c = 1; c < 4; ++c) {
+      if (N[c][c] > best) {
+        best = N[c][c];
+        qv[0] = V[0][c];
+        qv[1] = V[1][c];
+        qv[2] = V[2][c];
+        qv[3] = V[3][c];
+      }
+    }
+  }
+  double R[3][3];
+  icp_quat_rotation(qv[0], qv[1], qv[2], qv[3], R);
+  // t = q_mean - R p_mean on the unprimed means; T <- U T
+  double pm[3], qm[3], t[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    pm[c] = mp[c] + fr.o[c];
+    qm[c] = mq[c] + fr.o[c];
+  }
+#pragma unroll
+  for (int a = 0; a < 3; ++a) t[a] = qm[a] - fma(R[a][2], pm[2], fma(R[a][1], pm[1], R[a][0] * pm[0]));
+  icp_compose(R, t, Tp, Tn);
+}
+
+// A pivot of the Cholesky factorisation must exceed this fraction of its own original diagonal entry.  pivot_j / A_jj is
+// the share of column j of the Jacobian that the columns before it do not explain; the fixed-point sums carry each A_jj to
+// 2^-44 relative or better (scale 2^(61 - eN - ...) against at most 2^eN terms of that magnitude bound), so a share below
+// 2^-30 is four decimal orders above the noise of the sums and far below any geometry that constrains the pose.
+constexpr double ICP_PIVOT_MIN = 0x1.0p-30;
+
+// The point-to-plane update from the 29 sums: A x = -b by an unpivoted Cholesky, x = (alpha, t') about the origin o, the
+// rotation of the quaternion (1, alpha / 2).  false: a pivot is not finite or too small -- the problem stops.
+__device__ __forceinline__ bool icp_update_plane(const unsigned long long* __restrict__ S, const IcpFrame& fr,
+                                                 const IcpPlaneFrame& g, const double* __restrict__ Tp, double (&Tn)[12]) {
+  double A[6][6], L[6][6], bv[6], yv[6], xv[6];
+  {
+    int at = 1;
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+      for (int j = i; j < 6; ++j) {
+        const double inv = j < 3 ? g.inv_rr : (i < 3 ? g.inv_rt : g.inv_tt);
+        A[i][j] = (double)(long long)S[at++] * inv;
+        A[j][i] = A[i][j];
+      }
+  }
+#pragma unroll
+  for (int i = 0; i < 6; ++i) bv[i] = (double)(long long)S[22 + i] * (i < 3 ? g.inv_rd : g.inv_td);
+  bool ok = true;
+#pragma unroll
+  for (int j = 0; j < 6; ++j) {
+    double d = A[j][j];
+#pragma unroll
+    for (int k = 0; k < j; ++k) d = fma(-L[j][k], L[j][k], d);
+    if (!(isfinite(d) && d > ICP_PIVOT_MIN * A[j][j])) ok = false;
+    const double ljj = sqrt(d);
+    L[j][j] = ljj;
+#pragma unroll
+    for (int i = j + 1; i < 6; ++i) {
+      double v = A[i][j];
+#pragma unroll
+      for (int k = 0; k < j; ++k) v = fma(-L[i][k], L[j][k], v);
+      L[i][j] = v / ljj;
+    }
+  }
+  if (!ok) return false;
+#pragma unroll
+  for (int i = 0; i < 6; ++i) {
+    double v = -bv[i];
+#pragma unroll
+    for (int k = 0; k < i; ++k) v = fma(-L[i][k], yv[k], v);
+    yv[i] = v / L[i][i];
+  }
+#pragma unroll
+  for (int i = 5; i >= 0; --i) {
+    double v = yv[i];
+#pragma unroll
+    for (int k = i + 1; k < 6; ++k) v = fma(-L[k][i], xv[k], v);
+    xv[i] = v / L[i][i];
+  }
+  double R[3][3], t[3];
+  icp_quat_rotation(1.0, 0.5 * xv[0], 0.5 * xv[1], 0.5 * xv[2], R);
+  // p <- R (p - o) + t' + o:  t = t' + o - R o
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+    t[a] = (xv[3 + a] + fr.o[a]) - fma(R[a][2], fr.o[2], fma(R[a][1], fr.o[1], R[a][0] * fr.o[0]));
+  icp_compose(R, t, Tp, Tn);
+  return true;
+}
+
 // One lane per problem: the evaluation of the association just made, the stop rule, the update.  last = the round after
 // the max_iter-th update (or the only one when max_iter = 0): nothing is fitted, the f32 copy of T is written.
+template <int EST>
 __global__ void k_icp_step(const IcpProb* __restrict__ probs, int n_prob, const IcpFrame* __restrict__ frame,
-                           IcpCriteria crit, int round, int last, unsigned long long* __restrict__ sums,
-                           int32_t* __restrict__ done, double* __restrict__ T, float* __restrict__ T32,
-                           double* __restrict__ fitness, double* __restrict__ rmse, int32_t* __restrict__ iters,
-                           int32_t* __restrict__ ncorr) {
+                           const IcpPlaneFrame* __restrict__ pframe, IcpCriteria crit, int round, int last,
+                           unsigned long long* __restrict__ sums, int32_t* __restrict__ done, double* __restrict__ T,
+                           float* __restrict__ T32, double* __restrict__ fitness, double* __restrict__ rmse,
+                           int32_t* __restrict__ iters, int32_t* __restrict__ ncorr) {
+  constexpr int NS = icp_nsum<EST>();
+  constexpr int MIN_CORR = EST == ICP_PLANE ? 6 : 3;
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= n_prob) return;
   double* Tp = T + (int64_t)p * 16;
   if (!done[p]) {
     const IcpProb pr = probs[p];
     const IcpFrame fr = frame[p];
-    unsigned long long* S = sums + (int64_t)p * ICP_NSUM;
+    unsigned long long* S = sums + (int64_t)p * NS;
     const long long n = (long long)S[0];
     const double dn = (double)n;
     const double fit = pr.sn > 0 ? dn / (double)pr.sn : 0.0;
-    const double sd2 = (double)(long long)S[16] * fr.inv2;
+    const double sd2 = (double)(long long)S[NS - 1] * fr.inv2;
     const double rm = n > 0 ? sqrt(sd2 / dn) : 0.0;
     const double pfit = fitness[p], prm = rmse[p];
     fitness[p] = fit;
@@ -473,92 +716,20 @@ __global__ void k_icp_step(const IcpProb* __restrict__ probs, int n_prob, const 
     ncorr[p] = (int32_t)n;
     bool stop = last != 0;
     if (round > 0 && fabs(fit - pfit) < crit.rel_fitness && fabs(rm - prm) < crit.rel_rmse) stop = true;
-    if (n < 3 || !isfinite(fit) || !isfinite(rm)) stop = true;
+    if (n < MIN_CORR || !isfinite(fit) || !isfinite(rm)) stop = true;
     if (!stop) {
-      double sp[3], sq[3], mp[3], mq[3];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        sp[c] = (double)(long long)S[1 + c] * fr.inv1;
-        sq[c] = (double)(long long)S[4 + c] * fr.inv1;
-        mp[c] = sp[c] / dn;
-        mq[c] = sq[c] / dn;
-      }
-      // cross-covariance about the means, source index first (the RANSAC's S): sum p'_a q'_b - (sum p'_a) mean q'_b
-      double Sm[3][3], N[4][4], V[4][4];
-#pragma unroll
-      for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = 0; b < 3; ++b) Sm[a][b] = fma(-sp[a], mq[b], (double)(long long)S[7 + 3 * a + b] * fr.inv2);
-      N[0][0] = Sm[0][0] + Sm[1][1] + Sm[2][2];
-      N[0][1] = Sm[1][2] - Sm[2][1];
-      N[0][2] = Sm[2][0] - Sm[0][2];
-      N[0][3] = Sm[0][1] - Sm[1][0];
-      N[1][1] = Sm[0][0] - Sm[1][1] - Sm[2][2];
-      N[1][2] = Sm[0][1] + Sm[1][0];
-      N[1][3] = Sm[2][0] + Sm[0][2];
-      N[2][2] = -Sm[0][0] + Sm[1][1] - Sm[2][2];
-      N[2][3] = Sm[1][2] + Sm[2][1];
-      N[3][3] = -Sm[0][0] - Sm[1][1] + Sm[2][2];
-      N[1][0] = N[0][1];
-      N[2][0] = N[0][2];
-      N[3][0] = N[0][3];
-      N[2][1] = N[1][2];
-      N[3][1] = N[1][3];
-      N[3][2] = N[2][3];
-      double qv[4];
-      if (!horn_qcp(Sm, N, qv)) {
-        jacobi4(N, V);
-        // eigenvector of the largest eigenvalue (ties -> lowest index), as the RANSAC selects it
-        double best = N[0][0];
-        qv[0] = V[0][0]; qv[1] = V[1][0]; qv[2] = V[2][0]; qv[3] = V[3][0];
-#pragma unroll
-        for (int c = 1; c < 4; ++c) {
-          if (N[c][c] > best) {
-            best = N[c][c];
-            qv[0] = V[0][c];
-            qv[1] = V[1][c];
-            qv[2] = V[2][c];
-            qv[3] = V[3][c];
-          }
-        }
-      }
-      double qw = qv[0], qx = qv[1], qy = qv[2], qz = qv[3];
-      const double qn = sqrt(qw * qw + qx * qx + qy * qy + qz * qz);
-      qw = qw / qn;
-      qx = qx / qn;
-      qy = qy / qn;
-      qz = qz / qn;
-      double R[3][3];
-      R[0][0] = 1.0 - 2.0 * (qy * qy + qz * qz);
-      R[0][1] = 2.0 * (qx * qy - qw * qz);
-      R[0][2] = 2.0 * (qx * qz + qw * qy);
-      R[1][0] = 2.0 * (qx * qy + qw * qz);
-      R[1][1] = 1.0 - 2.0 * (qx * qx + qz * qz);
-      R[1][2] = 2.0 * (qy * qz - qw * qx);
-      R[2][0] = 2.0 * (qx * qz - qw * qy);
-      R[2][1] = 2.0 * (qy * qz + qw * qx);
-      R[2][2] = 1.0 - 2.0 * (qx * qx + qy * qy);
-      // t = q_mean - R p_mean on the unprimed means; T <- U T
-      double pm[3], qm[3], Tn[12];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        pm[c] = mp[c] + fr.o[c];
-        qm[c] = mq[c] + fr.o[c];
-      }
-#pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        const double t = qm[a] - fma(R[a][2], pm[2], fma(R[a][1], pm[1], R[a][0] * pm[0]));
-#pragma unroll
-        for (int b = 0; b < 3; ++b)
-          Tn[4 * a + b] = fma(R[a][0], Tp[b], fma(R[a][1], Tp[4 + b], R[a][2] * Tp[8 + b]));
-        Tn[4 * a + 3] = fma(R[a][0], Tp[3], fma(R[a][1], Tp[7], fma(R[a][2], Tp[11], t)));
-      }
-      if (icp_all_finite(Tn, 12)) {
+      double Tn[12];
+      bool solved = true;
+      if constexpr (EST == ICP_PLANE)
+        solved = icp_update_plane(S, fr, pframe[p], Tp, Tn);
+      else
+        icp_update_point(S, dn, fr, Tp, Tn);
+      if (solved && icp_all_finite(Tn, 12)) {
 #pragma unroll
         for (int i = 0; i < 12; ++i) Tp[i] = Tn[i];
         iters[p] = iters[p] + 1;
 #pragma unroll
-        for (int k = 0; k < ICP_NSUM; ++k) S[k] = 0;
+        for (int k = 0; k < NS; ++k) S[k] = 0;
       } else {
         stop = true;
       }
@@ -585,38 +756,32 @@ __global__ void k_icp_init(const float* __restrict__ T0, int n_prob, double* __r
 
 std::atomic<unsigned long long> g_icp_stats[2];
 
-}  // namespace
-}  // namespace cs
-
-using namespace cs;
-
-extern "C" {
-
-void cs_icp_stats(uint64_t out[2], int reset) { read_stats(g_icp_stats, out, reset); }
-
-int cs_icp_batch(const float* d_src, const int64_t* h_soff, const float* d_tgt, const int64_t* h_toff,
-                 const int32_t* h_src_seg, const int32_t* h_tgt_seg, int n_prob, const float* d_T0, double max_dist,
-                 int max_iter, double relative_fitness, double relative_rmse, double* d_T, float* d_T32,
-                 double* d_fitness, double* d_rmse, int32_t* d_iters, int32_t* d_ncorr, int32_t* d_corr, void* stream) {
-  CS_REQUIRE(h_soff && h_toff && h_src_seg && h_tgt_seg, CS_ERR_INVALID, "cs_icp_batch: NULL table");
-  CS_REQUIRE(n_prob >= 0, CS_ERR_INVALID, "cs_icp_batch: negative problem count");
-  CS_REQUIRE(max_dist > 0.0 && std::isfinite(max_dist), CS_ERR_INVALID, "cs_icp_batch: max_dist must be positive and finite");
-  CS_REQUIRE(max_iter >= 0 && max_iter <= 1000, CS_ERR_UNSUPPORTED, "cs_icp_batch: max_iter outside [0, 1000]");
+// Both entries: d_tnrm is the normal array of the plane estimation (EST = 1), unused otherwise.
+template <int EST>
+int icp_run(const char* name, const float* d_src, const int64_t* h_soff, const float* d_tgt, const float* d_tnrm,
+            const int64_t* h_toff, const int32_t* h_src_seg, const int32_t* h_tgt_seg, int n_prob, const float* d_T0,
+            double max_dist, int max_iter, double relative_fitness, double relative_rmse, double* d_T, float* d_T32,
+            double* d_fitness, double* d_rmse, int32_t* d_iters, int32_t* d_ncorr, int32_t* d_corr, void* stream) {
+  constexpr int NS = icp_nsum<EST>();
+  CS_REQUIRE(h_soff && h_toff && h_src_seg && h_tgt_seg, CS_ERR_INVALID, "%s: NULL table", name);
+  CS_REQUIRE(n_prob >= 0, CS_ERR_INVALID, "%s: negative problem count", name);
+  CS_REQUIRE(max_dist > 0.0 && std::isfinite(max_dist), CS_ERR_INVALID, "%s: max_dist must be positive and finite", name);
+  CS_REQUIRE(max_iter >= 0 && max_iter <= 1000, CS_ERR_UNSUPPORTED, "%s: max_iter outside [0, 1000]", name);
   CS_REQUIRE(!std::isnan(relative_fitness) && !std::isnan(relative_rmse), CS_ERR_INVALID,
-             "cs_icp_batch: a convergence threshold is NaN");
+             "%s: a convergence threshold is NaN", name);
   if (n_prob == 0) return CS_OK;
-  CS_REQUIRE(d_T0 && d_T && d_fitness && d_rmse && d_iters && d_ncorr, CS_ERR_INVALID, "cs_icp_batch: NULL argument");
+  CS_REQUIRE(d_T0 && d_T && d_fitness && d_rmse && d_iters && d_ncorr, CS_ERR_INVALID, "%s: NULL argument", name);
   std::vector<IcpProb> probs(n_prob);
   std::vector<IcpWork> work;
   int64_t nt_rows = 0, n_corr_rows = 0;
   double flop = 0.0;
   for (int p = 0; p < n_prob; ++p) {
     const int ss = h_src_seg[p], ts = h_tgt_seg[p];
-    CS_REQUIRE(ss >= 0 && ts >= 0, CS_ERR_INVALID, "cs_icp_batch: negative segment id in problem %d", p);
+    CS_REQUIRE(ss >= 0 && ts >= 0, CS_ERR_INVALID, "%s: negative segment id in problem %d", name, p);
     const int64_t sn = h_soff[ss + 1] - h_soff[ss], tn = h_toff[ts + 1] - h_toff[ts];
-    CS_REQUIRE(sn >= 0 && tn >= 0, CS_ERR_INVALID, "cs_icp_batch: bad segment in problem %d", p);
+    CS_REQUIRE(sn >= 0 && tn >= 0, CS_ERR_INVALID, "%s: bad segment in problem %d", name, p);
     CS_REQUIRE(sn < (1LL << 31) && tn < (1LL << 31), CS_ERR_UNSUPPORTED,
-               "cs_icp_batch: a segment of problem %d has 2^31 rows or more", p);
+               "%s: a segment of problem %d has 2^31 rows or more", name, p);
     IcpProb& pr = probs[p];
     pr.s0 = h_soff[ss];
     pr.t0 = h_toff[ts];
@@ -635,8 +800,9 @@ int cs_icp_batch(const float* d_src, const int64_t* h_soff, const float* d_tgt, 
     n_corr_rows += sn;
     flop += 8.0 * (double)sn * (double)tn;
   }
-  CS_REQUIRE(work.empty() || d_src, CS_ERR_INVALID, "cs_icp_batch: NULL source array");
-  CS_REQUIRE(nt_rows == 0 || d_tgt, CS_ERR_INVALID, "cs_icp_batch: NULL target array");
+  CS_REQUIRE(work.empty() || d_src, CS_ERR_INVALID, "%s: NULL source array", name);
+  CS_REQUIRE(nt_rows == 0 || d_tgt, CS_ERR_INVALID, "%s: NULL target array", name);
+  CS_REQUIRE(EST != ICP_PLANE || nt_rows == 0 || d_tnrm, CS_ERR_INVALID, "%s: NULL target normal array", name);
   hipStream_t s = (hipStream_t)stream;
   pool_use_stream(s);
   const bool use_f16 = !env_first_is("CS_ICP_F16", '0');
@@ -645,18 +811,20 @@ int cs_icp_batch(const float* d_src, const int64_t* h_soff, const float* d_tgt, 
   PoolBuf<IcpProb> dprob;
   PoolBuf<IcpWork> dwork;
   PoolBuf<IcpFrame> frame((size_t)n_prob);
-  PoolBuf<unsigned long long> sums((size_t)n_prob * ICP_NSUM + 2);   // + the two statistics counters
+  PoolBuf<IcpPlaneFrame> pframe;
+  PoolBuf<unsigned long long> sums((size_t)n_prob * NS + 2);   // + the two statistics counters
   PoolBuf<int32_t> done((size_t)n_prob);
-  CS_REQUIRE(frame.p && sums.p && done.p, CS_ERR_HIP, "cs_icp_batch: scratch allocation failed");
+  CS_REQUIRE(frame.p && sums.p && done.p, CS_ERR_HIP, "%s: scratch allocation failed", name);
+  if (EST == ICP_PLANE) CS_REQUIRE(pframe.alloc((size_t)n_prob), CS_ERR_HIP, "%s: scratch allocation failed", name);
   int rc = upload(dprob, probs, s);
   if (!rc) rc = upload(dwork, work, s);
   if (rc) return rc;
-  unsigned long long* dstats = sums.p + (size_t)n_prob * ICP_NSUM;
+  unsigned long long* dstats = sums.p + (size_t)n_prob * NS;
   ProfScope prof("icp", s, flop * (double)(max_iter + 1));
-  CS_HIP_CHECK(hipMemsetAsync(sums.p, 0, sizeof(unsigned long long) * ((size_t)n_prob * ICP_NSUM + 2), s));
+  CS_HIP_CHECK(hipMemsetAsync(sums.p, 0, sizeof(unsigned long long) * ((size_t)n_prob * NS + 2), s));
   const dim3 pgrid((unsigned)ceil_div(n_prob, 64));
   hipLaunchKernelGGL(k_icp_init, pgrid, dim3(64), 0, s, d_T0, n_prob, d_T, d_fitness, d_rmse, d_iters, d_ncorr, done.p);
-  hipLaunchKernelGGL(k_icp_frame, dim3((unsigned)n_prob), dim3(256), 0, s, dprob.p, d_tgt, max_dist, frame.p);
+  hipLaunchKernelGGL(k_icp_frame, dim3((unsigned)n_prob), dim3(256), 0, s, dprob.p, d_tgt, max_dist, frame.p, pframe.p);
   // the targets do not move: one image for every round
   PoolBuf<_Float16> img16;
   PoolBuf<float> tn16;
@@ -668,7 +836,7 @@ int cs_icp_batch(const float* d_src, const int64_t* h_soff, const float* d_tgt, 
     tn16.alloc((size_t)n_pad);
     t4f.alloc((size_t)(nt_rows ? nt_rows : 1));
     wflag.alloc(n_work);
-    CS_REQUIRE(img16.p && tn16.p && t4f.p && wflag.p, CS_ERR_HIP, "cs_icp_batch: scratch allocation failed");
+    CS_REQUIRE(img16.p && tn16.p && t4f.p && wflag.p, CS_ERR_HIP, "%s: scratch allocation failed", name);
     chamfer_pack16(d_tgt, nt_rows, n_pad, img16.p, tn16.p, t4f.p, s);
   }
   CS_LAUNCH_CHECK();
@@ -679,18 +847,20 @@ int cs_icp_batch(const float* d_src, const int64_t* h_soff, const float* d_tgt, 
   for (int round = 0; round <= max_iter; ++round) {
     if (n_work) {
       if (use_f16) {
-        hipLaunchKernelGGL(k_icp_f16, dim3(n_work), dim3(256), 0, s, dwork.p, dprob.p, d_src, t4f.p, img16.p, tn16.p,
-                           (const double*)d_T, frame.p, done.p, crit.thr2, sums.p, d_corr, wflag.p,
+        hipLaunchKernelGGL(k_icp_f16<EST>, dim3(n_work), dim3(256), 0, s, dwork.p, dprob.p, d_src, t4f.p, img16.p, tn16.p,
+                           d_tnrm, (const double*)d_T, frame.p, pframe.p, done.p, crit.thr2, sums.p, d_corr, wflag.p,
                            want_stats ? dstats : (unsigned long long*)nullptr);
-        hipLaunchKernelGGL(k_icp_exact, dim3(n_work), dim3(256), 0, s, dwork.p, dprob.p, d_src, d_tgt, (const double*)d_T,
-                           frame.p, done.p, crit.thr2, sums.p, d_corr, (const int32_t*)wflag.p);
+        hipLaunchKernelGGL(k_icp_exact<EST>, dim3(n_work), dim3(256), 0, s, dwork.p, dprob.p, d_src, d_tgt, d_tnrm,
+                           (const double*)d_T, frame.p, pframe.p, done.p, crit.thr2, sums.p, d_corr,
+                           (const int32_t*)wflag.p);
       } else {
-        hipLaunchKernelGGL(k_icp_exact, dim3(n_work), dim3(256), 0, s, dwork.p, dprob.p, d_src, d_tgt, (const double*)d_T,
-                           frame.p, done.p, crit.thr2, sums.p, d_corr, (const int32_t*)nullptr);
+        hipLaunchKernelGGL(k_icp_exact<EST>, dim3(n_work), dim3(256), 0, s, dwork.p, dprob.p, d_src, d_tgt, d_tnrm,
+                           (const double*)d_T, frame.p, pframe.p, done.p, crit.thr2, sums.p, d_corr,
+                           (const int32_t*)nullptr);
       }
     }
-    hipLaunchKernelGGL(k_icp_step, pgrid, dim3(64), 0, s, dprob.p, n_prob, frame.p, crit, round, round == max_iter ? 1 : 0,
-                       sums.p, done.p, d_T, d_T32, d_fitness, d_rmse, d_iters, d_ncorr);
+    hipLaunchKernelGGL(k_icp_step<EST>, pgrid, dim3(64), 0, s, dprob.p, n_prob, frame.p, pframe.p, crit, round,
+                       round == max_iter ? 1 : 0, sums.p, done.p, d_T, d_T32, d_fitness, d_rmse, d_iters, d_ncorr);
   }
   CS_LAUNCH_CHECK();
   if (want_stats) {
@@ -701,6 +871,34 @@ int cs_icp_batch(const float* d_src, const int64_t* h_soff, const float* d_tgt, 
     g_icp_stats[1] += h[1];
   }
   return CS_OK;
+}
+
+}  // namespace
+}  // namespace cs
+
+using namespace cs;
+
+extern "C" {
+
+void cs_icp_stats(uint64_t out[2], int reset) { read_stats(g_icp_stats, out, reset); }
+
+int cs_icp_batch(const float* d_src, const int64_t* h_soff, const float* d_tgt, const int64_t* h_toff,
+                 const int32_t* h_src_seg, const int32_t* h_tgt_seg, int n_prob, const float* d_T0, double max_dist,
+                 int max_iter, double relative_fitness, double relative_rmse, double* d_T, float* d_T32,
+                 double* d_fitness, double* d_rmse, int32_t* d_iters, int32_t* d_ncorr, int32_t* d_corr, void* stream) {
+  return icp_run<ICP_POINT>("cs_icp_batch", d_src, h_soff, d_tgt, nullptr, h_toff, h_src_seg, h_tgt_seg, n_prob, d_T0,
+                            max_dist, max_iter, relative_fitness, relative_rmse, d_T, d_T32, d_fitness, d_rmse, d_iters,
+                            d_ncorr, d_corr, stream);
+}
+
+int cs_icp_plane_batch(const float* d_src, const int64_t* h_soff, const float* d_tgt, const float* d_tgt_normal,
+                       const int64_t* h_toff, const int32_t* h_src_seg, const int32_t* h_tgt_seg, int n_prob,
+                       const float* d_T0, double max_dist, int max_iter, double relative_fitness, double relative_rmse,
+                       double* d_T, float* d_T32, double* d_fitness, double* d_rmse, int32_t* d_iters, int32_t* d_ncorr,
+                       int32_t* d_corr, void* stream) {
+  return icp_run<ICP_PLANE>("cs_icp_plane_batch", d_src, h_soff, d_tgt, d_tgt_normal, h_toff, h_src_seg, h_tgt_seg, n_prob,
+                            d_T0, max_dist, max_iter, relative_fitness, relative_rmse, d_T, d_T32, d_fitness, d_rmse,
+                            d_iters, d_ncorr, d_corr, stream);
 }
 
 }  // extern "C"

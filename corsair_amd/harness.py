@@ -44,19 +44,36 @@ class Config:
     # apart that NOBODY HAS TUNED; set it explicitly for real data
     icp_max_iter: int = 0
     icp_max_dist: float = 0.0
+    # "point" (cs_icp_batch) or "plane" (cs_icp_plane_batch on the normals of the CAD voxels, cs_estimate_normals over
+    # icp_normal_k neighbours).  16 is UNTUNED: 8 and 16 behaved alike in the experiment that motivated it
+    icp_estimation: str = "point"
+    icp_normal_k: int = 16
 
     def icp_distance(self):
         return self.icp_max_dist if self.icp_max_dist > 0 else 2.0 * self.voxel_size
+
+    def check_icp(self):
+        if self.icp_estimation not in ("point", "plane"):
+            raise ValueError("Config.icp_estimation must be 'point' or 'plane', got %r" % (self.icp_estimation,))
+        if not 3 <= int(self.icp_normal_k) <= 32:
+            raise ValueError("Config.icp_normal_k must lie in [3, 32], got %r" % (self.icp_normal_k,))
+
+    def icp_plane(self):
+        """True when the run refines with the point-to-plane estimation (and so needs the CAD voxels' normals)."""
+        self.check_icp()
+        return self.icp_max_iter > 0 and self.icp_estimation == "plane"
 
 
 @dataclass
 class EmbeddedSet:
     """Features of a set of clouds, packed: voxel features F [sumN,16], origins [sumN,3], offsets
-    (host list, len n+1), global descriptors [n,256] (row-normalised)."""
+    (host list, len n+1), global descriptors [n,256] (row-normalised); optionally the normals [sumN,3] of the origins
+    (backend.estimate_normals; the point-to-plane refinement's targets carry them)."""
     F: torch.Tensor
     origin: torch.Tensor
     offsets: list
     desc: torch.Tensor
+    normal: torch.Tensor = None
 
     def __len__(self):
         return len(self.offsets) - 1
@@ -72,7 +89,8 @@ class EmbeddedSet:
         rows = torch.arange(int(new_off[-1]), device=dev) + torch.repeat_interleave(
             starts, torch.from_numpy(lens).to(dev), output_size=int(new_off[-1]))
         return EmbeddedSet(self.F[rows], self.origin[rows], new_off.tolist(),
-                           self.desc[torch.from_numpy(ids).to(dev)])
+                           self.desc[torch.from_numpy(ids).to(dev)],
+                           None if self.normal is None else self.normal[rows])
 
 
 class Pipeline:
@@ -164,15 +182,24 @@ class Pipeline:
         return R.sym_pose_batch(queries.F, queries.origin, queries.offsets, cads.F, cads.origin,
                                 cads.offsets, syms, c.k_nn, c.max_corr, 0, anchor_ids, 100,
                                 c.ransac_max_iter, c.ransac_confidence, use_symmetry, force_gate,
-                                query_anchors, c.icp_max_iter, c.icp_distance() if c.icp_max_iter > 0 else None)
+                                query_anchors, c.icp_max_iter, c.icp_distance() if c.icp_max_iter > 0 else None,
+                                c.icp_estimation, c.icp_normal_k, cads.normal)
+
+    def with_normals(self, s):
+        """`s` with the normals of its origins (one cs_estimate_normals call over the whole set) when the configuration
+        refines point-to-plane and the set has none yet; `s` itself otherwise."""
+        if not self.cfg.icp_plane() or s.normal is not None:
+            return s
+        return EmbeddedSet(s.F, s.origin, s.offsets, s.desc, B.estimate_normals(s.origin, s.offsets, self.cfg.icp_normal_k))
 
 
 def concat_sets(sets):
     off = [0]
     for s in sets:
         off += [o + off[-1] for o in s.offsets[1:]]
+    normal = torch.cat([s.normal for s in sets]) if sets and all(s.normal is not None for s in sets) else None
     return EmbeddedSet(torch.cat([s.F for s in sets]), torch.cat([s.origin for s in sets]), off,
-                       torch.cat([s.desc for s in sets]))
+                       torch.cat([s.desc for s in sets]), normal)
 
 
 # ---- metric aggregation (evaluation.py:334-383) -----------------------------------------------------
@@ -333,6 +360,8 @@ def register_queries(pipe, qs, query_ids, cat, pos_idx, syms, base_T, lib_T, for
     bs = batch_size or pipe.cfg.batch_size
     query_ids = np.asarray(query_ids, dtype=np.int64)
     icp_on = getattr(pipe.cfg, "icp_max_iter", 0) > 0
+    if icp_on and len(query_ids) and hasattr(pipe, "with_normals"):
+        cat = pipe.with_normals(cat)     # point-to-plane: the catalog's normals once per evaluation, gathered per batch
     names = C_.NAMES + (C_.ICP_NAMES if icp_on else ())
     dtypes = dict(C_.DTYPES, **C_.ICP_DTYPES)
     if not len(query_ids):
@@ -524,6 +553,10 @@ def build_parser():
                     help="refine every kept pose with at most N point-to-point ICP updates (0 = off, the reference's behaviour)")
     ap.add_argument("--icp-max-dist", type=float, default=0.0,
                     help="ICP correspondence distance; 0 = 2 * voxel size (an untuned default)")
+    ap.add_argument("--icp-estimation", default="point", choices=["point", "plane"],
+                    help="ICP estimation: point-to-point, or point-to-plane on the CAD voxels' normals")
+    ap.add_argument("--icp-normal-k", type=int, default=16,
+                    help="neighbours of a CAD voxel's normal for --icp-estimation plane, 3..32 (an untuned default)")
     ap.add_argument("--in-flight", type=int, default=3, help="registration batches in flight (host threads x HIP streams)")
     ap.add_argument("--device", default="cuda", choices=["cuda"], help="there is no CPU path")
     return ap
@@ -544,7 +577,9 @@ def main(argv=None):
     if esd is None:
         raise SystemExit("checkpoint has no embedding_state_dict: retrieval needs the descriptor head (evaluation.py:199)")
     cfg = Config(n_points=a.n_points, batch_size=a.batch_size, embed_batch_size=a.embed_batch_size,
-                 ransac_max_iter=a.ransac_max_iter, icp_max_iter=a.icp_iters, icp_max_dist=a.icp_max_dist)
+                 ransac_max_iter=a.ransac_max_iter, icp_max_iter=a.icp_iters, icp_max_dist=a.icp_max_dist,
+                 icp_estimation=a.icp_estimation, icp_normal_k=a.icp_normal_k)
+    cfg.check_icp()
     pipe = Pipeline(sd, esd, device=a.device, config=cfg)
     cad_names, catalog = load_cloud_dir(a.catalog_dir, a.n_points, "catalog")
     _, queries = load_cloud_dir(a.query_dir, a.n_points, "queries")

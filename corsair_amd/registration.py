@@ -150,7 +150,8 @@ def part_configs(K, pos_sym):
 
 def sym_pose_batch(baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_nn=5, max_corr=0.20, seed=0,
                    anchor_ids=None, n_anchor=100, max_iter=100000, confidence=0.999,
-                   use_symmetry=True, force_gate=False, query_anchors=None, icp_max_iter=0, icp_max_dist=None):
+                   use_symmetry=True, force_gate=False, query_anchors=None, icp_max_iter=0, icp_max_dist=None,
+                   icp_estimation="point", icp_normal_k=16, normals1=None):
     """baseF f32 [N0,16], xyz0 f32 [N0,3] (query voxels of all pairs, segment p = off0[p]:off0[p+1]);
     posF/xyz1/off1 likewise for the CAD side; pos_syms: symmetry label per pair.
     anchor_ids[p] = (counter0, counter1) seeds the anchor draw of pair p (default (2p, 2p+1)).
@@ -159,7 +160,12 @@ def sym_pose_batch(baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_nn=5, max_co
     ~1 ms of host work would otherwise sit between the 5-NN and the part-cut launches.
     icp_max_iter > 0: T_best of every pair is refined by point-to-point ICP (cs_icp_batch: source = the query's voxels,
     target = the CAD's voxels, the direction of stage 5; correspondence distance icp_max_dist, required then) and the
-    result's T_icp / cd_icp / icp_* fields are filled; with the default 0 nothing is launched."""
+    result's T_icp / cd_icp / icp_* fields are filled; with the default 0 nothing is launched.
+    icp_estimation = "plane": the refinement is point-to-plane (cs_icp_plane_batch) on the normals of the CAD voxels,
+    normals1 f32 [N1,3] when the caller has them (a catalog's are computed once), else cs_estimate_normals over
+    icp_normal_k neighbours here; the same result fields are filled."""
+    if icp_estimation not in ("point", "plane"):
+        raise ValueError("sym_pose_batch: icp_estimation must be 'point' or 'plane', got %r" % (icp_estimation,))
     if icp_max_iter > 0 and not (icp_max_dist is not None and icp_max_dist > 0):
         raise ValueError("sym_pose_batch: icp_max_iter > 0 needs a positive icp_max_dist")
     dev = baseF.device
@@ -317,7 +323,10 @@ def sym_pose_batch(baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_nn=5, max_co
     # ---- 7. optional refinement of the kept estimate on the geometry itself (Open3D: registration_icp) ----
     if icp_max_iter > 0:
         pairs = list(range(P))
-        r = B.icp_batch(xyz0, off0, xyz1, off1, pairs, pairs, res.T_best, icp_max_dist, icp_max_iter)
+        nrm = None
+        if icp_estimation == "plane":
+            nrm = normals1 if normals1 is not None else B.estimate_normals(xyz1, off1, icp_normal_k)
+        r = B.icp_batch(xyz0, off0, xyz1, off1, pairs, pairs, res.T_best, icp_max_dist, icp_max_iter, tgt_normals=nrm)
         res.T_icp, res.icp_fitness, res.icp_rmse, res.icp_iters = r.T32, r.fitness, r.rmse, r.iters
         res.cd_icp = B.chamfer_1dir(xyz0, off0, xyz1, off1, pairs, pairs, r.T32)
     return res

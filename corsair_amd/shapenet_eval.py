@@ -32,6 +32,16 @@ class Config:
     symmetry_cd_threshold: float = 0.1
     ransac_max_iter: int = 100000
     ransac_confidence: float = 0.999
+    # ICP refinement of the kept pose (registration.sym_pose_batch): updates at most, 0 = off (the reference's behaviour);
+    # icp_max_dist = 0.0 means 2 * voxel_size (untuned, as in harness.Config); "point" or "plane" (normals over
+    # icp_normal_k neighbours of the posed copy's voxels, untuned)
+    icp_max_iter: int = 0
+    icp_max_dist: float = 0.0
+    icp_estimation: str = "point"
+    icp_normal_k: int = 16
+
+    def icp_distance(self):
+        return self.icp_max_dist if self.icp_max_dist > 0 else 2.0 * self.voxel_size
 
 
 def load_pc(pc):
@@ -109,8 +119,10 @@ def get_symmetry_label(pc, cd_threshold):
 
 def evaluate(pipe, clouds, cfg=None, pairs_per_batch=16, seed=None, force_gate=False):
     """clouds: list of raw [n,3] arrays.  Returns a list of result dicts (one per model x pose) with
-    the keys of registration_worker (evaluation-shapenet.py:242-275)."""
+    the keys of registration_worker (evaluation-shapenet.py:242-275); with cfg.icp_max_iter > 0 also T_est_icp, rte_icp,
+    rre_icp, chamfer_dist_icp and icp_iters of the refined pose."""
     cfg = cfg or Config()
+    icp_on = cfg.icp_max_iter > 0
     rng = np.random.default_rng(cfg.random_seed if seed is None else seed)
     dev = pipe.device
     jobs = []
@@ -138,7 +150,9 @@ def evaluate(pipe, clouds, cfg=None, pairs_per_batch=16, seed=None, force_gate=F
         res = R.sym_pose_batch(base.F, base.origin, base.offsets, posed.F, posed.origin, posed.offsets,
                                labels, cfg.k_nn, cfg.max_corr, 0,
                                [(2 * (s + i), 2 * (s + i) + 1) for i in range(P)], 100,
-                               cfg.ransac_max_iter, cfg.ransac_confidence, True, force_gate)
+                               cfg.ransac_max_iter, cfg.ransac_confidence, True, force_gate, None,
+                               cfg.icp_max_iter, cfg.icp_distance() if icp_on else None, cfg.icp_estimation,
+                               cfg.icp_normal_k)
         Tb, Tr = res.T_best.cpu().numpy(), res.T_ransac.cpu().numpy()
         cdb, cdr = res.cd_best.cpu().numpy(), res.cd_ransac.cpu().numpy()
         for i, (mi, pi, _, _, pose, label) in enumerate(chunk):
@@ -148,13 +162,23 @@ def evaluate(pipe, clouds, cfg=None, pairs_per_batch=16, seed=None, force_gate=F
                                 T_est_sym=Tb[i], chamfer_dist_sym=float(cdb[i]), T_est_ransac=Tr[i],
                                 chamfer_dist_ransac=float(cdr[i]), rte_sym=float(rte_s), rre_sym=float(rre_s),
                                 rte_ransac=float(rte_r), rre_ransac=float(rre_r), pose_gt=pose))
+        if icp_on:
+            Ti, cdi, iti = res.T_icp.cpu().numpy(), res.cd_icp.cpu().numpy(), res.icp_iters.cpu().numpy()
+            for i, (_, _, _, _, pose, label) in enumerate(chunk):
+                rte_i, rre_i = eval_pose(Ti[i], np.eye(4), pose, axis_symmetry=label)
+                results[s + i].update(T_est_icp=Ti[i], chamfer_dist_icp=float(cdi[i]), rte_icp=float(rte_i),
+                                      rre_icp=float(rre_i), icp_iters=int(iti[i]))
     return results
+
+
+def _has_icp(results):
+    return bool(results) and "rre_icp" in results[0]
 
 
 def threshold_table(results, rre_deg=(5, 15, 45), rte=(0.02, 0.05, 0.10, 0.15)):
     """compute_metrics_shapenet.py-style summary: fraction of cases under each threshold."""
     out = {}
-    for tag in ("ransac", "sym"):
+    for tag in ("ransac", "sym") + (("icp",) if _has_icp(results) else ()):
         r = np.array([x[f"rre_{tag}"] for x in results])
         t = np.array([x[f"rte_{tag}"] for x in results])
         out[tag] = {**{f"rre<={d}": float(np.mean(r <= np.deg2rad(d))) for d in rre_deg},
@@ -165,28 +189,35 @@ def threshold_table(results, rre_deg=(5, 15, 45), rte=(0.02, 0.05, 0.10, 0.15)):
 # ---- file-level entry: `python -m corsair_amd.shapenet_eval` (evaluation-shapenet.py:158-240,277-380) ---------------------
 CSV_COLUMNS = ("model", "pose_idx", "symmetry_label", "sym_success", "rte_sym", "rre_sym", "cd_sym", "rte_ransac",
                "rre_ransac", "cd_ransac")            # evaluation-shapenet.py:323-334
+ICP_CSV_COLUMNS = ("rte_icp", "rre_icp", "cd_icp", "icp_iters")      # trailing, only when the refinement ran
 
 
 def write_results(results, names, csv_file, npz_file):
     """results-*.csv with the reference's columns and poses-*.npz with poses_gt / poses_pred_sym / poses_pred_ransac
-    (evaluation-shapenet.py:345-380)."""
+    (evaluation-shapenet.py:345-380); results of a run with ICP refinement add the trailing ICP_CSV_COLUMNS and
+    poses_pred_icp."""
     import csv
 
+    icp = _has_icp(results)
     with open(csv_file, "w", newline="") as f:
         w = csv.writer(f)
-        w.writerow(CSV_COLUMNS)
+        w.writerow(CSV_COLUMNS + (ICP_CSV_COLUMNS if icp else ()))
         for r in results:
             w.writerow([names[r["model"]], r["pose_idx"], r["symmetry_label"], r["sym_success"], r["rte_sym"], r["rre_sym"],
-                        r["chamfer_dist_sym"], r["rte_ransac"], r["rre_ransac"], r["chamfer_dist_ransac"]])
+                        r["chamfer_dist_sym"], r["rte_ransac"], r["rre_ransac"], r["chamfer_dist_ransac"]] +
+                       ([r["rte_icp"], r["rre_icp"], r["chamfer_dist_icp"], r["icp_iters"]] if icp else []))
+    extra = {"poses_pred_icp": np.stack([r["T_est_icp"] for r in results])} if icp else {}
     with open(npz_file, "wb") as f:
         np.savez(f, poses_gt=np.stack([r["pose_gt"] for r in results]),
                  poses_pred_sym=np.stack([r["T_est_sym"] for r in results]),
-                 poses_pred_ransac=np.stack([r["T_est_ransac"] for r in results]))
+                 poses_pred_ransac=np.stack([r["T_est_ransac"] for r in results]), **extra)
 
 
 def summary(results):
-    """The three lines evaluation-shapenet.py:226-234 prints."""
-    r = {k: np.asarray([x[k] for x in results]) for k in ("rte_sym", "rte_ransac", "rre_sym", "rre_ransac")}
+    """The three lines evaluation-shapenet.py:226-234 prints; each gains an `icp` entry when the refinement ran."""
+    icp = _has_icp(results)
+    r = {k: np.asarray([x[k] for x in results])
+         for k in ("rte_sym", "rte_ransac", "rre_sym", "rre_ransac") + (("rte_icp", "rre_icp") if icp else ())}
     n, five = len(results), np.deg2rad(5)
     lines = []
     for title, fs, fr in (("RTE <= 0.02", r["rte_sym"] <= 0.02, r["rte_ransac"] <= 0.02),
@@ -194,6 +225,10 @@ def summary(results):
                           ("RTE <= 0.02 & RRE <= 5 deg", (r["rte_sym"] <= 0.02) & (r["rre_sym"] <= five),
                            (r["rte_ransac"] <= 0.02) & (r["rre_ransac"] <= five))):
         lines.append(f"{title}: sym: {fs.sum() / n:.4f}, ransac: {fr.sum() / n:.4f}")
+    if icp:
+        ti, ri = r["rte_icp"] <= 0.02, r["rre_icp"] <= five
+        for i, f in enumerate((ti, ri, ti & ri)):
+            lines[i] += f", icp: {f.sum() / n:.4f}"
     return "\n".join(lines)
 
 
@@ -219,6 +254,11 @@ def main(argv=None):
     ap.add_argument("--model-ckpt", "--ckpt", required=True, dest="ckpt")
     ap.add_argument("--random-seed", type=int, default=0)
     ap.add_argument("--ransac-max-iter", type=int, default=100000)
+    ap.add_argument("--icp-iters", type=int, default=0,
+                    help="refine every kept pose with at most N ICP updates (0 = off, the reference's behaviour)")
+    ap.add_argument("--icp-max-dist", type=float, default=0.0, help="ICP correspondence distance; 0 = 2 * voxel size")
+    ap.add_argument("--icp-estimation", default="point", choices=["point", "plane"])
+    ap.add_argument("--icp-normal-k", type=int, default=16)
     ap.add_argument("--out-dir", default=".")
     ap.add_argument("--device", default="cuda", choices=["cuda"])
     a = ap.parse_args(argv)
@@ -235,7 +275,8 @@ def main(argv=None):
     pipe = harness.Pipeline(sd, esd, device=a.device)
     cfg = Config(random_seed=a.random_seed, n_poses_per_model=a.n_poses_per_model, max_roll_deg=a.max_roll_deg,
                  max_pitch_deg=a.max_pitch_deg, max_yaw_deg=a.max_yaw_deg, max_translation=a.max_translation,
-                 ransac_max_iter=a.ransac_max_iter)
+                 ransac_max_iter=a.ransac_max_iter, icp_max_iter=a.icp_iters, icp_max_dist=a.icp_max_dist,
+                 icp_estimation=a.icp_estimation, icp_normal_k=a.icp_normal_k)
     results = evaluate(pipe, clouds, cfg)
     postfix = f"shapenet-seed{a.random_seed}-{a.category}-{len(files)}-{a.n_poses_per_model}"
     os.makedirs(a.out_dir, exist_ok=True)

@@ -533,10 +533,81 @@ int cs_icp_batch(const float* d_src, const int64_t* h_soff, const float* d_tgt, 
 void cs_icp_stats(uint64_t out[2], int reset);
 
 /* ------------------------------------------------------------------------------------------
+ * cs_icp_plane_batch: cs_icp_batch with Open3D's TransformationEstimationPointToPlane in the place of the point-to-point
+ * estimation (tests/icp_plane_ref.py restates it bit for bit).  The arguments are those of cs_icp_batch plus
+ * d_tgt_normal f32 [rows of d_tgt, 3], the normal of every target row (cs_estimate_normals, or the caller's own; they need
+ * not be unit vectors and their sign does not matter).  Problems, pose chain, association (both paths, the strict
+ * voucher, CS_ICP_F16, CS_ICP_STATS / cs_icp_stats), evaluation (rmse from the POINT distances d2, as [O3D-knowledge]
+ * Open3D's evaluation has it for every estimation), loop, stop rule, outputs, independence, empty-segment answers, refusals
+ * (+ a NULL d_tgt_normal while a target row exists) and stream behaviour are those of cs_icp_batch: the same code.  What
+ * differs is the sums and the update.
+ *   Per kept pair, with o, M, eM, eN of cs_icp_batch: p' = p - o, n = (double) normal row of the matched target,
+ *     e = p - q, r = fma(e_z, n_z, fma(e_y, n_y, e_x * n_x)), a = p' x n with a_x = fma(p'_y, n_z, -(p'_z * n_y)),
+ *     a_y = fma(p'_z, n_x, -(p'_x * n_z)), a_z = fma(p'_x, n_y, -(p'_y * n_x)), J = (a_x, a_y, a_z, n_x, n_y, n_z).
+ *   Sums: 29 signed 64-bit integers: count; I((J_i * J_j) * 2^s) for i <= j, row-major (21); I((J_i * r) * 2^s) (6);
+ *     I(d2 * 2^s2).  Each product is rounded to f64 first; I clamps to +-2^(61 - eN) and truncates.  With b = 61 - eN the
+ *     exponents s are, for i, j < 3 (rot x rot) b - 2 eM - 3, for i < 3 <= j (rot x trans) b - eM - 2, for 3 <= i, j
+ *     (trans x trans) b - 1, for J_i r with i < 3 b - 2 eM - 2 and with i >= 3 b - eM - 1: a kept pair has |p'_c| <= M,
+ *     |r| < max_dist <= M and, for unit normals, |n_c| <= 1, each class carries one bit for the roundings, no term reaches
+ *     the clamp and no sum leaves 2^61; the clamp keeps that true for any normals.
+ *   Update: A_ij = (double)sum * 2^-s (symmetric 6x6), b_i likewise; A x = -b by an unpivoted Cholesky, columns j = 0..5:
+ *       d = A_jj, then d = fma(-L_jk, L_jk, d) for k < j;  L_jj = sqrt(d);
+ *       L_ij (i > j) = (A_ij, then fma(-L_ik, L_jk, .) for k < j) / L_jj;
+ *       y_i = (-b_i, then fma(-L_ik, y_k, .) for k < i) / L_ii;   x_i (i = 5..0) = (y_i, then fma(-L_ki, x_k, .) for
+ *       k = i+1..5) / L_ii.
+ *     The quaternion (1, 0.5 x_0, 0.5 x_1, 0.5 x_2) is normalised by division and turned into R as in cs_ransac_batch (the
+ *     Cayley rotation; [O3D-knowledge] Open3D composes Rz Ry Rx of the three solved angles and solves by LDLT);
+ *     t_a = (x_(3+a) + o_a) - fma(R_a2, o_2, fma(R_a1, o_1, R_a0 * o_0));  T <- U T by cs_icp_batch's chain.
+ *   A problem stops at once, keeping T, when an evaluation has n_corr < 6 (3 for cs_icp_batch) or a non-finite value, when
+ *     a pivot d is not finite or not greater than 2^-30 * A_jj, or when the update would make T non-finite.
+ * Profile family "icp".
+ * ---------------------------------------------------------------------------------------- */
+int cs_icp_plane_batch(const float* d_src, const int64_t* h_soff, const float* d_tgt, const float* d_tgt_normal,
+                       const int64_t* h_toff, const int32_t* h_src_seg, const int32_t* h_tgt_seg, int n_prob,
+                       const float* d_T0, double max_dist, int max_iter, double relative_fitness, double relative_rmse,
+                       double* d_T, float* d_T32, double* d_fitness, double* d_rmse, int32_t* d_iters, int32_t* d_ncorr,
+                       int32_t* d_corr, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * cs_estimate_normals: one surface normal per row from the k nearest rows of the row's own segment, the semantics of
+ * [O3D-knowledge] Open3D's PointCloud::estimate_normals(KDTreeSearchParamKNN(k)): the eigenvector of the smallest
+ * eigenvalue of the neighbourhood's covariance.  The reference has no such step, so this comment is the specification
+ * (tests/normals_ref.py restates it bit for bit).  Every operation is ONE IEEE f64 operation or an explicit fma; nothing is
+ * contracted; only + - * / sqrt fma appear (no transcendental function, so a Python restatement can match every bit).
+ *   d_xyz f32 [n,3]; h_off int64 [n_seg + 1] host offsets; d_normal f32 [n,3].
+ *   Neighbours of row i of a segment of sn rows: the m = min(k, sn) rows j of the SAME segment with the smallest
+ *     (d2, j), d2 = fma(dz, dz, fma(dy, dy, dx * dx)), d. = (double)x_j. - (double)x_i., ties to the smaller row, the row
+ *     itself included ([O3D-knowledge]: a k-NN query of a cloud's own point returns that point first).  A row whose d2 is
+ *     NaN or +inf is never a neighbour, so fewer than m may be found; m' = the number found.  k in [3, 32].
+ *   m' < 3: the normal is (0, 0, 1) ([O3D-knowledge]: Open3D's answer for fewer than three neighbours).
+ *   Scatter matrix about the query row, over the neighbours in (d2, j) order: u = (double)x_j - (double)x_i;
+ *     s_a = s_a + u_a;  C_ab = fma(u_a, u_b, C_ab) (a <= b);  then S_ab = fma(-(s_a / m'), s_b, C_ab) (a <= b, mirrored).
+ *     ([O3D-knowledge]: Open3D accumulates the raw second moments about the origin; about the query row the cancellation
+ *     is between neighbour-sized numbers.)
+ *   Eigenvector: jacobi3 (corsair_amd/csrc/horn.h: cyclic Jacobi, 5 sweeps, jacobi4's rotation) on S; the column of the
+ *     smallest diagonal entry, ties to the smaller column; divided by sqrt(fma(e_z, e_z, fma(e_y, e_y, e_x * e_x))); negated
+ *     when its component of largest magnitude (the first such on ties) is negative ([O3D-knowledge]: Open3D leaves the sign
+ *     to a later orientation step; point-to-plane ICP does not see it).  A non-finite S, a zero or non-finite length or a
+ *     non-finite component gives (0, 0, 1).  One cast to f32.
+ *     Exactly degenerate inputs have defined answers: rows of one plane z = const give (0, 0, 1); rows of one line along x
+ *     give (0, 1, 0) (two zero eigenvalues, the smaller column); m' copies of one point give (1, 0, 0).
+ *   Independence: a row's normal depends on its segment alone -- not on batch neighbours, the launch shape or the run --
+ *     and on the ORDER of the rows inside the segment only through exact distance ties (which tied row enters the list, and
+ *     the order of the sums among tied rows).
+ *   n_seg = 0 and empty segments are legal.  Refused (CS_ERR_INVALID): a NULL offset table, a negative count, offsets that
+ *     decrease, NULL d_xyz or d_normal while a row exists; (CS_ERR_UNSUPPORTED): k outside [3, 32], a segment of 2^31 rows
+ *     or more.  (cs_knn_feat cannot serve this: its KNN_MAXK is 8, and it ranks features, not coordinates.)
+ *   Path: the exhaustive f64 scan of the row's own segment, staged through LDS, one thread per row with its neighbour list
+ *     in registers.  One launch on `stream`, no host wait, no atomics.
+ * Profile family "normals".
+ * ---------------------------------------------------------------------------------------- */
+int cs_estimate_normals(const float* d_xyz, const int64_t* h_off, int n_seg, int k, float* d_normal, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Profiling hooks for bench.py: when enabled the library brackets the launches of each named
  * kernel family with hipEvents on the launch stream and accumulates the elapsed time.
  * names: "conv", "ransac_eval", "ransac_pre", "ransac_hyp", "knn", "chamfer", "topk", "symcut",
- * "kmap", "loss", "hardneg", "icp".
+ * "kmap", "loss", "hardneg", "icp", "normals".
  * ---------------------------------------------------------------------------------------- */
 void cs_prof_enable(int on);
 void cs_prof_reset(void);

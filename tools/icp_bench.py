@@ -13,6 +13,11 @@ warm-up, device events (wall time next to it):
 Also the updates (a) and (b) actually applied, the share of workgroups the f16 association handed to the exhaustive kernel
 (CS_ICP_STATS=1, a run of its own), the library's own time of the call (profile family "icp"), and -- information only --
 one registration step (embed 32 queries, sym_pose_batch against their CADs) with icp_max_iter = 0 and 30 in this process.
+
+`--estimation plane` measures instead, alternating in one process and on the same clouds: (a) the point call
+above, (p) the point-to-plane call (cs_icp_plane_batch) with the target normals supplied, (n) backend.estimate_normals of
+the 32 targets over --normal-k neighbours; with the updates per problem, the time per round, the fallback share and the
+pose errors of both.  `--start large` is the 12 degree / 5 cm start with max_dist 0.12 (default: 3 degrees / 1 cm, 0.06).
 Prints one JSON line."""
 import argparse
 import json
@@ -126,6 +131,58 @@ def torch_icp(x0, off0, x1, off1, T0, max_dist, max_iter, rf=1e-6, rr=1e-6):
     return T, iters.tolist()
 
 
+def timed_alternating(fns, reps, warmup=3):
+    """Median device ms of every function of `fns`, the calls interleaved a, b, c, a, b, c, ... in this process."""
+    for _ in range(warmup):
+        for fn in fns.values():
+            fn()
+    ms = {k: [] for k in fns}
+    for _ in range(reps):
+        for k, fn in fns.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ms[k].append(e0.elapsed_time(e1))
+    return {k: round(float(np.median(v)), 4) for k, v in ms.items()}
+
+
+def plane_report(a, res, x0, off0, x1, off1, T0, truth, max_dist):
+    """The measurement of DESIGN 13: (a) point, (p) plane with normals supplied, (n) the normals of the targets."""
+    pairs = list(range(N_PAIRS))
+    nrm = B.estimate_normals(x1, off1, a.normal_k)
+    fns = {"point": lambda: B.icp_batch(x0, off0, x1, off1, pairs, pairs, T0, max_dist, MAX_ITER),
+           "plane": lambda: B.icp_batch(x0, off0, x1, off1, pairs, pairs, T0, max_dist, MAX_ITER, tgt_normals=nrm),
+           "normals": lambda: B.estimate_normals(x1, off1, a.normal_k)}
+    ms = timed_alternating(fns, a.reps)
+    res.update({"estimation": "plane", "normal_k": a.normal_k, "icp_point_ms": ms["point"], "icp_plane_ms": ms["plane"],
+                "normals_ms": ms["normals"], "plane_over_point": round(ms["plane"] / ms["point"], 4),
+                "bar_plane_le_point": bool(ms["plane"] <= ms["point"])})
+
+    def errs(T):
+        T = T.cpu().numpy().astype(np.float64)
+        rre = [np.degrees(np.arccos(np.clip((np.trace(T[p, :3, :3] @ truth[p, :3, :3].T) - 1) / 2, -1, 1))) for p in pairs]
+        rte = [np.linalg.norm(T[p, :3, 3] - truth[p, :3, 3]) for p in pairs]
+        return round(float(np.mean(rre)), 4), round(float(np.mean(rte)), 5)
+
+    res["rre_deg_rte_before"] = errs(T0)
+    os.environ["CS_ICP_STATS"] = "1"
+    for k in ("point", "plane"):
+        B.icp_stats(reset=True)
+        r = fns[k]()
+        st = B.icp_stats(reset=True)
+        it = r.iters.cpu().numpy()
+        res["updates_" + k] = {"mean": round(float(it.mean()), 2), "min": int(it.min()), "max": int(it.max())}
+        res["icp_%s_ms_per_round" % k] = round(ms[k] / (float(it.max()) + 1), 4)
+        res["fallback_share_" + k] = round(st[1] / max(st[0], 1), 5)
+        res["rre_deg_rte_after_" + k] = errs(r.T)
+        res["fitness_mean_" + k] = round(float(r.fitness.mean()), 4)
+    del os.environ["CS_ICP_STATS"]
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--json", default=None)
@@ -133,14 +190,28 @@ def main():
     ap.add_argument("--deg", type=float, default=3.0)
     ap.add_argument("--trans", type=float, default=0.01)
     ap.add_argument("--no-step", action="store_true", help="skip the registration-step timing (it builds the network)")
+    ap.add_argument("--estimation", default="point", choices=["point", "plane"],
+                    help="plane: point against point-to-plane against the normals, alternating (DESIGN 13)")
+    ap.add_argument("--normal-k", type=int, default=16)
+    ap.add_argument("--start", default="small", choices=["small", "large"],
+                    help="large: 12 degrees / 5 cm with max_dist 0.12 (overrides --deg / --trans)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
+    max_dist = 2 * VOXEL
+    if a.start == "large":
+        a.deg, a.trans, max_dist = 12.0, 0.05, 4 * VOXEL
     x0, off0, x1, off1, T0, truth, queries, cads = problems(dev, a.deg, a.trans)
     pairs = list(range(N_PAIRS))
-    max_dist = 2 * VOXEL
     res = {"device": torch.cuda.get_device_name(dev), "hip": torch.version.hip, "pairs": N_PAIRS, "voxel": VOXEL,
            "source_rows": off0[-1], "target_rows": off1[-1], "max_dist": max_dist, "max_iter": MAX_ITER,
            "perturbation": {"deg": a.deg, "trans": a.trans}}
+    if a.estimation == "plane":
+        res = plane_report(a, res, x0, off0, x1, off1, T0, truth, max_dist)
+        print(json.dumps(res))
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(res, f, indent=1)
+        return
 
     def hip():
         return B.icp_batch(x0, off0, x1, off1, pairs, pairs, T0, max_dist, MAX_ITER)
