@@ -481,6 +481,10 @@ class IcpResult(NamedTuple):
     ncorr: torch.Tensor      # int32 [n_prob]
     corr: Optional[torch.Tensor]   # int32, problem-major (problem p at corr_off[p]): local target row or -1
     corr_off: Optional[list]
+    wfitness: Optional[torch.Tensor] = None   # f64 [n_prob] weighted inlier share (a robust kernel was asked for)
+
+
+ICP_KERNELS = {"l2": 0, "huber": 1, "cauchy": 2, "tukey": 3}    # CS_ICP_KERNEL_*
 
 
 def estimate_normals(xyz, offsets, k=16):
@@ -497,11 +501,20 @@ def estimate_normals(xyz, offsets, k=16):
 
 
 def icp_batch(src, soff, tgt, toff, src_seg, tgt_seg, T0, max_dist, max_iter=30, relative_fitness=1e-6,
-              relative_rmse=1e-6, return_corr=False, tgt_normals=None):
+              relative_rmse=1e-6, return_corr=False, tgt_normals=None, kernel="l2", kernel_scale=None):
     """cs_icp_batch: point-to-point ICP of problem p = source segment src_seg[p] of `src` against target segment
     tgt_seg[p] of `tgt` (f32 [n,3] device, host offset lists), started at T0[p] (f32 [n_prob,4,4] device).  The semantics
     are the header comment of cs_icp_batch.  tgt_normals (f32, the shape of `tgt`; estimate_normals): point-to-plane
-    estimation instead, cs_icp_plane_batch.  Returns an IcpResult; no host wait."""
+    estimation instead, cs_icp_plane_batch.  kernel = "huber" / "cauchy" / "tukey" with kernel_scale > 0: the robust
+    point-to-plane estimation, cs_icp_plane_robust_batch, which also fills IcpResult.wfitness; it needs tgt_normals (robust
+    kernels exist for the plane estimation only, as in Open3D).  Returns an IcpResult; no host wait."""
+    if kernel not in ICP_KERNELS:
+        raise ValueError("icp_batch: kernel must be one of %s, got %r" % (sorted(ICP_KERNELS), kernel))
+    if kernel != "l2" and tgt_normals is None:
+        raise ValueError("icp_batch: kernel %r needs tgt_normals (robust kernels exist for the plane estimation only)"
+                         % (kernel,))
+    if kernel != "l2" and kernel_scale is None:
+        raise ValueError("icp_batch: kernel %r needs a kernel_scale" % (kernel,))
     src = _dev(src, torch.float32, "source").contiguous()
     tgt = _dev(tgt, torch.float32, "target").contiguous()
     T0 = _dev(T0, torch.float32, "initial transforms").contiguous()
@@ -529,19 +542,26 @@ def icp_batch(src, soff, tgt, toff, src_seg, tgt_seg, T0, max_dist, max_iter=30,
         lens = [int(soff[s + 1]) - int(soff[s]) for s in src_seg] if sane else []
         corr_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64).tolist()
         corr = torch.full((max(corr_off[-1], 1),), -1, dtype=torch.int32, device=dev)
-    tail = (i64_array(toff), i32_array(src_seg), i32_array(tgt_seg), n_prob, ptr(T0), float(max_dist), int(max_iter),
-            float(relative_fitness), float(relative_rmse), ptr(T), ptr(T32), ptr(fitness), ptr(rmse), ptr(iters),
-            ptr(ncorr), ptr(corr), stream_ptr())
+    head = (i64_array(toff), i32_array(src_seg), i32_array(tgt_seg), n_prob, ptr(T0), float(max_dist), int(max_iter),
+            float(relative_fitness), float(relative_rmse))
+    tail = head + (ptr(T), ptr(T32), ptr(fitness), ptr(rmse), ptr(iters), ptr(ncorr), ptr(corr), stream_ptr())
+    wfitness = None
     if tgt_normals is None:
         check(_lib.load().cs_icp_batch(ptr(src), i64_array(soff), ptr(tgt), *tail))
     else:
         nrm = _dev(tgt_normals, torch.float32, "target normals").contiguous()
         if nrm.shape != tgt.shape:
             raise ValueError("icp_batch: tgt_normals must have the shape of the target points")
-        check(_lib.load().cs_icp_plane_batch(ptr(src), i64_array(soff), ptr(tgt), ptr(nrm), *tail))
+        if kernel == "l2":
+            check(_lib.load().cs_icp_plane_batch(ptr(src), i64_array(soff), ptr(tgt), ptr(nrm), *tail))
+        else:
+            wfitness = torch.empty(n_prob, dtype=torch.float64, device=dev)
+            check(_lib.load().cs_icp_plane_robust_batch(
+                ptr(src), i64_array(soff), ptr(tgt), ptr(nrm), *head, ICP_KERNELS[kernel], float(kernel_scale), ptr(T),
+                ptr(T32), ptr(fitness), ptr(rmse), ptr(wfitness), ptr(iters), ptr(ncorr), ptr(corr), stream_ptr()))
     if corr is not None:
         corr = corr[:corr_off[-1]]
-    return IcpResult(T, T32, fitness, rmse, iters, ncorr, corr, corr_off)
+    return IcpResult(T, T32, fitness, rmse, iters, ncorr, corr, corr_off, wfitness)
 
 
 def icp_stats(reset=False):

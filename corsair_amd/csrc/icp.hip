@@ -1,16 +1,18 @@
-// Batched ICP: point-to-point (cs_icp_batch) and point-to-plane (cs_icp_plane_batch).  The specifications
-// are the comments of the two entries in include/corsair_hip.h; tests/icp_ref.py and tests/icp_plane_ref.py restate them bit
-// for bit.  The estimation is a compile-time parameter EST (0 = point, 1 = plane) of the sums at the end of the association
-// kernels and of the update; pose chain, association, evaluation, loop and stop rule are one code.
+// Batched ICP: point-to-point (cs_icp_batch), point-to-plane (cs_icp_plane_batch) and point-to-plane
+// with a robust kernel (cs_icp_plane_robust_batch).  The specifications are the comments of the three entries in
+// include/corsair_hip.h; tests/icp_ref.py, tests/icp_plane_ref.py and tests/icp_robust_ref.py restate them bit for bit.  The
+// estimation is a compile-time parameter EST (0 = point, 1 = plane, 2 = plane with a per-pair weight) of the sums at the end
+// of the association kernels and of the update; pose chain, association, evaluation, loop and stop rule are one code.  The
+// unweighted instantiations are what they were before the third existed: kernel = L2 runs EST = 1.
 //
 // One call = one target preparation + (max_iter + 1) rounds, all enqueued without a host wait:
 //   k_icp_frame    per problem: the bounding box of its target segment (exact min / max), the origin and the
 //                  power-of-two scales of its fixed-point sums
 //   chamfer_pack16 the f16 hi / lo image, |S t|^2 and the float4 rows of every target, once per call
 //   round r:       k_icp_f16 (+ k_icp_exact for the workgroups it flags) or k_icp_exact alone -- association of the posed
-//                  ORIGINAL sources under the current T, 17 (point) or 29 (plane) order-free 64-bit integer sums per
-//                  problem; k_icp_step -- one lane per problem: fitness / rmse of that association, the stop rule, Horn's
-//                  fit (point) or the 6x6 normal equations by Cholesky (plane) from the sums, T <- U T.
+//                  ORIGINAL sources under the current T, 17 (point), 29 (plane) or 30 (weighted plane) order-free 64-bit
+//                  integer sums per problem; k_icp_step -- one lane per problem: fitness / rmse of that association, the
+//                  stop rule, Horn's fit (point) or the 6x6 normal equations by Cholesky (plane) from the sums, T <- U T.
 // A problem that has stopped raises its device flag; its workgroups leave on it in every later round.
 #include <math.h>
 
@@ -26,10 +28,16 @@ constexpr int ICP_ST = 4 * 32 * CHF_NG;   // sources per workgroup (both associa
 constexpr int ICP_TT = 512;               // target rows per LDS stage of the exact kernel
 constexpr int ICP_NSUM = 17;              // count, sum p' (3), sum q' (3), sum p' q'^T (9), sum d^2
 constexpr int ICP_NSUM_PLANE = 29;        // count, sum J_i J_j (i <= j, 21), sum J_i r (6), sum d^2
-constexpr int ICP_POINT = 0, ICP_PLANE = 1;
+constexpr int ICP_NSUM_ROBUST = 30;       // the 29 plane sums (27 of them weighted) + sum w
+constexpr int ICP_POINT = 0, ICP_PLANE = 1, ICP_ROBUST = 2;
 template <int EST>
 constexpr int icp_nsum() {
-  return EST == ICP_PLANE ? ICP_NSUM_PLANE : ICP_NSUM;
+  return EST == ICP_ROBUST ? ICP_NSUM_ROBUST : (EST == ICP_PLANE ? ICP_NSUM_PLANE : ICP_NSUM);
+}
+// sum d^2 is the last point sum and the 29th of both plane layouts
+template <int EST>
+constexpr int icp_d2_at() {
+  return EST == ICP_POINT ? ICP_NSUM - 1 : ICP_NSUM_PLANE - 1;
 }
 
 // Fixed-point sums.  A kept pair has |p - q|^2 < max_dist^2 and q inside the bounding box of the target segment, so
@@ -57,6 +65,11 @@ constexpr int icp_nsum() {
 // so every scaled term is below 2^(61 - eN) and every sum below 2^61, as for the point sums; d^2 keeps the scale 2^s2.
 // The clamp makes that hold for ANY normals a caller passes (length 10^3, NaN): such sums are defined, not meaningful.
 // The exponents stay inside [-773, 260]: normal f64 powers of two, exact scaling.
+//
+// Weighted plane sums (EST = 2).  Each of the 27 rounded products is multiplied by the pair's weight w before it is scaled.
+// 0 <= w <= 1 for every kernel below (a NaN weight is replaced by 0) and rounding to nearest is monotone, so
+// |fl(x w)| <= |x|: no weighted term is larger than the unweighted term bounded above.  The 30th sum adds I(w 2^(61 - eN)),
+// at most 2^eN terms of at most 2^(61 - eN).  Nothing leaves 2^61; count and d^2 are not weighted.
 constexpr int ICP_EM_MIN = -100;
 constexpr int ICP_EM_MAX = 400;
 constexpr int ICP_SUM_BITS = 61;
@@ -80,6 +93,10 @@ struct IcpFrame {
 };
 struct IcpPlaneFrame {   // 2^s and 2^-s of the five product classes of the plane sums
   double sc_rr, inv_rr, sc_rt, inv_rt, sc_tt, inv_tt, sc_rd, inv_rd, sc_td, inv_td;
+};
+struct IcpLoss {     // the robust kernel of EST = 2 (CS_ICP_KERNEL_*), unused otherwise
+  int kind;
+  double k;          // kernel_scale
 };
 struct IcpCriteria {
   double thr2;      // max_dist * max_dist
@@ -166,20 +183,45 @@ __device__ __forceinline__ long long icp_fix(double v, double scale, double clam
   return (long long)x;                                     // truncates toward zero
 }
 
-// The sums of one workgroup (17 for the point estimation, 29 for the plane one): thread = one source (kept or not), wave
-// shuffle, LDS across the four waves, then ONE 64-bit integer atomic per sum.  Integer addition: the same total in any
-// order.  nrow: the normal row of the matched target (plane estimation, kept pairs only).
+// The weight of a kept pair from its point-to-plane residual r: [O3D-knowledge] Open3D's HuberLoss, CauchyLoss and
+// TukeyLoss::Weight.  One IEEE operation each; the branch is uniform over the launch.
+__device__ __forceinline__ double icp_weight(const IcpLoss& ls, double r) {
+  const double a = fabs(r), k = ls.k;
+  double w;
+  if (ls.kind == CS_ICP_KERNEL_HUBER) {
+    w = a <= k ? 1.0 : k / a;
+  } else if (ls.kind == CS_ICP_KERNEL_CAUCHY) {
+    const double q = r / k;
+    w = 1.0 / (1.0 + q * q);
+  } else if (ls.kind == CS_ICP_KERNEL_TUKEY) {
+    if (!(a < k)) {
+      w = 0.0;
+    } else {
+      const double q = r / k;
+      const double e = 1.0 - q * q;
+      w = e * e;
+    }
+  } else {
+    w = 1.0;
+  }
+  return w == w ? w : 0.0;
+}
+
+// The sums of one workgroup (17 for the point estimation, 29 for the plane one, 30 for the weighted one): thread = one
+// source (kept or not), wave shuffle, LDS across the four waves, then ONE 64-bit integer atomic per sum.  Integer addition:
+// the same total in any order.  nrow: the normal row of the matched target (plane estimation, kept pairs only).
 template <int EST>
 __device__ __forceinline__ void icp_block_sums(bool kept, double px, double py, double pz, float qx, float qy, float qz,
                                                double d2, const IcpFrame& fr, const IcpPlaneFrame* __restrict__ pfr,
-                                               const float* __restrict__ nrow, unsigned long long* __restrict__ sums,
+                                               const float* __restrict__ nrow, const IcpLoss& loss,
+                                               unsigned long long* __restrict__ sums,
                                                unsigned long long (*part)[icp_nsum<EST>()]) {
   constexpr int NS = icp_nsum<EST>();
   const int tid = threadIdx.x;
   long long v[NS];
 #pragma unroll
   for (int k = 0; k < NS; ++k) v[k] = 0;
-  if constexpr (EST == ICP_PLANE) {
+  if constexpr (EST != ICP_POINT) {
     if (kept) {
       const IcpPlaneFrame g = *pfr;
       const double p[3] = {px - fr.o[0], py - fr.o[1], pz - fr.o[2]};
@@ -188,22 +230,27 @@ __device__ __forceinline__ void icp_block_sums(bool kept, double px, double py, 
       const double r = fma(e[2], n[2], fma(e[1], n[1], e[0] * n[0]));
       const double J[6] = {fma(p[1], n[2], -(p[2] * n[1])), fma(p[2], n[0], -(p[0] * n[2])),
                            fma(p[0], n[1], -(p[1] * n[0])), n[0], n[1], n[2]};
+      double w = 1.0;
+      if constexpr (EST == ICP_ROBUST) w = icp_weight(loss, r);
       v[0] = 1;
       int at = 1;
 #pragma unroll
       for (int i = 0; i < 6; ++i)
 #pragma unroll
         for (int j = i; j < 6; ++j) {
-          const double prod = J[i] * J[j];   // rounded product (no contraction)
+          double prod = J[i] * J[j];   // rounded product (no contraction)
+          if constexpr (EST == ICP_ROBUST) prod = prod * w;
           const double sc = j < 3 ? g.sc_rr : (i < 3 ? g.sc_rt : g.sc_tt);
           v[at++] = icp_fix(prod, sc, fr.clamp);
         }
 #pragma unroll
       for (int i = 0; i < 6; ++i) {
-        const double prod = J[i] * r;
+        double prod = J[i] * r;
+        if constexpr (EST == ICP_ROBUST) prod = prod * w;
         v[22 + i] = icp_fix(prod, i < 3 ? g.sc_rd : g.sc_td, fr.clamp);
       }
       v[28] = icp_fix(d2, fr.sc2, fr.clamp);
+      if constexpr (EST == ICP_ROBUST) v[29] = icp_fix(w, fr.clamp, fr.clamp);
     }
   } else if (kept) {
     const double p[3] = {px - fr.o[0], py - fr.o[1], pz - fr.o[2]};
@@ -255,7 +302,8 @@ __global__ __launch_bounds__(256) void k_icp_exact(const IcpWork* __restrict__ w
                                                    const IcpFrame* __restrict__ frame,
                                                    const IcpPlaneFrame* __restrict__ pframe,
                                                    const int32_t* __restrict__ done, double thr2,
-                                                   unsigned long long* __restrict__ sums, int32_t* __restrict__ corr,
+                                                   IcpLoss loss, unsigned long long* __restrict__ sums,
+                                                   int32_t* __restrict__ corr,
                                                    const int32_t* __restrict__ only_flagged) {
   __shared__ float t_lds[ICP_TT * 3];
   __shared__ unsigned long long part[4][icp_nsum<EST>()];
@@ -295,8 +343,8 @@ __global__ __launch_bounds__(256) void k_icp_exact(const IcpWork* __restrict__ w
     qz = tp[2];
   }
   if (corr && active) corr[wk.c0 + tid] = kept ? bidx : -1;
-  icp_block_sums<EST>(kept, px, py, pz, qx, qy, qz, best, frame[wk.prob], EST == ICP_PLANE ? pframe + wk.prob : nullptr,
-                      EST == ICP_PLANE && kept ? tnrm + (pr.t0 + bidx) * 3 : nullptr,
+  icp_block_sums<EST>(kept, px, py, pz, qx, qy, qz, best, frame[wk.prob], EST != ICP_POINT ? pframe + wk.prob : nullptr,
+                      EST != ICP_POINT && kept ? tnrm + (pr.t0 + bidx) * 3 : nullptr, loss,
                       sums + (int64_t)wk.prob * icp_nsum<EST>(), part);
 }
 
@@ -313,8 +361,9 @@ __global__ __launch_bounds__(256) void k_icp_f16(const IcpWork* __restrict__ wor
                                                  const IcpFrame* __restrict__ frame,
                                                  const IcpPlaneFrame* __restrict__ pframe,
                                                  const int32_t* __restrict__ done, double thr2,
-                                                 unsigned long long* __restrict__ sums, int32_t* __restrict__ corr,
-                                                 int32_t* __restrict__ flag, unsigned long long* __restrict__ stats) {
+                                                 IcpLoss loss, unsigned long long* __restrict__ sums,
+                                                 int32_t* __restrict__ corr, int32_t* __restrict__ flag,
+                                                 unsigned long long* __restrict__ stats) {
   __shared__ __attribute__((aligned(16))) _Float16 a_s[2][CHF_ROWS * CHF_PITCH];
   __shared__ __attribute__((aligned(16))) float tn_s[2][CHF_ROWS];
   __shared__ unsigned long long part[4][icp_nsum<EST>()];
@@ -518,8 +567,8 @@ __global__ __launch_bounds__(256) void k_icp_f16(const IcpWork* __restrict__ wor
   if (kept) q = trow[my_row];
   if (corr && active) corr[wk.c0 + tid] = kept ? my_row : -1;
   icp_block_sums<EST>(kept, mpx, mpy, mpz, q.x, q.y, q.z, my_e, frame[wk.prob],
-                      EST == ICP_PLANE ? pframe + wk.prob : nullptr,
-                      EST == ICP_PLANE && kept ? tnrm + (pr.t0 + my_row) * 3 : nullptr,
+                      EST != ICP_POINT ? pframe + wk.prob : nullptr,
+                      EST != ICP_POINT && kept ? tnrm + (pr.t0 + my_row) * 3 : nullptr, loss,
                       sums + (int64_t)wk.prob * icp_nsum<EST>(), part);
 }
 
@@ -628,8 +677,9 @@ __device__ __forceinline__ void icp_update_point(const unsigned long long* __res
 // 2^-30 is four decimal orders above the noise of the sums and far below any geometry that constrains the pose.
 constexpr double ICP_PIVOT_MIN = 0x1.0p-30;
 
-// The point-to-plane update from the 29 sums: A x = -b by an unpivoted Cholesky, x = (alpha, t') about the origin o, the
-// rotation of the quaternion (1, alpha / 2).  false: a pivot is not finite or too small -- the problem stops.
+// The point-to-plane update from the 29 sums (the weighted layout has the same entries in the same places): A x = -b by an
+// unpivoted Cholesky, x = (alpha, t') about the origin o, the rotation of the quaternion (1, alpha / 2).  false: a pivot is
+// not finite or too small -- the problem stops.
 __device__ __forceinline__ bool icp_update_plane(const unsigned long long* __restrict__ S, const IcpFrame& fr,
                                                  const IcpPlaneFrame& g, const double* __restrict__ Tp, double (&Tn)[12]) {
   double A[6][6], L[6][6], bv[6], yv[6], xv[6];
@@ -695,9 +745,9 @@ __global__ void k_icp_step(const IcpProb* __restrict__ probs, int n_prob, const 
                            const IcpPlaneFrame* __restrict__ pframe, IcpCriteria crit, int round, int last,
                            unsigned long long* __restrict__ sums, int32_t* __restrict__ done, double* __restrict__ T,
                            float* __restrict__ T32, double* __restrict__ fitness, double* __restrict__ rmse,
-                           int32_t* __restrict__ iters, int32_t* __restrict__ ncorr) {
+                           double* __restrict__ wfitness, int32_t* __restrict__ iters, int32_t* __restrict__ ncorr) {
   constexpr int NS = icp_nsum<EST>();
-  constexpr int MIN_CORR = EST == ICP_PLANE ? 6 : 3;
+  constexpr int MIN_CORR = EST != ICP_POINT ? 6 : 3;
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= n_prob) return;
   double* Tp = T + (int64_t)p * 16;
@@ -708,19 +758,25 @@ __global__ void k_icp_step(const IcpProb* __restrict__ probs, int n_prob, const 
     const long long n = (long long)S[0];
     const double dn = (double)n;
     const double fit = pr.sn > 0 ? dn / (double)pr.sn : 0.0;
-    const double sd2 = (double)(long long)S[NS - 1] * fr.inv2;
+    const double sd2 = (double)(long long)S[icp_d2_at<EST>()] * fr.inv2;
     const double rm = n > 0 ? sqrt(sd2 / dn) : 0.0;
     const double pfit = fitness[p], prm = rmse[p];
     fitness[p] = fit;
     rmse[p] = rm;
     ncorr[p] = (int32_t)n;
+    if (wfitness) {   // sum w = S_w 2^-(61 - eN); every weight is 1 without a kernel, and the share is the fitness
+      if constexpr (EST == ICP_ROBUST)
+        wfitness[p] = pr.sn > 0 ? ((double)(long long)S[NS - 1] * (1.0 / fr.clamp)) / (double)pr.sn : 0.0;
+      else
+        wfitness[p] = fit;
+    }
     bool stop = last != 0;
     if (round > 0 && fabs(fit - pfit) < crit.rel_fitness && fabs(rm - prm) < crit.rel_rmse) stop = true;
     if (n < MIN_CORR || !isfinite(fit) || !isfinite(rm)) stop = true;
     if (!stop) {
       double Tn[12];
       bool solved = true;
-      if constexpr (EST == ICP_PLANE)
+      if constexpr (EST != ICP_POINT)
         solved = icp_update_plane(S, fr, pframe[p], Tp, Tn);
       else
         icp_update_point(S, dn, fr, Tp, Tn);
@@ -742,13 +798,14 @@ __global__ void k_icp_step(const IcpProb* __restrict__ probs, int n_prob, const 
 }
 
 __global__ void k_icp_init(const float* __restrict__ T0, int n_prob, double* __restrict__ T, double* __restrict__ fitness,
-                           double* __restrict__ rmse, int32_t* __restrict__ iters, int32_t* __restrict__ ncorr,
-                           int32_t* __restrict__ done) {
+                           double* __restrict__ rmse, double* __restrict__ wfitness, int32_t* __restrict__ iters,
+                           int32_t* __restrict__ ncorr, int32_t* __restrict__ done) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= n_prob) return;
   for (int i = 0; i < 16; ++i) T[(int64_t)p * 16 + i] = (double)T0[(int64_t)p * 16 + i];
   fitness[p] = 0.0;
   rmse[p] = 0.0;
+  if (wfitness) wfitness[p] = 0.0;
   iters[p] = 0;
   ncorr[p] = 0;
   done[p] = 0;
@@ -756,12 +813,14 @@ __global__ void k_icp_init(const float* __restrict__ T0, int n_prob, double* __r
 
 std::atomic<unsigned long long> g_icp_stats[2];
 
-// Both entries: d_tnrm is the normal array of the plane estimation (EST = 1), unused otherwise.
+// Every entry: d_tnrm is the normal array of the plane estimations (EST = 1, 2), loss the kernel of EST = 2, d_wfitness the
+// optional weighted inlier share of cs_icp_plane_robust_batch (NULL for the other two entries).
 template <int EST>
 int icp_run(const char* name, const float* d_src, const int64_t* h_soff, const float* d_tgt, const float* d_tnrm,
             const int64_t* h_toff, const int32_t* h_src_seg, const int32_t* h_tgt_seg, int n_prob, const float* d_T0,
             double max_dist, int max_iter, double relative_fitness, double relative_rmse, double* d_T, float* d_T32,
-            double* d_fitness, double* d_rmse, int32_t* d_iters, int32_t* d_ncorr, int32_t* d_corr, void* stream) {
+            double* d_fitness, double* d_rmse, int32_t* d_iters, int32_t* d_ncorr, int32_t* d_corr, void* stream,
+            IcpLoss loss = IcpLoss{CS_ICP_KERNEL_L2, 0.0}, double* d_wfitness = nullptr) {
   constexpr int NS = icp_nsum<EST>();
   CS_REQUIRE(h_soff && h_toff && h_src_seg && h_tgt_seg, CS_ERR_INVALID, "%s: NULL table", name);
   CS_REQUIRE(n_prob >= 0, CS_ERR_INVALID, "%s: negative problem count", name);
@@ -802,7 +861,7 @@ int icp_run(const char* name, const float* d_src, const int64_t* h_soff, const f
   }
   CS_REQUIRE(work.empty() || d_src, CS_ERR_INVALID, "%s: NULL source array", name);
   CS_REQUIRE(nt_rows == 0 || d_tgt, CS_ERR_INVALID, "%s: NULL target array", name);
-  CS_REQUIRE(EST != ICP_PLANE || nt_rows == 0 || d_tnrm, CS_ERR_INVALID, "%s: NULL target normal array", name);
+  CS_REQUIRE(EST == ICP_POINT || nt_rows == 0 || d_tnrm, CS_ERR_INVALID, "%s: NULL target normal array", name);
   hipStream_t s = (hipStream_t)stream;
   pool_use_stream(s);
   const bool use_f16 = !env_first_is("CS_ICP_F16", '0');
@@ -815,7 +874,7 @@ int icp_run(const char* name, const float* d_src, const int64_t* h_soff, const f
   PoolBuf<unsigned long long> sums((size_t)n_prob * NS + 2);   // + the two statistics counters
   PoolBuf<int32_t> done((size_t)n_prob);
   CS_REQUIRE(frame.p && sums.p && done.p, CS_ERR_HIP, "%s: scratch allocation failed", name);
-  if (EST == ICP_PLANE) CS_REQUIRE(pframe.alloc((size_t)n_prob), CS_ERR_HIP, "%s: scratch allocation failed", name);
+  if (EST != ICP_POINT) CS_REQUIRE(pframe.alloc((size_t)n_prob), CS_ERR_HIP, "%s: scratch allocation failed", name);
   int rc = upload(dprob, probs, s);
   if (!rc) rc = upload(dwork, work, s);
   if (rc) return rc;
@@ -823,7 +882,8 @@ int icp_run(const char* name, const float* d_src, const int64_t* h_soff, const f
   ProfScope prof("icp", s, flop * (double)(max_iter + 1));
   CS_HIP_CHECK(hipMemsetAsync(sums.p, 0, sizeof(unsigned long long) * ((size_t)n_prob * NS + 2), s));
   const dim3 pgrid((unsigned)ceil_div(n_prob, 64));
-  hipLaunchKernelGGL(k_icp_init, pgrid, dim3(64), 0, s, d_T0, n_prob, d_T, d_fitness, d_rmse, d_iters, d_ncorr, done.p);
+  hipLaunchKernelGGL(k_icp_init, pgrid, dim3(64), 0, s, d_T0, n_prob, d_T, d_fitness, d_rmse, d_wfitness, d_iters,
+                     d_ncorr, done.p);
   hipLaunchKernelGGL(k_icp_frame, dim3((unsigned)n_prob), dim3(256), 0, s, dprob.p, d_tgt, max_dist, frame.p, pframe.p);
   // the targets do not move: one image for every round
   PoolBuf<_Float16> img16;
@@ -848,19 +908,20 @@ int icp_run(const char* name, const float* d_src, const int64_t* h_soff, const f
     if (n_work) {
       if (use_f16) {
         hipLaunchKernelGGL(k_icp_f16<EST>, dim3(n_work), dim3(256), 0, s, dwork.p, dprob.p, d_src, t4f.p, img16.p, tn16.p,
-                           d_tnrm, (const double*)d_T, frame.p, pframe.p, done.p, crit.thr2, sums.p, d_corr, wflag.p,
+                           d_tnrm, (const double*)d_T, frame.p, pframe.p, done.p, crit.thr2, loss, sums.p, d_corr, wflag.p,
                            want_stats ? dstats : (unsigned long long*)nullptr);
         hipLaunchKernelGGL(k_icp_exact<EST>, dim3(n_work), dim3(256), 0, s, dwork.p, dprob.p, d_src, d_tgt, d_tnrm,
-                           (const double*)d_T, frame.p, pframe.p, done.p, crit.thr2, sums.p, d_corr,
+                           (const double*)d_T, frame.p, pframe.p, done.p, crit.thr2, loss, sums.p, d_corr,
                            (const int32_t*)wflag.p);
       } else {
         hipLaunchKernelGGL(k_icp_exact<EST>, dim3(n_work), dim3(256), 0, s, dwork.p, dprob.p, d_src, d_tgt, d_tnrm,
-                           (const double*)d_T, frame.p, pframe.p, done.p, crit.thr2, sums.p, d_corr,
+                           (const double*)d_T, frame.p, pframe.p, done.p, crit.thr2, loss, sums.p, d_corr,
                            (const int32_t*)nullptr);
       }
     }
     hipLaunchKernelGGL(k_icp_step<EST>, pgrid, dim3(64), 0, s, dprob.p, n_prob, frame.p, pframe.p, crit, round,
-                       round == max_iter ? 1 : 0, sums.p, done.p, d_T, d_T32, d_fitness, d_rmse, d_iters, d_ncorr);
+                       round == max_iter ? 1 : 0, sums.p, done.p, d_T, d_T32, d_fitness, d_rmse, d_wfitness, d_iters,
+                       d_ncorr);
   }
   CS_LAUNCH_CHECK();
   if (want_stats) {
@@ -899,6 +960,26 @@ int cs_icp_plane_batch(const float* d_src, const int64_t* h_soff, const float* d
   return icp_run<ICP_PLANE>("cs_icp_plane_batch", d_src, h_soff, d_tgt, d_tgt_normal, h_toff, h_src_seg, h_tgt_seg, n_prob,
                             d_T0, max_dist, max_iter, relative_fitness, relative_rmse, d_T, d_T32, d_fitness, d_rmse,
                             d_iters, d_ncorr, d_corr, stream);
+}
+
+int cs_icp_plane_robust_batch(const float* d_src, const int64_t* h_soff, const float* d_tgt, const float* d_tgt_normal,
+                              const int64_t* h_toff, const int32_t* h_src_seg, const int32_t* h_tgt_seg, int n_prob,
+                              const float* d_T0, double max_dist, int max_iter, double relative_fitness,
+                              double relative_rmse, int kernel, double kernel_scale, double* d_T, float* d_T32,
+                              double* d_fitness, double* d_rmse, double* d_wfitness, int32_t* d_iters, int32_t* d_ncorr,
+                              int32_t* d_corr, void* stream) {
+  const char* name = "cs_icp_plane_robust_batch";
+  CS_REQUIRE(kernel >= CS_ICP_KERNEL_L2 && kernel <= CS_ICP_KERNEL_TUKEY, CS_ERR_INVALID, "%s: unknown kernel %d", name,
+             kernel);
+  if (kernel == CS_ICP_KERNEL_L2)   // every weight is 1: cs_icp_plane_batch's instantiation, the scale is ignored
+    return icp_run<ICP_PLANE>(name, d_src, h_soff, d_tgt, d_tgt_normal, h_toff, h_src_seg, h_tgt_seg, n_prob, d_T0, max_dist,
+                              max_iter, relative_fitness, relative_rmse, d_T, d_T32, d_fitness, d_rmse, d_iters, d_ncorr,
+                              d_corr, stream, IcpLoss{CS_ICP_KERNEL_L2, 0.0}, d_wfitness);
+  CS_REQUIRE(std::isfinite(kernel_scale) && kernel_scale > 0.0, CS_ERR_INVALID,
+             "%s: kernel_scale must be positive and finite", name);
+  return icp_run<ICP_ROBUST>(name, d_src, h_soff, d_tgt, d_tgt_normal, h_toff, h_src_seg, h_tgt_seg, n_prob, d_T0, max_dist,
+                             max_iter, relative_fitness, relative_rmse, d_T, d_T32, d_fitness, d_rmse, d_iters, d_ncorr,
+                             d_corr, stream, IcpLoss{kernel, kernel_scale}, d_wfitness);
 }
 
 }  // extern "C"

@@ -23,6 +23,8 @@ from . import engine as E
 from . import registration as R
 from .utils.eval_pose import eval_pose
 
+ICP_KERNEL_NAMES = tuple(B.ICP_KERNELS)       # "l2", "huber", "cauchy", "tukey"
+
 
 @dataclass
 class Config:
@@ -48,13 +50,25 @@ class Config:
     # icp_normal_k neighbours).  16 is UNTUNED: 8 and 16 behaved alike in the experiment that motivated it
     icp_estimation: str = "point"
     icp_normal_k: int = 16
+    # robust kernel of the plane estimation: "l2" (none), "huber", "cauchy" or "tukey" (cs_icp_plane_robust_batch).
+    # icp_kernel_scale = 0.0 means 1 * voxel_size -- the size of the residual a voxel grid leaves on a matching surface,
+    # which NOBODY HAS TUNED; set it explicitly for real data
+    icp_kernel: str = "l2"
+    icp_kernel_scale: float = 0.0
 
     def icp_distance(self):
         return self.icp_max_dist if self.icp_max_dist > 0 else 2.0 * self.voxel_size
 
+    def icp_scale(self):
+        return self.icp_kernel_scale if self.icp_kernel_scale > 0 else 1.0 * self.voxel_size
+
     def check_icp(self):
         if self.icp_estimation not in ("point", "plane"):
             raise ValueError("Config.icp_estimation must be 'point' or 'plane', got %r" % (self.icp_estimation,))
+        if self.icp_kernel not in ICP_KERNEL_NAMES:
+            raise ValueError("Config.icp_kernel must be one of %s, got %r" % (ICP_KERNEL_NAMES, self.icp_kernel))
+        if self.icp_kernel != "l2" and self.icp_estimation != "plane":
+            raise ValueError("Config.icp_kernel %r needs icp_estimation = 'plane'" % (self.icp_kernel,))
         if not 3 <= int(self.icp_normal_k) <= 32:
             raise ValueError("Config.icp_normal_k must lie in [3, 32], got %r" % (self.icp_normal_k,))
 
@@ -183,7 +197,8 @@ class Pipeline:
                                 cads.offsets, syms, c.k_nn, c.max_corr, 0, anchor_ids, 100,
                                 c.ransac_max_iter, c.ransac_confidence, use_symmetry, force_gate,
                                 query_anchors, c.icp_max_iter, c.icp_distance() if c.icp_max_iter > 0 else None,
-                                c.icp_estimation, c.icp_normal_k, cads.normal)
+                                c.icp_estimation, c.icp_normal_k, cads.normal, c.icp_kernel,
+                                c.icp_scale() if c.icp_kernel != "l2" else None)
 
     def with_normals(self, s):
         """`s` with the normals of its origins (one cs_estimate_normals call over the whole set) when the configuration
@@ -557,6 +572,10 @@ def build_parser():
                     help="ICP estimation: point-to-point, or point-to-plane on the CAD voxels' normals")
     ap.add_argument("--icp-normal-k", type=int, default=16,
                     help="neighbours of a CAD voxel's normal for --icp-estimation plane, 3..32 (an untuned default)")
+    ap.add_argument("--icp-kernel", default="l2", choices=list(ICP_KERNEL_NAMES),
+                    help="robust kernel on the point-to-plane residual (needs --icp-estimation plane); l2 = none")
+    ap.add_argument("--icp-kernel-scale", type=float, default=0.0,
+                    help="scale k of --icp-kernel; 0 = 1 * voxel size (an untuned default)")
     ap.add_argument("--in-flight", type=int, default=3, help="registration batches in flight (host threads x HIP streams)")
     ap.add_argument("--device", default="cuda", choices=["cuda"], help="there is no CPU path")
     return ap
@@ -578,7 +597,8 @@ def main(argv=None):
         raise SystemExit("checkpoint has no embedding_state_dict: retrieval needs the descriptor head (evaluation.py:199)")
     cfg = Config(n_points=a.n_points, batch_size=a.batch_size, embed_batch_size=a.embed_batch_size,
                  ransac_max_iter=a.ransac_max_iter, icp_max_iter=a.icp_iters, icp_max_dist=a.icp_max_dist,
-                 icp_estimation=a.icp_estimation, icp_normal_k=a.icp_normal_k)
+                 icp_estimation=a.icp_estimation, icp_normal_k=a.icp_normal_k, icp_kernel=a.icp_kernel,
+                 icp_kernel_scale=a.icp_kernel_scale)
     cfg.check_icp()
     pipe = Pipeline(sd, esd, device=a.device, config=cfg)
     cad_names, catalog = load_cloud_dir(a.catalog_dir, a.n_points, "catalog")

@@ -39,9 +39,16 @@ class Config:
     icp_max_dist: float = 0.0
     icp_estimation: str = "point"
     icp_normal_k: int = 16
+    # robust kernel of the plane estimation ("l2" = none, "huber", "cauchy", "tukey"); icp_kernel_scale = 0.0 means
+    # 1 * voxel_size (UNTUNED, as in harness.Config)
+    icp_kernel: str = "l2"
+    icp_kernel_scale: float = 0.0
 
     def icp_distance(self):
         return self.icp_max_dist if self.icp_max_dist > 0 else 2.0 * self.voxel_size
+
+    def icp_scale(self):
+        return self.icp_kernel_scale if self.icp_kernel_scale > 0 else 1.0 * self.voxel_size
 
 
 def load_pc(pc):
@@ -152,7 +159,8 @@ def evaluate(pipe, clouds, cfg=None, pairs_per_batch=16, seed=None, force_gate=F
                                [(2 * (s + i), 2 * (s + i) + 1) for i in range(P)], 100,
                                cfg.ransac_max_iter, cfg.ransac_confidence, True, force_gate, None,
                                cfg.icp_max_iter, cfg.icp_distance() if icp_on else None, cfg.icp_estimation,
-                               cfg.icp_normal_k)
+                               cfg.icp_normal_k, None, cfg.icp_kernel,
+                               cfg.icp_scale() if cfg.icp_kernel != "l2" else None)
         Tb, Tr = res.T_best.cpu().numpy(), res.T_ransac.cpu().numpy()
         cdb, cdr = res.cd_best.cpu().numpy(), res.cd_ransac.cpu().numpy()
         for i, (mi, pi, _, _, pose, label) in enumerate(chunk):
@@ -232,12 +240,8 @@ def summary(results):
     return "\n".join(lines)
 
 
-def main(argv=None):
+def build_parser():
     import argparse
-    import os
-
-    from . import harness
-    from .utils import ckpts
 
     ap = argparse.ArgumentParser(prog="python -m corsair_amd.shapenet_eval",
                                  description="Registration evaluation with synthetic poses on a directory of .npy clouds "
@@ -259,9 +263,23 @@ def main(argv=None):
     ap.add_argument("--icp-max-dist", type=float, default=0.0, help="ICP correspondence distance; 0 = 2 * voxel size")
     ap.add_argument("--icp-estimation", default="point", choices=["point", "plane"])
     ap.add_argument("--icp-normal-k", type=int, default=16)
+    ap.add_argument("--icp-kernel", default="l2", choices=["l2", "huber", "cauchy", "tukey"],
+                    help="robust kernel on the point-to-plane residual (needs --icp-estimation plane); l2 = none")
+    ap.add_argument("--icp-kernel-scale", type=float, default=0.0, help="scale of --icp-kernel; 0 = 1 * voxel size (untuned)")
     ap.add_argument("--out-dir", default=".")
     ap.add_argument("--device", default="cuda", choices=["cuda"])
-    a = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None):
+    import os
+
+    from . import harness
+    from .utils import ckpts
+
+    a = build_parser().parse_args(argv)
+    if a.icp_kernel != "l2" and a.icp_estimation != "plane":
+        raise SystemExit("--icp-kernel %s needs --icp-estimation plane" % a.icp_kernel)
     if not a.data_dir:
         if not a.shapenet_root:
             raise SystemExit("give --data-dir, or --shapenet-root with --category")
@@ -276,7 +294,8 @@ def main(argv=None):
     cfg = Config(random_seed=a.random_seed, n_poses_per_model=a.n_poses_per_model, max_roll_deg=a.max_roll_deg,
                  max_pitch_deg=a.max_pitch_deg, max_yaw_deg=a.max_yaw_deg, max_translation=a.max_translation,
                  ransac_max_iter=a.ransac_max_iter, icp_max_iter=a.icp_iters, icp_max_dist=a.icp_max_dist,
-                 icp_estimation=a.icp_estimation, icp_normal_k=a.icp_normal_k)
+                 icp_estimation=a.icp_estimation, icp_normal_k=a.icp_normal_k, icp_kernel=a.icp_kernel,
+                 icp_kernel_scale=a.icp_kernel_scale)
     results = evaluate(pipe, clouds, cfg)
     postfix = f"shapenet-seed{a.random_seed}-{a.category}-{len(files)}-{a.n_poses_per_model}"
     os.makedirs(a.out_dir, exist_ok=True)

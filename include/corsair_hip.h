@@ -569,6 +569,47 @@ int cs_icp_plane_batch(const float* d_src, const int64_t* h_soff, const float* d
                        int32_t* d_corr, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * cs_icp_plane_robust_batch: cs_icp_plane_batch with a robust kernel on the point-to-plane residual, the RobustKernel
+ * argument of Open3D's TransformationEstimationPointToPlane (tests/icp_robust_ref.py restates it bit for bit).
+ * The arguments are those of cs_icp_plane_batch plus `kernel` (CS_ICP_KERNEL_*), `kernel_scale` (k) and one more optional
+ * output, d_wfitness f64 [n_prob].  Everything not said here -- problems, pose chain, association on both paths, evaluation,
+ * loop, stop rules, outputs, independence, empty segments, stream behaviour -- is cs_icp_plane_batch's: the same code.
+ *   Weight of a kept pair, from r of cs_icp_plane_batch, a = |r|, k = kernel_scale, every operation ONE IEEE f64 operation
+ *   ([O3D-knowledge]: Open3D's HuberLoss, CauchyLoss and TukeyLoss::Weight as remembered; not checked against Open3D):
+ *       L2:      w = 1
+ *       Huber:   w = (a <= k) ? 1 : k / a
+ *       Cauchy:  q = r / k;  w = 1 / (1 + q * q)
+ *       Tukey:   if (!(a < k)) w = 0;  else { q = r / k;  e = 1 - q * q;  w = e * e; }
+ *     and a w that is NaN becomes 0.  (Open3D's GM and L1 kernels are left out on purpose: their weights, k / (k + r^2)^2
+ *     with k < 1 and 1 / |r|, are not bounded by 1 and the bound below would not hold.)
+ *   Sums: 30 signed 64-bit integers, the 29 of cs_icp_plane_batch and one more.  Each of the 27 products J_i * J_j and
+ *     J_i * r is rounded to f64 as there, THEN multiplied by w (one more rounding), then scaled by its class's power of two,
+ *     clamped to +-2^(61 - eN) and truncated.  The count and I(d2 * 2^s2) stay unweighted: fitness, rmse and n_corr are
+ *     Open3D's evaluation, the numbers cs_icp_plane_batch returns for the same pose.  The 30th sum is I(w * 2^(61 - eN)).
+ *     Bound: 0 <= w <= 1 and rounding is monotone, so |fl(x * w)| <= |x|: no weighted term is larger than the unweighted
+ *     term that cs_icp_plane_batch bounds, and the 30th sum has at most 2^eN terms of at most 2^(61 - eN).  Nothing leaves
+ *     2^61, and the clamp keeps that true for any input.
+ *   d_wfitness = ((double)sum_w * 2^-(61 - eN)) / n_src of the last evaluation: the weighted inlier share (0 for an empty
+ *     source segment; equal to the fitness with L2).
+ *   Update and stop rules: cs_icp_plane_batch's on the weighted A and b.  When every weight is 0 (Tukey with every
+ *     |r| >= k) A is exactly zero, the first pivot fails cs_icp_plane_batch's pivot rule and the problem stops after that
+ *     evaluation: T = T0 when it is the first, 0 updates, wfitness 0.
+ *   kernel = CS_ICP_KERNEL_L2 runs cs_icp_plane_batch's code and returns its bits; kernel_scale is ignored then.
+ *   Refused (CS_ERR_INVALID) in addition: kernel outside 0..3; kernel_scale not finite or <= 0 while kernel != L2.
+ * Profile family "icp".
+ * ---------------------------------------------------------------------------------------- */
+#define CS_ICP_KERNEL_L2 0
+#define CS_ICP_KERNEL_HUBER 1
+#define CS_ICP_KERNEL_CAUCHY 2
+#define CS_ICP_KERNEL_TUKEY 3
+int cs_icp_plane_robust_batch(const float* d_src, const int64_t* h_soff, const float* d_tgt, const float* d_tgt_normal,
+                              const int64_t* h_toff, const int32_t* h_src_seg, const int32_t* h_tgt_seg, int n_prob,
+                              const float* d_T0, double max_dist, int max_iter, double relative_fitness,
+                              double relative_rmse, int kernel, double kernel_scale, double* d_T, float* d_T32,
+                              double* d_fitness, double* d_rmse, double* d_wfitness, int32_t* d_iters, int32_t* d_ncorr,
+                              int32_t* d_corr, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * cs_estimate_normals: one surface normal per row from the k nearest rows of the row's own segment, the semantics of
  * [O3D-knowledge] Open3D's PointCloud::estimate_normals(KDTreeSearchParamKNN(k)): the eigenvector of the smallest
  * eigenvalue of the neighbourhood's covariance.  The reference has no such step, so this comment is the specification

@@ -18,6 +18,14 @@ one registration step (embed 32 queries, sym_pose_batch against their CADs) with
 above, (p) the point-to-plane call (cs_icp_plane_batch) with the target normals supplied, (n) backend.estimate_normals of
 the 32 targets over --normal-k neighbours; with the updates per problem, the time per round, the fallback share and the
 pose errors of both.  `--start large` is the 12 degree / 5 cm start with max_dist 0.12 (default: 3 degrees / 1 cm, 0.06).
+
+`--kernel huber|cauchy|tukey [--kernel-scale K]` (K defaults to one voxel, untuned) measures, alternating in one
+process on the same problems: (l2) the point-to-plane call above and (k) cs_icp_plane_robust_batch with that kernel; per
+call ms, updates, ms per round (DESIGN 13's definition, ms / (most updates + 1), and -- the cleaner figure -- a run of
+exactly 11 full rounds: max_iter 10 with both convergence thresholds 0), mean RRE / RTE and the fallback share.
+`--clutter F` makes the share F of every source clutter first: rows of the pair's target displaced by 0.035 / 0.06 of
+max_dist along +x or +y (two slabs just off the surface, every row inside max_dist of a target row), moved into the
+source's frame.  Without --json the result goes to profiles/icp_robust_<kernel>[_clutter].json.
 Prints one JSON line."""
 import argparse
 import json
@@ -183,6 +191,73 @@ def plane_report(a, res, x0, off0, x1, off1, T0, truth, max_dist):
     return res
 
 
+def add_clutter(x0, off0, x1, off1, truth, share, max_dist):
+    """Sources of which `share` is clutter: per pair, rows of the target shifted by 0.035 / 0.06 * max_dist along +x (half)
+    or +y (half) and moved by the inverse of the true pose (query -> CAD) into the query's frame."""
+    rng = np.random.default_rng(14)
+    s, t = x0.cpu().numpy().astype(np.float64), x1.cpu().numpy().astype(np.float64)
+    shift = 0.035 / 0.06 * max_dist
+    parts, off = [], [0]
+    for p in range(len(off0) - 1):
+        src, tgt = s[off0[p]:off0[p + 1]], t[off1[p]:off1[p + 1]]
+        n = int(round(share / (1.0 - share) * len(src)))
+        rows = tgt[rng.integers(0, len(tgt), n)].copy()
+        rows[:n // 2, 0] += shift
+        rows[n // 2:, 1] += shift
+        Tinv = np.linalg.inv(truth[p])
+        parts += [src, rows @ Tinv[:3, :3].T + Tinv[:3, 3]]
+        off.append(off[-1] + len(src) + n)
+    return torch.from_numpy(np.concatenate(parts).astype(np.float32)).to(x0.device), off
+
+
+def robust_report(a, res, x0, off0, x1, off1, T0, truth, max_dist):
+    """The measurement of DESIGN 14: (l2) the plane call and (k) the call with a robust kernel, alternating."""
+    pairs = list(range(N_PAIRS))
+    scale = a.kernel_scale if a.kernel_scale > 0 else VOXEL
+    if a.clutter > 0:
+        x0, off0 = add_clutter(x0, off0, x1, off1, truth, a.clutter, max_dist)
+    nrm = B.estimate_normals(x1, off1, a.normal_k)
+    kw = {"l2": {}, a.kernel: {"kernel": a.kernel, "kernel_scale": scale}}
+
+    def call(k, max_iter=MAX_ITER, **more):
+        return B.icp_batch(x0, off0, x1, off1, pairs, pairs, T0, max_dist, max_iter, tgt_normals=nrm, **kw[k], **more)
+
+    full = dict(relative_fitness=0.0, relative_rmse=0.0)           # no problem converges: max_iter + 1 full rounds
+    ms = timed_alternating({"l2": lambda: call("l2"), a.kernel: lambda: call(a.kernel),
+                            "l2_full": lambda: call("l2", 10, **full), a.kernel + "_full": lambda: call(a.kernel, 10, **full)},
+                           a.reps)
+    res.update({"estimation": "plane", "normal_k": a.normal_k, "kernel": a.kernel, "kernel_scale": scale,
+                "clutter": a.clutter, "source_rows": off0[-1]})
+
+    def errs(T):
+        T = T.cpu().numpy().astype(np.float64)
+        rre = [np.degrees(np.arccos(np.clip((np.trace(T[p, :3, :3] @ truth[p, :3, :3].T) - 1) / 2, -1, 1))) for p in pairs]
+        rte = [np.linalg.norm(T[p, :3, 3] - truth[p, :3, 3]) for p in pairs]
+        return round(float(np.mean(rre)), 4), round(float(np.mean(rte)), 5)
+
+    res["rre_deg_rte_before"] = errs(T0)
+    os.environ["CS_ICP_STATS"] = "1"
+    for k in ("l2", a.kernel):
+        B.icp_stats(reset=True)
+        r = call(k)
+        st = B.icp_stats(reset=True)
+        it = r.iters.cpu().numpy()
+        full_it = call(k, 10, **full).iters.cpu().numpy()
+        res[k] = {"ms": ms[k], "updates": {"mean": round(float(it.mean()), 2), "min": int(it.min()), "max": int(it.max())},
+                  "ms_per_round": round(ms[k] / (float(it.max()) + 1), 4),
+                  "full_rounds_ms": ms[k + "_full"], "full_rounds_updates_min": int(full_it.min()),
+                  "full_rounds_ms_per_round": round(ms[k + "_full"] / 11.0, 4),
+                  "fallback_share": round(st[1] / max(st[0], 1), 5), "rre_deg_rte_after": errs(r.T),
+                  "fitness_mean": round(float(r.fitness.mean()), 4),
+                  "wfitness_mean": None if r.wfitness is None else round(float(r.wfitness.mean()), 4)}
+    del os.environ["CS_ICP_STATS"]
+    res["kernel_over_l2_per_round"] = round(res[a.kernel]["ms_per_round"] / res["l2"]["ms_per_round"], 4)
+    res["kernel_over_l2_per_full_round"] = round(res[a.kernel]["full_rounds_ms_per_round"] /
+                                                 res["l2"]["full_rounds_ms_per_round"], 4)
+    res["bar_kernel_le_1p10_l2_per_round"] = bool(res["kernel_over_l2_per_round"] <= 1.10)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--json", default=None)
@@ -195,7 +270,14 @@ def main():
     ap.add_argument("--normal-k", type=int, default=16)
     ap.add_argument("--start", default="small", choices=["small", "large"],
                     help="large: 12 degrees / 5 cm with max_dist 0.12 (overrides --deg / --trans)")
+    ap.add_argument("--kernel", default="l2", choices=["l2", "huber", "cauchy", "tukey"],
+                    help="a robust kernel: the plane call against cs_icp_plane_robust_batch with it, alternating (DESIGN 14)")
+    ap.add_argument("--kernel-scale", type=float, default=0.0, help="scale of --kernel; 0 = one voxel (untuned)")
+    ap.add_argument("--clutter", type=float, default=0.0,
+                    help="share of every source that is clutter just off the target's surface (with --kernel)")
     a = ap.parse_args()
+    if not 0.0 <= a.clutter < 1.0 or (a.clutter > 0 and a.kernel == "l2"):
+        ap.error("--clutter needs a share in [0, 1) and a --kernel")
     dev = torch.device("cuda:0")
     max_dist = 2 * VOXEL
     if a.start == "large":
@@ -205,6 +287,13 @@ def main():
     res = {"device": torch.cuda.get_device_name(dev), "hip": torch.version.hip, "pairs": N_PAIRS, "voxel": VOXEL,
            "source_rows": off0[-1], "target_rows": off1[-1], "max_dist": max_dist, "max_iter": MAX_ITER,
            "perturbation": {"deg": a.deg, "trans": a.trans}}
+    if a.kernel != "l2":
+        res = robust_report(a, res, x0, off0, x1, off1, T0, truth, max_dist)
+        print(json.dumps(res))
+        path = a.json or os.path.join(ROOT, "profiles", "icp_robust_%s%s.json" % (a.kernel, "_clutter" if a.clutter > 0 else ""))
+        with open(path, "w") as f:
+            json.dump(res, f, indent=1)
+        return
     if a.estimation == "plane":
         res = plane_report(a, res, x0, off0, x1, off1, T0, truth, max_dist)
         print(json.dumps(res))
