@@ -487,17 +487,31 @@ class IcpResult(NamedTuple):
 ICP_KERNELS = {"l2": 0, "huber": 1, "cauchy": 2, "tukey": 3}    # CS_ICP_KERNEL_*
 
 
-def estimate_normals(xyz, offsets, k=16):
+def estimate_normals(xyz, offsets, k=16, radius=None):
     """cs_estimate_normals: one normal per row (f32 [n,3] device) from the k nearest rows of the row's own segment
-    (host offset list); 3 <= k <= 32.  The semantics are the header comment of cs_estimate_normals.  No host wait."""
+    (host offset list); 3 <= k <= 32.  The semantics are the header comment of cs_estimate_normals.  With a `radius`:
+    cs_estimate_normals_hybrid, the at most k nearest rows strictly inside the radius (k is Open3D's max_nn).  No host
+    wait."""
     xyz = _dev(xyz, torch.float32, "points").contiguous()
     if xyz.dim() != 2 or xyz.shape[1] != 3:
         raise ValueError("estimate_normals: points must be [n, 3]")
     if len(offsets) < 1 or int(offsets[-1]) > xyz.shape[0]:
         raise ValueError("estimate_normals: the offset table exceeds the point array")
     out = torch.empty_like(xyz)
-    check(_lib.load().cs_estimate_normals(ptr(xyz), i64_array(offsets), len(offsets) - 1, int(k), ptr(out), stream_ptr()))
+    if radius is None:
+        check(_lib.load().cs_estimate_normals(ptr(xyz), i64_array(offsets), len(offsets) - 1, int(k), ptr(out), stream_ptr()))
+    else:
+        check(_lib.load().cs_estimate_normals_hybrid(ptr(xyz), i64_array(offsets), len(offsets) - 1, float(radius), int(k),
+                                                     ptr(out), stream_ptr()))
     return out
+
+
+def normals_stats(reset=False):
+    """cs_normals_stats: (rows answered by a cell-grid path, of those recomputed by the exhaustive scan); counts only
+    under CS_NORMALS_STATS=1."""
+    out = (ctypes.c_uint64 * 2)()
+    _lib.load().cs_normals_stats(out, 1 if reset else 0)
+    return int(out[0]), int(out[1])
 
 
 def icp_batch(src, soff, tgt, toff, src_seg, tgt_seg, T0, max_dist, max_iter=30, relative_fitness=1e-6,

@@ -5,14 +5,14 @@
 //
 // Radius search: the target rows of every problem are sorted by (problem, cell) with cell = floor(t / c), c slightly
 // larger than r; an open-addressing table maps a cell to its [begin, end) range of the sorted rows; every source row
-// probes the 27 neighbouring cells (complete, because |s - t| < r puts the two cells at most one apart).  Cells are
-// clamped to the 16-bit key range: clamping is monotone, so neighbours stay neighbours (or share a cell) and the
-// search stays exact for any coordinates, only slower for far-out points.
+// probes the 27 neighbouring cells.  The cell function, the table and the probe are cellgrid.h's (shared with
+// normals.hip), with the completeness argument and the clamp to the 16-bit key range; the distance chain rp_d2 is this
+// unit's own.
 #include <hipcub/hipcub.hpp>
 
 #include <vector>
 
-#include "common.h"
+#include "cellgrid.h"
 
 namespace cs {
 namespace {
@@ -26,23 +26,13 @@ struct RPProb {
 
 constexpr int kSmallRow = 32;   // rows with at most this many hits are sorted in private memory
 
-__device__ __forceinline__ int rp_cell(double x, double cell) {
-  double q = floor(x / cell);
-  if (!(q >= -32767.0)) q = -32767.0;   // also NaN: such a point never passes d2 < r2
-  if (q > 32767.0) q = 32767.0;
-  return (int)q;
-}
-
 __device__ __forceinline__ double rp_d2(double sx, double sy, double sz, double tx, double ty, double tz) {
   const double dx = sx - tx, dy = sy - ty, dz = sz - tz;
   return (dx * dx + dy * dy) + dz * dz;   // -ffp-contract=off: no fma
 }
 
 struct RPTable {
-  const uint64_t* keys;
-  const int32_t* beg;
-  const int32_t* end;
-  uint64_t mask;
+  CellTable cells;
   const double* xyz;   // sorted target rows [M,3]
   const int32_t* j;    // local target index of every sorted row
 };
@@ -51,23 +41,9 @@ struct RPTable {
 template <typename F>
 __device__ __forceinline__ void rp_probe(const RPTable& tb, int p, double sx, double sy, double sz, double cell,
                                          double r2, F&& f) {
-  const int cx = rp_cell(sx, cell), cy = rp_cell(sy, cell), cz = rp_cell(sz, cell);
-  for (int dz = -1; dz <= 1; ++dz)
-    for (int dy = -1; dy <= 1; ++dy)
-      for (int dx = -1; dx <= 1; ++dx) {
-        const int x = cx + dx, y = cy + dy, z = cz + dz;
-        if (x < -32767 || x > 32767 || y < -32767 || y > 32767 || z < -32767 || z > 32767) continue;
-        const uint64_t key = pack_key(p, x, y, z);
-        uint64_t slot = hash64(key) & tb.mask;
-        uint64_t k;
-        while ((k = tb.keys[slot]) != key && k != kEmptyKey) slot = (slot + 1) & tb.mask;
-        if (k != key) continue;
-        const int32_t e = tb.end[slot];
-        for (int32_t m = tb.beg[slot]; m < e; ++m) {
-          const double d2 = rp_d2(sx, sy, sz, tb.xyz[3 * m], tb.xyz[3 * m + 1], tb.xyz[3 * m + 2]);
-          if (d2 < r2) f(d2, tb.j[m]);
-        }
-      }
+  cg_probe<3>(
+      tb.cells, tb.xyz, p, sx, sy, sz, cell, r2, [&](const double* t) { return rp_d2(sx, sy, sz, t[0], t[1], t[2]); },
+      [&](double d2, int32_t m) { f(d2, tb.j[m]); });
 }
 
 __global__ void k_rp_keys(const RPProb* __restrict__ probs, const double* __restrict__ tgt, double cell,
@@ -77,7 +53,7 @@ __global__ void k_rp_keys(const RPProb* __restrict__ probs, const double* __rest
   const int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (j >= P.nt) return;
   const double* t = tgt + 3 * (P.t0 + j);
-  keys[P.m0 + j] = pack_key(p, rp_cell(t[0], cell), rp_cell(t[1], cell), rp_cell(t[2], cell));
+  keys[P.m0 + j] = pack_key(p, cg_cell(t[0], cell), cg_cell(t[1], cell), cg_cell(t[2], cell));
   vals[P.m0 + j] = (int32_t)j;
 }
 
@@ -93,12 +69,12 @@ __global__ void k_rp_gather(const RPProb* __restrict__ probs, const double* __re
   xyz[3 * m + 2] = t[2];
 }
 
-__global__ void k_rp_table_fill(uint64_t* keys, uint64_t cap) {
+__global__ void k_cg_table_fill(uint64_t* keys, uint64_t cap) {
   for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < cap; i += (uint64_t)gridDim.x * blockDim.x)
     keys[i] = kEmptyKey;
 }
 
-__device__ __forceinline__ uint64_t rp_insert(uint64_t* keys, uint64_t mask, uint64_t key) {
+__device__ __forceinline__ uint64_t cg_insert(uint64_t* keys, uint64_t mask, uint64_t key) {
   uint64_t slot = hash64(key) & mask;
   while (true) {
     const unsigned long long old = atomicCAS((unsigned long long*)&keys[slot], (unsigned long long)kEmptyKey,
@@ -109,13 +85,13 @@ __device__ __forceinline__ uint64_t rp_insert(uint64_t* keys, uint64_t mask, uin
 }
 
 // every run of equal keys (one cell of one problem) gets its [begin, end) range
-__global__ void k_rp_insert(const uint64_t* __restrict__ skeys, int64_t m_total, uint64_t* keys, int32_t* beg,
+__global__ void k_cg_insert(const uint64_t* __restrict__ skeys, int64_t m_total, uint64_t* keys, int32_t* beg,
                             int32_t* end, uint64_t mask) {
   const int64_t m = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (m >= m_total) return;
   const uint64_t k = skeys[m];
-  if (m == 0 || skeys[m - 1] != k) beg[rp_insert(keys, mask, k)] = (int32_t)m;
-  if (m == m_total - 1 || skeys[m + 1] != k) end[rp_insert(keys, mask, k)] = (int32_t)(m + 1);
+  if (m == 0 || skeys[m - 1] != k) beg[cg_insert(keys, mask, k)] = (int32_t)m;
+  if (m == m_total - 1 || skeys[m + 1] != k) end[cg_insert(keys, mask, k)] = (int32_t)(m + 1);
 }
 
 __global__ void k_rp_count(const RPProb* __restrict__ probs, const double* __restrict__ src, RPTable tb,
@@ -371,10 +347,20 @@ void plan_release(cs_radius_plan* pl) {
 }
 
 RPTable plan_table(const cs_radius_plan* pl) {
-  return RPTable{pl->d_tkeys, pl->d_tbeg, pl->d_tend, pl->cap - 1, pl->d_xyz, pl->d_j};
+  return RPTable{CellTable{pl->d_tkeys, pl->d_tbeg, pl->d_tend, pl->cap - 1}, pl->d_xyz, pl->d_j};
 }
 
 }  // namespace
+
+// the launchers of cellgrid.h
+void cellgrid_table_fill(uint64_t* d_keys, uint64_t cap, hipStream_t s) {
+  hipLaunchKernelGGL(k_cg_table_fill, dim3((unsigned)(cap / 256 < 2048 ? cap / 256 : 2048)), dim3(256), 0, s, d_keys, cap);
+}
+void cellgrid_insert_ranges(const uint64_t* d_skeys, int64_t m_total, uint64_t* d_keys, int32_t* d_beg, int32_t* d_end,
+                            uint64_t mask, hipStream_t s) {
+  hipLaunchKernelGGL(k_cg_insert, dim3((unsigned)ceil_div(m_total, 256)), dim3(256), 0, s, d_skeys, m_total, d_keys, d_beg,
+                     d_end, mask);
+}
 }  // namespace cs
 
 using namespace cs;
@@ -441,8 +427,7 @@ int cs_radius_pairs(const double* d_src, const int64_t* h_soff, const double* d_
   hipError_t e = hipMemcpyAsync(pl->d_probs, hp.data(), sizeof(RPProb) * n_prob, hipMemcpyHostToDevice, s);
   if (e == hipSuccess) e = hipMemsetAsync(cnt.p, 0, sizeof(int64_t) * (rows + 1), s);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_rp_table_fill, dim3((unsigned)(pl->cap / 256 < 2048 ? pl->cap / 256 : 2048)), dim3(256), 0,
-                       s, pl->d_tkeys, pl->cap);
+    cellgrid_table_fill(pl->d_tkeys, pl->cap, s);
     e = hipGetLastError();
   }
   if (e == hipSuccess && m_total > 0) {
@@ -458,8 +443,7 @@ int cs_radius_pairs(const double* d_src, const int64_t* h_soff, const double* d_
       const unsigned g = (unsigned)ceil_div(m_total, 256);
       hipLaunchKernelGGL(k_rp_gather, dim3(g), dim3(256), 0, s, pl->d_probs, d_tgt, skeys.p, pl->d_j, m_total,
                          pl->d_xyz);
-      hipLaunchKernelGGL(k_rp_insert, dim3(g), dim3(256), 0, s, skeys.p, m_total, pl->d_tkeys, pl->d_tbeg,
-                         pl->d_tend, pl->cap - 1);
+      cellgrid_insert_ranges(skeys.p, m_total, pl->d_tkeys, pl->d_tbeg, pl->d_tend, pl->cap - 1, s);
       e = hipGetLastError();
     }
   }

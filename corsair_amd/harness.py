@@ -50,6 +50,9 @@ class Config:
     # icp_normal_k neighbours).  16 is UNTUNED: 8 and 16 behaved alike in the experiment that motivated it
     icp_estimation: str = "point"
     icp_normal_k: int = 16
+    # 0.0 = those k nearest rows (the default); > 0: the at most icp_normal_k nearest rows strictly inside this radius
+    # (cs_estimate_normals_hybrid), in the units of the clouds.  NO RADIUS HAS BEEN TUNED
+    icp_normal_radius: float = 0.0
     # robust kernel of the plane estimation: "l2" (none), "huber", "cauchy" or "tukey" (cs_icp_plane_robust_batch).
     # icp_kernel_scale = 0.0 means 1 * voxel_size -- the size of the residual a voxel grid leaves on a matching surface,
     # which NOBODY HAS TUNED; set it explicitly for real data
@@ -71,6 +74,12 @@ class Config:
             raise ValueError("Config.icp_kernel %r needs icp_estimation = 'plane'" % (self.icp_kernel,))
         if not 3 <= int(self.icp_normal_k) <= 32:
             raise ValueError("Config.icp_normal_k must lie in [3, 32], got %r" % (self.icp_normal_k,))
+        if not 0 <= float(self.icp_normal_radius) < float("inf"):
+            raise ValueError("Config.icp_normal_radius must be finite and >= 0 (0 = k-NN), got %r"
+                             % (self.icp_normal_radius,))
+
+    def normal_radius(self):
+        return float(self.icp_normal_radius) if self.icp_normal_radius > 0 else None
 
     def icp_plane(self):
         """True when the run refines with the point-to-plane estimation (and so needs the CAD voxels' normals)."""
@@ -197,15 +206,16 @@ class Pipeline:
                                 cads.offsets, syms, c.k_nn, c.max_corr, 0, anchor_ids, 100,
                                 c.ransac_max_iter, c.ransac_confidence, use_symmetry, force_gate,
                                 query_anchors, c.icp_max_iter, c.icp_distance() if c.icp_max_iter > 0 else None,
-                                c.icp_estimation, c.icp_normal_k, cads.normal, c.icp_kernel,
+                                c.icp_estimation, c.icp_normal_k, cads.normal, c.normal_radius(), c.icp_kernel,
                                 c.icp_scale() if c.icp_kernel != "l2" else None)
 
     def with_normals(self, s):
-        """`s` with the normals of its origins (one cs_estimate_normals call over the whole set) when the configuration
-        refines point-to-plane and the set has none yet; `s` itself otherwise."""
+        """`s` with the normals of its origins (one cs_estimate_normals call over the whole set, or one
+        cs_estimate_normals_hybrid call when the configuration has an icp_normal_radius) when the configuration refines
+        point-to-plane and the set has none yet; `s` itself otherwise."""
         if not self.cfg.icp_plane() or s.normal is not None:
             return s
-        return EmbeddedSet(s.F, s.origin, s.offsets, s.desc, B.estimate_normals(s.origin, s.offsets, self.cfg.icp_normal_k))
+        return EmbeddedSet(s.F, s.origin, s.offsets, s.desc, B.estimate_normals(s.origin, s.offsets, self.cfg.icp_normal_k, self.cfg.normal_radius()))
 
 
 def concat_sets(sets):
@@ -572,6 +582,8 @@ def build_parser():
                     help="ICP estimation: point-to-point, or point-to-plane on the CAD voxels' normals")
     ap.add_argument("--icp-normal-k", type=int, default=16,
                     help="neighbours of a CAD voxel's normal for --icp-estimation plane, 3..32 (an untuned default)")
+    ap.add_argument("--icp-normal-radius", type=float, default=0.0,
+                    help="radius of the normals' hybrid search (at most --icp-normal-k rows inside it); 0 = k-NN.  Untuned")
     ap.add_argument("--icp-kernel", default="l2", choices=list(ICP_KERNEL_NAMES),
                     help="robust kernel on the point-to-plane residual (needs --icp-estimation plane); l2 = none")
     ap.add_argument("--icp-kernel-scale", type=float, default=0.0,
@@ -598,7 +610,7 @@ def main(argv=None):
     cfg = Config(n_points=a.n_points, batch_size=a.batch_size, embed_batch_size=a.embed_batch_size,
                  ransac_max_iter=a.ransac_max_iter, icp_max_iter=a.icp_iters, icp_max_dist=a.icp_max_dist,
                  icp_estimation=a.icp_estimation, icp_normal_k=a.icp_normal_k, icp_kernel=a.icp_kernel,
-                 icp_kernel_scale=a.icp_kernel_scale)
+                 icp_kernel_scale=a.icp_kernel_scale, icp_normal_radius=a.icp_normal_radius)
     cfg.check_icp()
     pipe = Pipeline(sd, esd, device=a.device, config=cfg)
     cad_names, catalog = load_cloud_dir(a.catalog_dir, a.n_points, "catalog")

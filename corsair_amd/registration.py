@@ -152,7 +152,8 @@ def part_configs(K, pos_sym):
 def sym_pose_batch(baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_nn=5, max_corr=0.20, seed=0,
                    anchor_ids=None, n_anchor=100, max_iter=100000, confidence=0.999,
                    use_symmetry=True, force_gate=False, query_anchors=None, icp_max_iter=0, icp_max_dist=None,
-                   icp_estimation="point", icp_normal_k=16, normals1=None, icp_kernel="l2", icp_kernel_scale=None):
+                   icp_estimation="point", icp_normal_k=16, normals1=None, icp_normal_radius=None, icp_kernel="l2",
+                   icp_kernel_scale=None):
     """baseF f32 [N0,16], xyz0 f32 [N0,3] (query voxels of all pairs, segment p = off0[p]:off0[p+1]);
     posF/xyz1/off1 likewise for the CAD side; pos_syms: symmetry label per pair.
     anchor_ids[p] = (counter0, counter1) seeds the anchor draw of pair p (default (2p, 2p+1)).
@@ -164,7 +165,8 @@ def sym_pose_batch(baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_nn=5, max_co
     result's T_icp / cd_icp / icp_* fields are filled; with the default 0 nothing is launched.
     icp_estimation = "plane": the refinement is point-to-plane (cs_icp_plane_batch) on the normals of the CAD voxels,
     normals1 f32 [N1,3] when the caller has them (a catalog's are computed once), else cs_estimate_normals over
-    icp_normal_k neighbours here; the same result fields are filled.
+    icp_normal_k neighbours here; the same result fields are filled.  icp_normal_radius (None = k-NN): those normals
+    come from the at most icp_normal_k nearest rows strictly inside that radius instead (cs_estimate_normals_hybrid).
     icp_kernel = "huber" / "cauchy" / "tukey" with icp_kernel_scale > 0 (plane estimation only): the residuals are weighted
     by that robust kernel (cs_icp_plane_robust_batch) and icp_wfitness is filled too."""
     if icp_kernel not in B.ICP_KERNELS:
@@ -175,6 +177,9 @@ def sym_pose_batch(baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_nn=5, max_co
         raise ValueError("sym_pose_batch: icp_kernel %r needs a positive icp_kernel_scale" % (icp_kernel,))
     if icp_estimation not in ("point", "plane"):
         raise ValueError("sym_pose_batch: icp_estimation must be 'point' or 'plane', got %r" % (icp_estimation,))
+    if icp_normal_radius is not None and not (0 < icp_normal_radius < float("inf")):
+        raise ValueError("sym_pose_batch: icp_normal_radius must be positive and finite (None = k-NN), got %r"
+                         % (icp_normal_radius,))
     if icp_max_iter > 0 and not (icp_max_dist is not None and icp_max_dist > 0):
         raise ValueError("sym_pose_batch: icp_max_iter > 0 needs a positive icp_max_dist")
     dev = baseF.device
@@ -334,7 +339,7 @@ def sym_pose_batch(baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_nn=5, max_co
         pairs = list(range(P))
         nrm = None
         if icp_estimation == "plane":
-            nrm = normals1 if normals1 is not None else B.estimate_normals(xyz1, off1, icp_normal_k)
+            nrm = normals1 if normals1 is not None else B.estimate_normals(xyz1, off1, icp_normal_k, icp_normal_radius)
         r = B.icp_batch(xyz0, off0, xyz1, off1, pairs, pairs, res.T_best, icp_max_dist, icp_max_iter, tgt_normals=nrm,
                         kernel=icp_kernel, kernel_scale=icp_kernel_scale)
         res.T_icp, res.icp_fitness, res.icp_rmse, res.icp_iters = r.T32, r.fitness, r.rmse, r.iters

@@ -39,6 +39,8 @@ class Config:
     icp_max_dist: float = 0.0
     icp_estimation: str = "point"
     icp_normal_k: int = 16
+    # 0.0 = k-NN (the default); > 0: the at most icp_normal_k nearest rows strictly inside this radius (UNTUNED)
+    icp_normal_radius: float = 0.0
     # robust kernel of the plane estimation ("l2" = none, "huber", "cauchy", "tukey"); icp_kernel_scale = 0.0 means
     # 1 * voxel_size (UNTUNED, as in harness.Config)
     icp_kernel: str = "l2"
@@ -49,6 +51,12 @@ class Config:
 
     def icp_scale(self):
         return self.icp_kernel_scale if self.icp_kernel_scale > 0 else 1.0 * self.voxel_size
+
+    def normal_radius(self):
+        if not 0 <= float(self.icp_normal_radius) < float("inf"):
+            raise ValueError("Config.icp_normal_radius must be finite and >= 0 (0 = k-NN), got %r"
+                             % (self.icp_normal_radius,))
+        return float(self.icp_normal_radius) if self.icp_normal_radius > 0 else None
 
 
 def load_pc(pc):
@@ -159,7 +167,7 @@ def evaluate(pipe, clouds, cfg=None, pairs_per_batch=16, seed=None, force_gate=F
                                [(2 * (s + i), 2 * (s + i) + 1) for i in range(P)], 100,
                                cfg.ransac_max_iter, cfg.ransac_confidence, True, force_gate, None,
                                cfg.icp_max_iter, cfg.icp_distance() if icp_on else None, cfg.icp_estimation,
-                               cfg.icp_normal_k, None, cfg.icp_kernel,
+                               cfg.icp_normal_k, None, cfg.normal_radius(), cfg.icp_kernel,
                                cfg.icp_scale() if cfg.icp_kernel != "l2" else None)
         Tb, Tr = res.T_best.cpu().numpy(), res.T_ransac.cpu().numpy()
         cdb, cdr = res.cd_best.cpu().numpy(), res.cd_ransac.cpu().numpy()
@@ -263,6 +271,8 @@ def build_parser():
     ap.add_argument("--icp-max-dist", type=float, default=0.0, help="ICP correspondence distance; 0 = 2 * voxel size")
     ap.add_argument("--icp-estimation", default="point", choices=["point", "plane"])
     ap.add_argument("--icp-normal-k", type=int, default=16)
+    ap.add_argument("--icp-normal-radius", type=float, default=0.0,
+                    help="radius of the normals' hybrid search (at most --icp-normal-k rows inside it); 0 = k-NN (untuned)")
     ap.add_argument("--icp-kernel", default="l2", choices=["l2", "huber", "cauchy", "tukey"],
                     help="robust kernel on the point-to-plane residual (needs --icp-estimation plane); l2 = none")
     ap.add_argument("--icp-kernel-scale", type=float, default=0.0, help="scale of --icp-kernel; 0 = 1 * voxel size (untuned)")
@@ -295,7 +305,7 @@ def main(argv=None):
                  max_pitch_deg=a.max_pitch_deg, max_yaw_deg=a.max_yaw_deg, max_translation=a.max_translation,
                  ransac_max_iter=a.ransac_max_iter, icp_max_iter=a.icp_iters, icp_max_dist=a.icp_max_dist,
                  icp_estimation=a.icp_estimation, icp_normal_k=a.icp_normal_k, icp_kernel=a.icp_kernel,
-                 icp_kernel_scale=a.icp_kernel_scale)
+                 icp_kernel_scale=a.icp_kernel_scale, icp_normal_radius=a.icp_normal_radius)
     results = evaluate(pipe, clouds, cfg)
     postfix = f"shapenet-seed{a.random_seed}-{a.category}-{len(files)}-{a.n_poses_per_model}"
     os.makedirs(a.out_dir, exist_ok=True)

@@ -638,11 +638,59 @@ int cs_icp_plane_robust_batch(const float* d_src, const int64_t* h_soff, const f
  *   n_seg = 0 and empty segments are legal.  Refused (CS_ERR_INVALID): a NULL offset table, a negative count, offsets that
  *     decrease, NULL d_xyz or d_normal while a row exists; (CS_ERR_UNSUPPORTED): k outside [3, 32], a segment of 2^31 rows
  *     or more.  (cs_knn_feat cannot serve this: its KNN_MAXK is 8, and it ranks features, not coordinates.)
- *   Path: the exhaustive f64 scan of the row's own segment, staged through LDS, one thread per row with its neighbour list
- *     in registers.  One launch on `stream`, no host wait, no atomics.
+ *   Paths, the same bits.  The exhaustive f64 scan of the row's own segment, staged through LDS, one thread
+ *     per row with its neighbour list in registers, is the DEFINITION of the neighbour list and the whole path under
+ *     CS_NORMALS_GRID=0 (read per call).  Otherwise a segment of more than 1024 rows is ranked on a cell grid
+ *     (corsair_amd/csrc/cellgrid.h): the cell size c = 1.5 sqrt(k A / (pi n)) comes on the device from the segment's bounding
+ *     box (A its surface area, n its rows; min / max are exact and order-free), every row probes the 27 cells around its
+ *     own, and its list is accepted only when its k-th d2 lies STRICTLY below c^2 (1 - 2^-30) -- every row the 27 cells do
+ *     not hold is then strictly farther, roundings of floor(x / c) and of the distance chain included (the argument is in
+ *     normals.hip), so no unseen row can enter or tie.  Rows that are not accepted are compacted into a list (an integer
+ *     counter; the order of the list reaches no output) and recomputed by the exhaustive scan, one wave per row.
+ *     Segments with a bounding box of zero area (copies of one point, a single row, rows of one line) or one that is not
+ *     finite, segments so far from the origin that a cell index would leave the 16-bit range, and segments of at most
+ *     1024 rows go straight to the exhaustive kernel.  Everything is enqueued on `stream`; no host wait (CS_NORMALS_STATS=1
+ *     adds one at the end); the atomics are integer (the table's compare-and-swap, the list's counter).
  * Profile family "normals".
  * ---------------------------------------------------------------------------------------- */
 int cs_estimate_normals(const float* d_xyz, const int64_t* h_off, int n_seg, int k, float* d_normal, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * cs_estimate_normals_hybrid: cs_estimate_normals with the neighbours of [O3D-knowledge] Open3D's
+ * KDTreeSearchParamHybrid(radius, max_nn): the at most max_nn nearest rows inside the radius (DESIGN 15;
+ * tests/normals_hybrid_ref.py restates it bit for bit).  d_xyz, h_off, n_seg, d_normal and stream are cs_estimate_normals'.
+ *   Neighbours of row i: the rows j of the SAME segment with d2 < radius * radius (one f64 product; d2 is
+ *     cs_estimate_normals' chain fma(dz, dz, fma(dy, dy, dx * dx)) on the coordinates widened to f64).  STRICT, the
+ *     project's convention for every threshold ([O3D-knowledge]: Open3D's radius search keeps a point AT the radius; no
+ *     measured input can tell the two apart, an integer lattice can).  Of those, the min(max_nn, found) smallest by
+ *     (d2, j), ties to the smaller row, the row itself included.  A NaN or inf d2 is never a neighbour (also when
+ *     radius * radius overflows to +inf: then every finite d2 passes and the call is cs_estimate_normals(k = max_nn)).
+ *     max_nn in [3, 32]; radius finite and > 0.  A radius whose square underflows to 0 finds nothing.
+ *   Everything after the neighbour list is cs_estimate_normals' -- the same code (nrm_finish, normals.hip): fewer than three
+ *     neighbours give (0, 0, 1); the scatter about the query row in (d2, j) order, jacobi3, the selection, sign and
+ *     degenerate rules, the one cast.  Independence as stated there.
+ *   n_seg = 0 and empty segments are legal, and so is every n_seg and segment size cs_estimate_normals accepts.  Refused:
+ *     what cs_estimate_normals refuses (max_nn in the place of k), and (CS_ERR_INVALID) a radius that is NaN, infinite or
+ *     <= 0.
+ *   Paths, the same bits:
+ *     the exhaustive scan, cs_estimate_normals' kernel with the radius test added: the definition, the whole path under
+ *       CS_NORMALS_GRID=0 (read per call), and the path of every segment of at most 512 rows (one LDS stage of the scan)
+ *       and of a radius of 1e300 or more;
+ *     the cell grid (corsair_amd/csrc/cellgrid.h, shared with cs_radius_pairs): cells of radius (1 + 2^-10), rows sorted
+ *       by (segment, cell), an open-addressing table of the cells' ranges, every row probes the 27 cells around its own --
+ *       complete for d2 < radius^2 by the argument in cellgrid.h, roundings of floor(x / cell) and of the distance chain
+ *       included -- and keeps its list in registers, inserting by the full (d2, j) pair since candidates come in no
+ *       particular order.  Cells clamp to the 16-bit key range: exact for any coordinates, only slower for far-out rows.
+ *       The 16-bit segment field of the key means the grid is built per chunk of 65 535 segments.
+ *   Everything is enqueued on `stream`; no host wait; the only atomics are the table's integer compare-and-swap, whose
+ *     order reaches no output.
+ *   cs_normals_stats: out = {rows answered by a grid path, of those recomputed by the exhaustive scan}, counted only while
+ *     CS_NORMALS_STATS=1.  The hybrid grid is complete and recomputes nothing.
+ * Profile family "normals", one scope per call.
+ * ---------------------------------------------------------------------------------------- */
+int cs_estimate_normals_hybrid(const float* d_xyz, const int64_t* h_off, int n_seg, double radius, int max_nn,
+                               float* d_normal, void* stream);
+void cs_normals_stats(uint64_t out[2], int reset);
 
 /* ------------------------------------------------------------------------------------------
  * Profiling hooks for bench.py: when enabled the library brackets the launches of each named

@@ -19,6 +19,9 @@ above, (p) the point-to-plane call (cs_icp_plane_batch) with the target normals 
 the 32 targets over --normal-k neighbours; with the updates per problem, the time per round, the fallback share and the
 pose errors of both.  `--start large` is the 12 degree / 5 cm start with max_dist 0.12 (default: 3 degrees / 1 cm, 0.06).
 
+`--normal-radius R` (with --estimation plane) times beside (n): (h) the hybrid search of at most --normal-k
+rows inside R, and (n0) the exhaustive scan alone (CS_NORMALS_GRID=0); it records the share of the grid's rows that the
+voucher sent back to the scan.
 `--kernel huber|cauchy|tukey [--kernel-scale K]` (K defaults to one voxel, untuned) measures, alternating in one
 process on the same problems: (l2) the point-to-plane call above and (k) cs_icp_plane_robust_batch with that kernel; per
 call ms, updates, ms per round (DESIGN 13's definition, ms / (most updates + 1), and -- the cleaner figure -- a run of
@@ -164,10 +167,27 @@ def plane_report(a, res, x0, off0, x1, off1, T0, truth, max_dist):
     fns = {"point": lambda: B.icp_batch(x0, off0, x1, off1, pairs, pairs, T0, max_dist, MAX_ITER),
            "plane": lambda: B.icp_batch(x0, off0, x1, off1, pairs, pairs, T0, max_dist, MAX_ITER, tgt_normals=nrm),
            "normals": lambda: B.estimate_normals(x1, off1, a.normal_k)}
+    if a.normal_radius > 0:     # (h) the hybrid search beside (n): at most normal_k rows inside the radius
+        fns["normals_hybrid"] = lambda: B.estimate_normals(x1, off1, a.normal_k, radius=a.normal_radius)
+    os.environ["CS_NORMALS_GRID"] = "0"     # (n0) the exhaustive scan alone, the definition
+    ms0 = timed_alternating({"normals": fns["normals"]}, a.reps)
+    del os.environ["CS_NORMALS_GRID"]
     ms = timed_alternating(fns, a.reps)
     res.update({"estimation": "plane", "normal_k": a.normal_k, "icp_point_ms": ms["point"], "icp_plane_ms": ms["plane"],
-                "normals_ms": ms["normals"], "plane_over_point": round(ms["plane"] / ms["point"], 4),
+                "normals_ms": ms["normals"], "normals_exhaustive_ms": ms0["normals"],
+                "plane_over_point": round(ms["plane"] / ms["point"], 4),
                 "bar_plane_le_point": bool(ms["plane"] <= ms["point"])})
+    os.environ["CS_NORMALS_STATS"] = "1"
+    B.normals_stats(reset=True)
+    fns["normals"]()
+    st = B.normals_stats(reset=True)
+    res["normals_grid_rows"], res["normals_fallback_share"] = st[0], round(st[1] / max(st[0], 1), 6)
+    if a.normal_radius > 0:
+        found = fns["normals_hybrid"]()
+        res.update({"normal_radius": a.normal_radius, "normals_hybrid_ms": ms["normals_hybrid"],
+                    "normals_hybrid_grid_rows": B.normals_stats(reset=True)[0],
+                    "normals_hybrid_differs_from_knn_rows": int((found != nrm).any(1).sum())})
+    del os.environ["CS_NORMALS_STATS"]
 
     def errs(T):
         T = T.cpu().numpy().astype(np.float64)
@@ -268,6 +288,8 @@ def main():
     ap.add_argument("--estimation", default="point", choices=["point", "plane"],
                     help="plane: point against point-to-plane against the normals, alternating (DESIGN 13)")
     ap.add_argument("--normal-k", type=int, default=16)
+    ap.add_argument("--normal-radius", type=float, default=0.0,
+                    help="with --estimation plane: also time the hybrid search (at most --normal-k rows inside this radius)")
     ap.add_argument("--start", default="small", choices=["small", "large"],
                     help="large: 12 degrees / 5 cm with max_dist 0.12 (overrides --deg / --trans)")
     ap.add_argument("--kernel", default="l2", choices=["l2", "huber", "cauchy", "tukey"],
