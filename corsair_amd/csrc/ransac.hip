@@ -51,6 +51,7 @@
 #include <vector>
 
 #include "common.h"
+#include "exact_div.h"
 #include "horn.h"
 
 namespace cs {
@@ -110,8 +111,9 @@ __global__ void k_ransac_pack(const float* __restrict__ src, const float* __rest
 }
 
 // hyp layout: [prob][12][bmax] (structure of arrays), element 4a+b = R[a][b], 4a+3 = t[a]
-// RN = ransac_n when it is known at compile time (10: the reference's value; the sampled pairs then stay
-// in registers between the centroid and the covariance pass), 0 = read it from the argument
+// RN = ransac_n when it is known at compile time (10: the reference's value; the loops are unrolled and the sampled
+// pairs stay in registers between the centroid and the covariance pass), 0 = read it from the argument and read the
+// pairs again; inv_n = exact_div_recip(ransac_n)
 // Placement table of a round (problem of XCD x, slot i) as a kernel ARGUMENT: the host builds it per round, a
 // device copy of it was one hipMemcpyAsync (a blit-kernel launch) per round.  Rounds with more than XCD_SLOTS
 // problems per XCD fall back to the device table (xcd_ptr != nullptr).
@@ -128,10 +130,37 @@ __device__ __forceinline__ void pf_emit_row(const RansacProb& pr, int p, int h, 
                                             const unsigned* __restrict__ stat, const double* __restrict__ sums, double thr2,
                                             double tcap, _Float16* __restrict__ A16, float* __restrict__ c_h);
 
+// centroids = sums / ransac_n, six quotients with one divisor: exact_div.h's multiply-and-correct sequence, which returns the
+// IEEE quotient (proof and conditions there), when the host found the divisor admissible (inv_n != 0) and all six sums are in
+// the proven range; otherwise (a sum that is 0, subnormal or not finite) the six divisions as before
+__device__ __forceinline__ void centroid_div(double (&cs_)[3], double (&ct_)[3], double dn, double inv_n) {
+  bool fast = inv_n != 0.0;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) fast = fast && exact_div_ok(cs_[a]) && exact_div_ok(ct_[a]);
+  if (fast) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      cs_[a] = exact_div(cs_[a], dn, inv_n);
+      ct_[a] = exact_div(ct_[a], dn, inv_n);
+    }
+  } else {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      cs_[a] = cs_[a] / dn;
+      ct_[a] = ct_[a] / dn;
+    }
+  }
+}
+
+// Five waves per SIMD: the attribute holds the register allocator to that budget for BOTH instantiations -- <10> takes 96
+// registers and <0> 94, neither uses scratch (without it <10> takes 107 and runs at four waves).  The budget is not free: a
+// change here or in horn.h that needs more registers would spill instead of failing, so check the compiler's resource report
+// (-Rpass-analysis=kernel-resource-usage: VGPRs <= 96, ScratchSize 0) after touching either.
 template <int RN>
+__attribute__((amdgpu_waves_per_eu(5, 5)))
 __global__ __launch_bounds__(256) void k_ransac_hyp(const RansacProb* probs,
                                                     const float4* __restrict__ pair32, int it0,
-                                                    int bcount, int bmax, int ransac_n,
+                                                    int bcount, int bmax, int ransac_n, double inv_n,
                                                     uint64_t seed,
                                                     const int32_t* __restrict__ xcd_prob, const XcdTab xcd_tab,
                                                     int slots, int tiles, int force_jacobi,
@@ -158,35 +187,33 @@ __global__ __launch_bounds__(256) void k_ransac_hyp(const RansacProb* probs,
   double cs_[3] = {0, 0, 0}, ct_[3] = {0, 0, 0};
   double S[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
   if (RN > 0) {
-    float4 pa[RN > 0 ? RN : 1];
-    float2 pb[RN > 0 ? RN : 1];
+    // the ten samples stay in registers between the two passes AS THE f32 VALUES THEY WERE LOADED AS (60 registers)
+    float pa[RN > 0 ? RN : 1][6];
 #pragma unroll
     for (int j = 0; j < RN; ++j) {
       const int64_t i = pr.off + rng_index(seed, (uint64_t)itr, (uint64_t)j, m);
       const float4 a = pair32[2 * i], b = pair32[2 * i + 1];  // one 32-B sector
-      pa[j] = a;
-      pb[j] = make_float2(b.x, b.y);
-      cs_[0] += (double)a.x;
-      cs_[1] += (double)a.y;
-      cs_[2] += (double)a.z;
-      ct_[0] += (double)a.w;
-      ct_[1] += (double)b.x;
-      ct_[2] += (double)b.y;
-    }
-    const double dn = (double)RN;
+      pa[j][0] = a.x; pa[j][1] = a.y; pa[j][2] = a.z; pa[j][3] = a.w; pa[j][4] = b.x; pa[j][5] = b.y;
 #pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      cs_[a] = cs_[a] / dn;
-      ct_[a] = ct_[a] / dn;
+      for (int c = 0; c < 3; ++c) {
+        cs_[c] += (double)pa[j][c];
+        ct_[c] += (double)pa[j][3 + c];
+      }
     }
+    centroid_div(cs_, ct_, (double)RN, inv_n);
 #pragma unroll
     for (int j = 0; j < RN; ++j) {
-      const double ds[3] = {(double)pa[j].x - cs_[0], (double)pa[j].y - cs_[1], (double)pa[j].z - cs_[2]};
-      const double dt[3] = {(double)pa[j].w - ct_[0], (double)pb[j].x - ct_[1], (double)pb[j].y - ct_[2]};
+      // opaque copies, so that the values are converted to f64 AGAIN here: the compiler otherwise keeps the sixty f64
+      // conversions of the first pass alive (120 registers; the kernel then held 164 and ran at three waves per SIMD).
+      // Reading the sectors a second time instead was measured slower than the parent (113 vs 105 us per launch).
 #pragma unroll
-      for (int a = 0; a < 3; ++a)
+      for (int c = 0; c < 6; ++c) asm volatile("" : "+v"(pa[j][c]));
+      const double ds[3] = {(double)pa[j][0] - cs_[0], (double)pa[j][1] - cs_[1], (double)pa[j][2] - cs_[2]};
+      const double dt[3] = {(double)pa[j][3] - ct_[0], (double)pa[j][4] - ct_[1], (double)pa[j][5] - ct_[2]};
 #pragma unroll
-        for (int b = 0; b < 3; ++b) S[a][b] = fma(ds[a], dt[b], S[a][b]);
+      for (int x = 0; x < 3; ++x)
+#pragma unroll
+        for (int y = 0; y < 3; ++y) S[x][y] = fma(ds[x], dt[y], S[x][y]);
     }
   } else {
     for (int j = 0; j < ransac_n; ++j) {
@@ -199,12 +226,7 @@ __global__ __launch_bounds__(256) void k_ransac_hyp(const RansacProb* probs,
       ct_[1] += (double)b.x;
       ct_[2] += (double)b.y;
     }
-    const double dn = (double)ransac_n;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-      cs_[a] = cs_[a] / dn;
-      ct_[a] = ct_[a] / dn;
-    }
+    centroid_div(cs_, ct_, (double)ransac_n, inv_n);
     for (int j = 0; j < ransac_n; ++j) {
       const int64_t i = pr.off + rng_index(seed, (uint64_t)itr, (uint64_t)j, m);
       const float4 a = pair32[2 * i], b = pair32[2 * i + 1];
@@ -472,18 +494,38 @@ __host__ __device__ static inline int64_t pf_padded(int64_t m) { return (m + PF_
 // spread of the problem's points.  The part-to-part problems of split_corr (utils/symmetry.py:145-179: a leg against a leg)
 // sit far from the origin; without the centring 30 % of their hypotheses exceeded the |t| cap of the K = 16 form.
 __global__ __launch_bounds__(256) void k_ransac_pair_sums(const RansacProb* __restrict__ probs, const float* __restrict__ src,
-                                                          const float* __restrict__ tgt, double* __restrict__ sums) {
+                                                          const float* __restrict__ tgt, double* __restrict__ sums,
+                                                          unsigned* __restrict__ stat, unsigned long long* __restrict__ chk_stats) {
   // ONE workgroup per problem and a fixed reduction order: the means -- and with them the prefilter's survivor sets -- are
   // the same in every run (an atomic accumulation made the survivor counts of otherwise identical runs differ by 1e-4)
   __shared__ double red[4][6];
   const RansacProb pr = probs[blockIdx.x];
+  // the maxima that k_ransac_images accumulates with atomics, and the CS_RANSAC_CHECK totals, start at zero (this kernel
+  // precedes both on the stream: no fill launches)
+  if (threadIdx.x < PF_STAT) stat[blockIdx.x * PF_STAT + threadIdx.x] = 0u;
+  if (blockIdx.x == 0 && threadIdx.x < 4) chk_stats[threadIdx.x] = 0ull;
   double a[6] = {0, 0, 0, 0, 0, 0};
-  for (int j = threadIdx.x; j < pr.m; j += 256) {
-    const int64_t i = pr.off + j;
+  // a lane adds its rows j = lane, lane + 256, ... in that order; the loads of SUMS_U rows are issued together (the loop is
+  // bound by the latency of its strided loads: one workgroup walks a whole problem)
+  constexpr int SUMS_U = 8;
+  for (int j0 = threadIdx.x; j0 < pr.m; j0 += 256 * SUMS_U) {
+    float v[SUMS_U][6];
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      a[c] += (double)src[3 * i + c];
-      a[3 + c] += (double)tgt[3 * i + c];
+    for (int u = 0; u < SUMS_U; ++u) {
+      const int j = j0 + 256 * u;
+      const int64_t i = pr.off + (j < pr.m ? j : j0);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        v[u][c] = src[3 * i + c];
+        v[u][3 + c] = tgt[3 * i + c];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < SUMS_U; ++u) {
+      if (j0 + 256 * u < pr.m) {
+#pragma unroll
+        for (int c = 0; c < 6; ++c) a[c] += (double)v[u][c];
+      }
     }
   }
 #pragma unroll
@@ -506,17 +548,35 @@ __device__ __forceinline__ void pf_centre(const double* __restrict__ sums, int p
   for (int c = 0; c < 6; ++c) mu[c] = sums[p * 6 + c];
 }
 
-// NM = 2: rows [bh | bl | pad] of the K = 32 form.  NM = 1 (round 4): rows [bh | pad] of the K = 16 form -- the matrix pipe
-// then evaluates a_hi . b_hi only, and what it drops, a_hi . b_lo, is bounded PER PAIR and taken out of the pair's constant
-// term b_0 (a_0 = 1 exactly) by k_ransac_pack16_b0 below, so the sign test stays an upper bound (see there).
-template <int NM>
-__global__ __launch_bounds__(256) void k_ransac_pack16(const RansacProb* __restrict__ probs,
+// The centred bilinear row of one pair, b = (|s|^2 + |q|^2, s, q (x) s, q), and the pair's magnitude test -- ONE definition for
+// k_ransac_images and k_ransac_pack16_b0, whose rows must agree.  Returns max(|s|, |q|) rounded up to f32 (1.0000002: the f32
+// norm may round down); NaN when a coordinate is not finite.  A pair is in f16 range iff the value is <= PF_SMAX.
+__device__ __forceinline__ float pf_pair_row(float s0, float s1, float s2, float q0, float q1, float q2, const double (&mu)[6],
+                                             double (&b)[16]) {
+  const double sx = s0 - mu[0], sy = s1 - mu[1], sz = s2 - mu[2];
+  const double qx = q0 - mu[3], qy = q1 - mu[4], qz = q2 - mu[5];
+  const double ss = sx * sx + sy * sy + sz * sz, qq = qx * qx + qy * qy + qz * qz;
+  b[0] = ss + qq;
+  b[1] = sx; b[2] = sy; b[3] = sz;
+  b[4] = qx * sx; b[5] = qx * sy; b[6] = qx * sz;
+  b[7] = qy * sx; b[8] = qy * sy; b[9] = qy * sz;
+  b[10] = qz * sx; b[11] = qz * sy; b[12] = qz * sz;
+  b[13] = qx; b[14] = qy; b[15] = qz;
+  return 1.0000002f * (float)sqrt(fmax(ss, qq));
+}
+
+// First pass over the pairs of a call: the packed copies (k_ransac_pack's pk and pair32), the per-problem statistics and the
+// rows [bh | bl | pad] of the K = 32 form (B32, PF_PITCH halfs: the prefilter's image with CS_RANSAC_PF_K=32, the second
+// stage's otherwise; null with CS_RANSAC_STAGE2=0) from one read of src / tgt and one evaluation of the centred bilinear
+// row b and its hi / lo split.  The rows of the K = 16 form need the problem's smax: k_ransac_pack16_b0 below.
+static_assert(PF_PITCH == 40 && PF_PITCH1 == 24, "k_ransac_images / k_ransac_pack16_b0 write 5 / 3 pieces of 16 B per row");
+__global__ __launch_bounds__(256) void k_ransac_images(const RansacProb* __restrict__ probs,
                                                        const int64_t* __restrict__ off16,
                                                        const float* __restrict__ src,
                                                        const float* __restrict__ tgt,
-                                                       const double* __restrict__ sums,
-                                                       _Float16* __restrict__ B16,
-                                                       unsigned* __restrict__ stat) {
+                                                       const double* __restrict__ sums, int64_t n,
+                                                       float* __restrict__ pk, float4* __restrict__ pair32,
+                                                       _Float16* __restrict__ B32, unsigned* __restrict__ stat) {
   __shared__ float red[4][PF_STAT];
   const RansacProb pr = probs[blockIdx.y];
   double mu[6];
@@ -526,7 +586,6 @@ __global__ __launch_bounds__(256) void k_ransac_pack16(const RansacProb* __restr
 #pragma unroll
   for (int k = 0; k < PF_STAT; ++k) mx[k] = 0.f;
   for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < mpad; j += gridDim.x * blockDim.x) {
-    constexpr int NV = pf_pitch(NM) / 8;   // 16-B pieces per row
     union {
       _Float16 h[PF_PITCH];
       uint4 v[5];
@@ -535,18 +594,17 @@ __global__ __launch_bounds__(256) void k_ransac_pack16(const RansacProb* __restr
     for (int k = 0; k < 5; ++k) row.v[k] = make_uint4(0u, 0u, 0u, 0u);
     if (j < pr.m) {
       const int64_t i = pr.off + j;
-      const double sx = src[3 * i] - mu[0], sy = src[3 * i + 1] - mu[1], sz = src[3 * i + 2] - mu[2];
-      const double qx = tgt[3 * i] - mu[3], qy = tgt[3 * i + 1] - mu[4], qz = tgt[3 * i + 2] - mu[5];
-      const double ss = sx * sx + sy * sy + sz * sz, qq = qx * qx + qy * qy + qz * qz;
+      const float fs[3] = {src[3 * i], src[3 * i + 1], src[3 * i + 2]};
+      const float fq[3] = {tgt[3 * i], tgt[3 * i + 1], tgt[3 * i + 2]};
+      pair32[2 * i + 0] = make_float4(fs[0], fs[1], fs[2], fq[0]);
+      pair32[2 * i + 1] = make_float4(fq[1], fq[2], 0.f, 0.f);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        pk[c * n + i] = fs[c];
+        pk[(3 + c) * n + i] = fq[c];
+      }
       double b[16];
-      b[0] = ss + qq;
-      b[1] = sx; b[2] = sy; b[3] = sz;
-      b[4] = qx * sx; b[5] = qx * sy; b[6] = qx * sz;
-      b[7] = qy * sx; b[8] = qy * sy; b[9] = qy * sz;
-      b[10] = qz * sx; b[11] = qz * sy; b[12] = qz * sz;
-      b[13] = qx; b[14] = qy; b[15] = qz;
-      // 1.0000002: the f32 norm may round down
-      float mag = 1.0000002f * (float)sqrt(fmax(ss, qq));
+      float mag = pf_pair_row(fs[0], fs[1], fs[2], fq[0], fq[1], fq[2], mu, b);
       // out of f16 range (or NaN): a finite (zero) row; smax then marks the problem's hypotheses unusable
       const bool ok = mag <= PF_SMAX;
       if (!(mag == mag)) mag = INFINITY;
@@ -558,15 +616,18 @@ __global__ __launch_bounds__(256) void k_ransac_pack16(const RansacProb* __restr
           mx[1 + k] = fmaxf(mx[1 + k], __double2float_ru(fabs(b[k])));
         }
         row.h[k] = hi;
-        if (NM == 2) row.h[16 + k] = lo;
+        row.h[16 + k] = lo;
       }
       mx[0] = fmaxf(mx[0], mag);
     } else {
       row.h[0] = (_Float16)60000.0f;  // pairs with a_0 = 1
     }
-    uint4* dst = reinterpret_cast<uint4*>(B16 + (off16[blockIdx.y] + j) * pf_pitch(NM));
+    const int64_t r = off16[blockIdx.y] + j;
+    if (B32) {
+      uint4* dst = reinterpret_cast<uint4*>(B32 + r * PF_PITCH);
 #pragma unroll
-    for (int k = 0; k < NV; ++k) dst[k] = row.v[k];
+      for (int k = 0; k < PF_PITCH / 8; ++k) dst[k] = row.v[k];
+    }
   }
 #pragma unroll
   for (int k = 0; k < PF_STAT; ++k) {
@@ -582,8 +643,11 @@ __global__ __launch_bounds__(256) void k_ransac_pack16(const RansacProb* __restr
   }
 }
 
-// K = 16 form, second pass over the pairs (needs the problem's smax, which the first pass produces): the constant term of
-// every pair becomes   b_0' = round_down_f16( b_0 - E_p ),   E_p = (1 + 2^-10) sum_{k=1..15} A_k |b_k - hi(b_k)|,
+// K = 16 form (round 4), second pass over the pairs (needs the problem's smax, which the first pass produces): rows
+// [bh | pad] (PF_PITCH1 halfs) -- the matrix pipe then evaluates a_hi . b_hi only, and what it drops, a_hi . b_lo, is bounded
+// PER PAIR and taken out of the pair's constant term b_0 (a_0 = 1 exactly), so the sign test stays an upper bound.  The
+// kernel writes WHOLE rows (a 2-byte update of rows another kernel wrote was a read-modify-write in memory).  The constant
+// term of every pair is   b_0' = round_down_f16( b_0 - E_p ),   E_p = (1 + 2^-10) sum_{k=1..15} A_k |b_k - hi(b_k)|,
 // with A_k an upper bound of |a_hi_k| over all USABLE hypotheses of the problem:
 //   k = 4..12  (a = -2 R):          |a| <= 2 sqrt(1 + max|E|) <= 2.002   (pf_emit_row requires max|E| < 1e-3)
 //   k = 1..3, 13..15 (2 R^T t, -2 t): |a| <= 2 |t| sqrt(1 + max|E|) with |t| <= tcap * smax: pf_emit_row CHECKS that and
@@ -598,7 +662,7 @@ __global__ __launch_bounds__(256) void k_ransac_pack16(const RansacProb* __restr
 // bound: E_p is ~1e-3 for unit-sized objects (2.5 % of thr^2 = 0.04), the rounding of b_0 another ~2.4e-4 on average.
 __global__ __launch_bounds__(256) void k_ransac_pack16_b0(const RansacProb* __restrict__ probs,
                                                           const int64_t* __restrict__ off16,
-                                                          const float* __restrict__ src, const float* __restrict__ tgt,
+                                                          const float4* __restrict__ pair32,
                                                           const double* __restrict__ sums,
                                                           const unsigned* __restrict__ stat, double tcap,
                                                           _Float16* __restrict__ B16) {
@@ -606,33 +670,56 @@ __global__ __launch_bounds__(256) void k_ransac_pack16_b0(const RansacProb* __re
   double mu[6];
   pf_centre(sums, blockIdx.y, pr.m, mu);
   const double smax = (double)__uint_as_float(stat[blockIdx.y * PF_STAT]);
-  if (!(smax <= (double)PF_SMAX)) return;   // the problem bypasses the prefilter (every hypothesis unusable)
+  // smax out of range (a point norm above PF_SMAX, or not finite): the problem bypasses the prefilter, every hypothesis is
+  // unusable; its rows keep the plain b_0 and are zero where the pair itself is out of range.  Otherwise every pair is in range.
+  const bool bypass = !(smax <= (double)PF_SMAX);
   const double beta = smax * smax;
   const double a_rot = 2.002 * (1.0 + 0x1p-11), a_t = 2.0 * tcap * smax * 1.0005 * (1.0 + 0x1p-11);
-  for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < pr.m; j += gridDim.x * blockDim.x) {
-    const int64_t i = pr.off + j;
-    const double sx = src[3 * i] - mu[0], sy = src[3 * i + 1] - mu[1], sz = src[3 * i + 2] - mu[2];
-    const double qx = tgt[3 * i] - mu[3], qy = tgt[3 * i + 1] - mu[4], qz = tgt[3 * i + 2] - mu[5];
-    const double ss = sx * sx + sy * sy + sz * sz, qq = qx * qx + qy * qy + qz * qz;
-    const double b[16] = {ss + qq, sx, sy, sz, qx * sx, qx * sy, qx * sz, qy * sx, qy * sy, qy * sz,
-                          qz * sx, qz * sy, qz * sz, qx, qy, qz};
-    double e_t = 0.0, e_rot = 0.0;
+  const int mpad = (int)pf_padded(pr.m);
+  for (int j = blockIdx.x * blockDim.x + threadIdx.x; j < mpad; j += gridDim.x * blockDim.x) {
+    union {
+      _Float16 h[PF_PITCH1];
+      uint4 v[3];
+    } row;
 #pragma unroll
-    for (int k = 1; k < 16; ++k) {
-      const double lo = fabs(b[k] - (double)f16_of(b[k]));
-      if (k >= 4 && k <= 12) e_rot += lo; else e_t += lo;
+    for (int k = 0; k < 3; ++k) row.v[k] = make_uint4(0u, 0u, 0u, 0u);
+    if (j < pr.m) {
+      const int64_t i = pr.off + j;
+      const float4 pa = pair32[2 * i], pb = pair32[2 * i + 1];   // the pair as k_ransac_images packed it: (sx, sy, sz, qx | qy, qz)
+      double b[16];
+      const float mag = pf_pair_row(pa.x, pa.y, pa.z, pa.w, pb.x, pb.y, mu, b);
+      if (bypass) {
+        if (mag <= PF_SMAX) {   // (false for NaN)
+#pragma unroll
+          for (int k = 0; k < 16; ++k) row.h[k] = f16_of(b[k]);
+        }
+      } else {
+        double e_t = 0.0, e_rot = 0.0;
+#pragma unroll
+        for (int k = 1; k < 16; ++k) {
+          const _Float16 hi = f16_of(b[k]);
+          row.h[k] = hi;
+          const double lo = fabs(b[k] - (double)hi);
+          if (k >= 4 && k <= 12) e_rot += lo; else e_t += lo;
+        }
+        const double ep = (1.0 + 0x1p-10) * (a_rot * e_rot + a_t * e_t);
+        // round toward -inf into f16: RNE first, one ulp down when that landed above
+        const double v = (b[0] - beta) - ep - 0x1p-40 * (fabs(b[0]) + beta + ep);   // (the f64 roundings of the terms themselves)
+        _Float16 h = f16_of(v);
+        if ((double)h > v) {
+          unsigned short u = __builtin_bit_cast(unsigned short, h);
+          // next representable value below: magnitude down for positive values, up for negative ones (+0 -> -min subnormal)
+          u = (u & 0x8000u) ? (unsigned short)(u + 1) : (u == 0 ? (unsigned short)0x8001u : (unsigned short)(u - 1));
+          h = __builtin_bit_cast(_Float16, u);
+        }
+        row.h[0] = h;
+      }
+    } else {
+      row.h[0] = (_Float16)60000.0f;  // pairs with a_0 = 1
     }
-    const double ep = (1.0 + 0x1p-10) * (a_rot * e_rot + a_t * e_t);
-    // round toward -inf into f16: RNE first, one ulp down when that landed above
-    const double v = (b[0] - beta) - ep - 0x1p-40 * (fabs(b[0]) + beta + ep);   // (the f64 roundings of the terms themselves)
-    _Float16 h = f16_of(v);
-    if ((double)h > v) {
-      unsigned short u = __builtin_bit_cast(unsigned short, h);
-      // next representable value below: magnitude down for positive values, up for negative ones (+0 -> -min subnormal)
-      u = (u & 0x8000u) ? (unsigned short)(u + 1) : (u == 0 ? (unsigned short)0x8001u : (unsigned short)(u - 1));
-      h = __builtin_bit_cast(_Float16, u);
-    }
-    B16[(off16[blockIdx.y] + j) * PF_PITCH1] = h;
+    uint4* dst = reinterpret_cast<uint4*>(B16 + (off16[blockIdx.y] + j) * PF_PITCH1);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) dst[k] = row.v[k];
   }
 }
 
@@ -741,7 +828,7 @@ __device__ __forceinline__ void pf_emit_row(const RansacProb& pr, int p, int h, 
 // any |acc| < 2^40 (tools/ubench/rtn_count.hip: edge cases incl. -0 and denormals) -- one FULL-RATE VALU op per result
 // instead of a 4.5-cycle v_alignbit.  Full-rate ops do not overlap with the matrix pipe, but the K = 16 unit has only one
 // MFMA: 32 + 16 x 2.3 = 69 cycles against 72+ (tools/ubench/pf_k16_mix.hip: 29.2 vs 32.8 ns per unit per SIMD).
-template <int NM, bool RTN>   // NM = MFMAs per unit: 2 = K 32 (a_hi . (b_hi + b_lo)), 1 = K 16 (a_hi . b_hi', k_ransac_pack16<1> + _b0)
+template <int NM, bool RTN>   // NM = MFMAs per unit: 2 = K 32 (a_hi . (b_hi + b_lo)), 1 = K 16 (a_hi . b_hi', k_ransac_images + k_ransac_pack16_b0)
 __global__ __launch_bounds__(256) void k_ransac_prefilter(const RansacProb* probs,
                                                           const int64_t* __restrict__ off16,
                                                           const _Float16* __restrict__ B16,
@@ -1533,7 +1620,6 @@ struct Scratch {
   PoolBuf<_Float16> B32, A16s;
   PoolBuf<float> c_hs;
   PoolBuf<int32_t> cnt2;
-  PoolBuf<unsigned> pf_stat2;              // (the K = 32 pack writes the same statistics again: scratch)
   PoolBuf<int32_t> exact_dbg;              // CS_RANSAC_CHECK
   PoolBuf<unsigned long long> chk_stats;
   PoolBuf<int32_t> xcd_buf;                // placement tables, one per round parity (8 x n_prob entries each)
@@ -1555,7 +1641,7 @@ struct Scratch {
            c_h.alloc(pf ? 2 * nb : 1) && cnt_up.alloc(pf ? 2 * nb : 1) && hlist.alloc(pf ? nb : 1) &&
            pf_stat.alloc((size_t)n * PF_STAT) && pf_sums.alloc((size_t)n * 6) &&
            B32.alloc(stage2 ? (size_t)rows16 * PF_PITCH : 8) && A16s.alloc(stage2 ? ns2 * PF_K : 8) &&
-           c_hs.alloc(stage2 ? ns2 : 1) && cnt2.alloc(stage2 ? ns2 : 1) && pf_stat2.alloc((size_t)n * PF_STAT) &&
+           c_hs.alloc(stage2 ? ns2 : 1) && cnt2.alloc(stage2 ? ns2 : 1) &&
            exact_dbg.alloc(check ? nb : 1) && chk_stats.alloc(4) && xcd_buf.alloc((size_t)16 * n) && trace.alloc(trace_cap);
   }
   RansacProb* probs() const { return reinterpret_cast<RansacProb*>(state.p); }
@@ -1699,30 +1785,26 @@ int RansacCall::setup(const float* d_src, const float* d_tgt) {
   memcpy(sc.h_state, hp.data(), sc.st_probs);
   CS_HIP_CHECK(hipMemcpyAsync(sc.state.p, sc.h_state, sc.st_bytes, hipMemcpyHostToDevice, s));
   RansacProb* const d_probs = sc.probs();
-  if (total > 0) {
-    hipLaunchKernelGGL(k_ransac_pack, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, s,
-                       d_src, d_tgt, total, sc.pk.p, sc.pair32.p);
-    CS_LAUNCH_CHECK();
-  }
   if (pf_alloc) {
-    CS_HIP_CHECK(hipMemsetAsync(sc.pf_stat.p, 0, sizeof(unsigned) * n_prob * PF_STAT, s));
-    CS_HIP_CHECK(hipMemsetAsync(sc.chk_stats.p, 0, sizeof(unsigned long long) * 4, s));
+    // three launches: means (+ cleared statistics) -> packed pairs, K = 32 image and the per-problem maxima -> (K = 16) the
+    // one-MFMA image, whose constant term takes the per-pair bound of the dropped term and needs the problem's smax.  The
+    // first two read src / tgt once each, the third the packed pairs.
     int pblocks = (int)ceil_div(m_max > 0 ? m_max : 1, 256);
     if (pblocks > 64) pblocks = 64;
     const dim3 pgrid((unsigned)pblocks, (unsigned)n_prob);
     CS_HIP_CHECK(hipMemcpyAsync(sc.off16.p, h_off16.data(), sizeof(int64_t) * (n_prob + 1),
                                 hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_ransac_pair_sums, dim3((unsigned)n_prob), dim3(256), 0, s, d_probs, d_src, d_tgt, sc.pf_sums.p);
-    hipLaunchKernelGGL(opt.pf_nm == 2 ? k_ransac_pack16<2> : k_ransac_pack16<1>, pgrid, dim3(256), 0, s,
-                       d_probs, sc.off16.p, d_src, d_tgt, sc.pf_sums.p, sc.B16.p, sc.pf_stat.p);
-    if (opt.pf_nm == 1)   // K = 16: the per-pair bound of the dropped term goes into the constant term
+    hipLaunchKernelGGL(k_ransac_pair_sums, dim3((unsigned)n_prob), dim3(256), 0, s, d_probs, d_src, d_tgt, sc.pf_sums.p,
+                       sc.pf_stat.p, sc.chk_stats.p);
+    hipLaunchKernelGGL(k_ransac_images, pgrid, dim3(256), 0, s, d_probs, sc.off16.p, d_src, d_tgt, sc.pf_sums.p, total,
+                       sc.pk.p, sc.pair32.p, opt.pf_nm == 2 ? sc.B16.p : (stage2 ? sc.B32.p : nullptr), sc.pf_stat.p);
+    if (opt.pf_nm == 1)
       hipLaunchKernelGGL(k_ransac_pack16_b0, pgrid, dim3(256), 0, s,
-                         d_probs, sc.off16.p, d_src, d_tgt, sc.pf_sums.p, sc.pf_stat.p, tcap, sc.B16.p);
-    if (stage2) {
-      CS_HIP_CHECK(hipMemsetAsync(sc.pf_stat2.p, 0, sizeof(unsigned) * n_prob * PF_STAT, s));
-      hipLaunchKernelGGL(k_ransac_pack16<2>, pgrid, dim3(256), 0, s,
-                         d_probs, sc.off16.p, d_src, d_tgt, sc.pf_sums.p, sc.B32.p, sc.pf_stat2.p);
-    }
+                         d_probs, sc.off16.p, sc.pair32.p, sc.pf_sums.p, sc.pf_stat.p, tcap, sc.B16.p);
+    CS_LAUNCH_CHECK();
+  } else if (total > 0) {   // no prefilter in this call: the packed pairs alone
+    hipLaunchKernelGGL(k_ransac_pack, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, s,
+                       d_src, d_tgt, total, sc.pk.p, sc.pair32.p);
     CS_LAUNCH_CHECK();
   }
   if (opt.trace_it0 >= 0) CS_HIP_CHECK(hipMemsetAsync(sc.trace.p, 0, sizeof(unsigned long long) * sc.trace_cap, s));
@@ -1811,7 +1893,7 @@ Front RansacCall::enqueue_front(int it0, int par, hipStream_t st) {
     int32_t* fz = psplits > 1 ? cnt_up_r : nullptr;
     const auto kernel = ransac_n == 10 ? k_ransac_hyp<10> : k_ransac_hyp<0>;
     hipLaunchKernelGGL(kernel, dim3((unsigned)(8 * pslots * htiles)), dim3(256), 0, sh, d_probs,
-                       sc.pair32.p, it0, b, BMAX, ransac_n, seed, f.xcd_prob, f.xtab, pslots, htiles, opt.force_jacobi,
+                       sc.pair32.p, it0, b, BMAX, ransac_n, exact_div_recip((double)ransac_n), seed, f.xcd_prob, f.xtab, pslots, htiles, opt.force_jacobi,
                        sc.hyp_of(par), sc.pf_stat.p, sc.pf_sums.p, thr2, tcap, A16_r, c_h_r, fz);
   }
   if (f.pf) {
