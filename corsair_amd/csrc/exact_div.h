@@ -2,7 +2,7 @@
 // one fma-based correction (Markstein's division step: P. Markstein, "Computation of elementary functions on the IBM RISC
 // System/6000 processor", IBM J. Res. Dev. 34(1), 1990; with the divisor known in advance: Brisebarre, Muller, Raina,
 // "Accelerating correctly rounded floating-point division when the divisor is known in advance", IEEE TC 53(8), 2004).
-// Shared by k_ransac_hyp (ransac.hip) and the CPU sweep tools/div_sweep.cpp, which compares it with `/`.
+// Shared by k_ransac_hyp (ransac_hyp.hip) and the CPU sweep tools/div_sweep.cpp, which compares it with `/`.
 //
 // Claim: for an integer 1 <= n <= 64, r = RN(1 / n) and a double x with 2^-900 <= |x| < 2^901,
 //   q0 = RN(x r),  e = RN(x - q0 n) (one fma),  q = RN(q0 + e r) (one fma)      gives      q = RN(x / n).

@@ -261,7 +261,7 @@ static void oc_jacobi4(double a[4][4], double v[4][4]) {
 }
 
 /* Largest eigenpair of the Horn matrix without iterating on the matrix (round 4; the same operation
- * sequence as horn_qcp in corsair_amd/csrc/ransac.hip).  N is symmetric and traceless, so its characteristic
+ * sequence as horn_qcp in corsair_amd/csrc/horn.h).  N is symmetric and traceless, so its characteristic
  * polynomial is l^4 + c2 l^2 + c1 l + c0 with c2 = -2 |S|_F^2, c1 = -8 det S, c0 = det N (Theobald's QCP
  * observation).  All four roots are real, so Halley's iteration started at the upper bound sqrt(3) |S|_F
  * (>= sigma1 + sigma2 + sigma3 >= l_max) decreases monotonically onto the largest root with cubic order;

@@ -421,6 +421,60 @@ def test_ransac_second_stage_leaves_the_trajectory_unchanged(gpu, monkeypatch):
         assert np.array_equal(a, b)
 
 
+def _ball(rng, n, centre, radius):
+    v = rng.standard_normal((n, 3))
+    v *= (radius * rng.random(n) ** (1.0 / 3.0) / np.linalg.norm(v, axis=1))[:, None]
+    return (v + np.asarray(centre)).astype(np.float32)
+
+
+def test_ransac_long_survivor_list_bit_exact(gpu, oracle_native):
+    """The list path of a prefiltered round: k_ransac_count<true> -> k_ransac_err -> k_ransac_scan2.  Source and target are
+    two balls of radius 0.01: every finite hypothesis maps its sample centroid onto the target's, so every residual is at
+    most 0.04 < max_corr, every hypothesis counts all 300 pairs and every bound reaches the carried best -- whole chunks
+    survive.  The round [2048, 4096) leaves 2 048 survivors (> FEW_MAX = 1024) and the round [4096, 8192) has b = 4096
+    (> 1024), so that round counts its survivors with the list kernel.  confidence = 1: no early exit."""
+    from corsair_amd import backend as B
+
+    rng = np.random.default_rng(61)
+    src = _ball(rng, 300, (0.0, 0.0, 0.0), 0.01)
+    tgt = _ball(rng, 300, (0.3, -0.2, 0.1), 0.01)
+    S, D = torch.from_numpy(src).to(gpu), torch.from_numpy(tgt).to(gpu)
+    _prefilter_stats(reset=True)
+    T, inl, rmse, iters = (t.cpu().numpy() for t in B.ransac_batch(S, D, [0, 300], 0.2, 10, 8192, 1.0, 0))
+    surv = _prefilter_stats()[3]
+    wT, winl, wrmse, wit = oracle_native.ransac(src, tgt, 0.2, 10, 8192, 1.0, 0)
+    assert inl[0] == winl and iters[0] == wit, (inl[0], winl, iters[0], wit)
+    assert np.array_equal(T[0], wT)
+    assert rmse[0] == pytest.approx(wrmse, rel=1e-12)
+    assert winl == 300 and wit == 8192
+    assert surv >= 4096 + 2048, surv       # the last two rounds passed whole: the list path ran
+
+
+def test_ransac_device_placement_table_bit_exact(gpu, oracle_native):
+    """More than 64 problems on an XCD: the placement table of a round no longer fits the kernel argument and is read
+    from device memory by k_ransac_hyp and k_ransac_prefilter (xcd_ptr != nullptr).  520 live problems of 12 pairs (65 per
+    XCD) and two that are done at the start (0 and 3 pairs < ransac_n); the round [64, 128) is prefiltered."""
+    from corsair_amd import backend as B
+
+    rng = np.random.default_rng(62)
+    sizes = [12] * 520
+    sizes.insert(100, 0)
+    sizes.insert(400, 3)
+    probs = [_corr_problem(rng, m, float(rng.choice([0.3, 0.5, 0.8, 1.0])), pose_id=400 + i)[:2] for i, m in enumerate(sizes)]
+    off = np.concatenate([[0], np.cumsum(sizes)]).tolist()
+    src, tgt = np.concatenate([p[0] for p in probs]), np.concatenate([p[1] for p in probs])
+    _prefilter_stats(reset=True)
+    T, inl, rmse, iters = (t.cpu().numpy() for t in B.ransac_batch(torch.from_numpy(src).to(gpu), torch.from_numpy(tgt).to(gpu),
+                                                                   off, 0.2, 4, 128, 0.999, 3))
+    assert _prefilter_stats()[4] > 64 * 520    # hypotheses were evaluated beyond the first chunk
+    wT, winl, wrmse, wit = oracle_native.ransac_batch(src, tgt, off, 0.2, 4, 128, 0.999, 3)
+    assert np.array_equal(inl, winl) and np.array_equal(iters, wit)
+    assert np.array_equal(T, wT)
+    assert rmse == pytest.approx(wrmse, rel=1e-12)
+    for p in (100, 400):
+        assert np.array_equal(T[p], np.eye(4, dtype=np.float32)) and inl[p] == 0 and iters[p] == 0
+
+
 def _engine_features(gpu, cloud_ids, pose_ids):
     from corsair_amd import engine, synth
     from tests.helpers import make_batch

@@ -196,10 +196,13 @@ def test_library_exports_header_and_shared_solver():
         assert word in text
     # one definition of the eigen-solvers, included by both users
     csrc = os.path.join(os.path.dirname(_lib.LIB_PATH))
-    units = {n: open(os.path.join(csrc, n)).read() for n in ("horn.h", "ransac.hip", "icp.hip")}
+    ransac_units = ("ransac.hip", "ransac_hyp.hip", "ransac_prefilter.hip", "ransac_count.hip", "ransac.h")
+    units = {n: open(os.path.join(csrc, n)).read() for n in ("horn.h", "icp.hip") + ransac_units}
     for fn in ("bool horn_qcp(", "void jacobi4("):
-        assert fn in units["horn.h"] and fn not in units["ransac.hip"] and fn not in units["icp.hip"]
-    assert '#include "horn.h"' in units["ransac.hip"] and '#include "horn.h"' in units["icp.hip"]
+        assert fn in units["horn.h"]
+        for n in ("icp.hip",) + ransac_units:
+            assert fn not in units[n], n
+    assert '#include "horn.h"' in units["ransac_hyp.hip"] and '#include "horn.h"' in units["icp.hip"]
 
 
 def test_python_surface(tmp_path):
