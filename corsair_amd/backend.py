@@ -482,6 +482,7 @@ class IcpResult(NamedTuple):
     corr: Optional[torch.Tensor]   # int32, problem-major (problem p at corr_off[p]): local target row or -1
     corr_off: Optional[list]
     wfitness: Optional[torch.Tensor] = None   # f64 [n_prob] weighted inlier share (a robust kernel was asked for)
+    scale: Optional[torch.Tensor] = None      # f64 [n_prob] the factor the call added to T0 (with_scaling was asked for)
 
 
 ICP_KERNELS = {"l2": 0, "huber": 1, "cauchy": 2, "tukey": 3}    # CS_ICP_KERNEL_*
@@ -515,13 +516,28 @@ def normals_stats(reset=False):
 
 
 def icp_batch(src, soff, tgt, toff, src_seg, tgt_seg, T0, max_dist, max_iter=30, relative_fitness=1e-6,
-              relative_rmse=1e-6, return_corr=False, tgt_normals=None, kernel="l2", kernel_scale=None):
+              relative_rmse=1e-6, return_corr=False, tgt_normals=None, kernel="l2", kernel_scale=None, with_scaling=False,
+              scale_bounds=(0.5, 2.0)):
     """cs_icp_batch: point-to-point ICP of problem p = source segment src_seg[p] of `src` against target segment
     tgt_seg[p] of `tgt` (f32 [n,3] device, host offset lists), started at T0[p] (f32 [n_prob,4,4] device).  The semantics
     are the header comment of cs_icp_batch.  tgt_normals (f32, the shape of `tgt`; estimate_normals): point-to-plane
     estimation instead, cs_icp_plane_batch.  kernel = "huber" / "cauchy" / "tukey" with kernel_scale > 0: the robust
     point-to-plane estimation, cs_icp_plane_robust_batch, which also fills IcpResult.wfitness; it needs tgt_normals (robust
-    kernels exist for the plane estimation only, as in Open3D).  Returns an IcpResult; no host wait."""
+    kernels exist for the plane estimation only, as in Open3D).  with_scaling: cs_icp_scale_batch, either estimation with
+    an isotropic scale of the source as one more unknown (Open3D's with_scaling = true for the point estimation); T is then
+    a similarity and IcpResult.scale the factor the call added to T0.  A problem whose accumulated scale would leave
+    scale_bounds = (min, max), min <= 1 <= max, stops before that update; the default (0.5, 2.0) is untuned.  Robust
+    kernels with a scale are out of scope and refused.  Returns an IcpResult; no host wait."""
+    if with_scaling:
+        if kernel != "l2":
+            raise ValueError("icp_batch: with_scaling with a robust kernel (%r) is out of scope: robust kernels exist for "
+                             "the rigid plane estimation only" % (kernel,))
+        try:
+            smin, smax = float(scale_bounds[0]), float(scale_bounds[1])
+        except (TypeError, ValueError, IndexError):
+            raise ValueError("icp_batch: scale_bounds must be a pair (min, max), got %r" % (scale_bounds,))
+        if not (np.isfinite(smin) and np.isfinite(smax) and 0.0 < smin <= 1.0 <= smax):
+            raise ValueError("icp_batch: scale_bounds must be finite with 0 < min <= 1 <= max, got %r" % (scale_bounds,))
     if kernel not in ICP_KERNELS:
         raise ValueError("icp_batch: kernel must be one of %s, got %r" % (sorted(ICP_KERNELS), kernel))
     if kernel != "l2" and tgt_normals is None:
@@ -559,13 +575,20 @@ def icp_batch(src, soff, tgt, toff, src_seg, tgt_seg, T0, max_dist, max_iter=30,
     head = (i64_array(toff), i32_array(src_seg), i32_array(tgt_seg), n_prob, ptr(T0), float(max_dist), int(max_iter),
             float(relative_fitness), float(relative_rmse))
     tail = head + (ptr(T), ptr(T32), ptr(fitness), ptr(rmse), ptr(iters), ptr(ncorr), ptr(corr), stream_ptr())
-    wfitness = None
-    if tgt_normals is None:
-        check(_lib.load().cs_icp_batch(ptr(src), i64_array(soff), ptr(tgt), *tail))
-    else:
+    wfitness = scale = None
+    nrm = None
+    if tgt_normals is not None:
         nrm = _dev(tgt_normals, torch.float32, "target normals").contiguous()
         if nrm.shape != tgt.shape:
             raise ValueError("icp_batch: tgt_normals must have the shape of the target points")
+    if with_scaling:
+        scale = torch.empty(n_prob, dtype=torch.float64, device=dev)
+        check(_lib.load().cs_icp_scale_batch(
+            ptr(src), i64_array(soff), ptr(tgt), ptr(nrm), *head, smin, smax, ptr(T), ptr(T32), ptr(fitness), ptr(rmse),
+            ptr(scale), ptr(iters), ptr(ncorr), ptr(corr), stream_ptr()))
+    elif nrm is None:
+        check(_lib.load().cs_icp_batch(ptr(src), i64_array(soff), ptr(tgt), *tail))
+    else:
         if kernel == "l2":
             check(_lib.load().cs_icp_plane_batch(ptr(src), i64_array(soff), ptr(tgt), ptr(nrm), *tail))
         else:
@@ -575,7 +598,7 @@ def icp_batch(src, soff, tgt, toff, src_seg, tgt_seg, T0, max_dist, max_iter=30,
                 ptr(T32), ptr(fitness), ptr(rmse), ptr(wfitness), ptr(iters), ptr(ncorr), ptr(corr), stream_ptr()))
     if corr is not None:
         corr = corr[:corr_off[-1]]
-    return IcpResult(T, T32, fitness, rmse, iters, ncorr, corr, corr_off, wfitness)
+    return IcpResult(T, T32, fitness, rmse, iters, ncorr, corr, corr_off, wfitness, scale)
 
 
 def icp_stats(reset=False):

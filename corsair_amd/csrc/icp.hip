@@ -1,18 +1,21 @@
-// Batched ICP: point-to-point (cs_icp_batch), point-to-plane (cs_icp_plane_batch) and point-to-plane
-// with a robust kernel (cs_icp_plane_robust_batch).  The specifications are the comments of the three entries in
-// include/corsair_hip.h; tests/icp_ref.py, tests/icp_plane_ref.py and tests/icp_robust_ref.py restate them bit for bit.  The
-// estimation is a compile-time parameter EST (0 = point, 1 = plane, 2 = plane with a per-pair weight) of the sums at the end
+// Batched ICP: point-to-point (cs_icp_batch), point-to-plane (cs_icp_plane_batch), point-to-plane
+// with a robust kernel (cs_icp_plane_robust_batch) and both estimations with an isotropic scale (cs_icp_scale_batch).  The
+// specifications are the comments of the four entries in include/corsair_hip.h; tests/icp_ref.py, tests/icp_plane_ref.py,
+// tests/icp_robust_ref.py and tests/icp_scale_ref.py restate them bit for bit.  The estimation is a compile-time parameter
+// EST (0 = point, 1 = plane, 2 = plane with a per-pair weight, 3 = point + scale, 4 = plane + scale) of the sums at the end
 // of the association kernels and of the update; pose chain, association, evaluation, loop and stop rule are one code.  The
-// unweighted instantiations are what they were before the third existed: kernel = L2 runs EST = 1.
+// rigid instantiations are what they were before the others existed: kernel = L2 runs EST = 1, and nothing of EST = 3 / 4
+// is launched unless cs_icp_scale_batch is called.
 //
 // One call = one target preparation + (max_iter + 1) rounds, all enqueued without a host wait:
 //   k_icp_frame    per problem: the bounding box of its target segment (exact min / max), the origin and the
 //                  power-of-two scales of its fixed-point sums
 //   chamfer_pack16 the f16 hi / lo image, |S t|^2 and the float4 rows of every target, once per call
 //   round r:       k_icp_f16 (+ k_icp_exact for the workgroups it flags) or k_icp_exact alone -- association of the posed
-//                  ORIGINAL sources under the current T, 17 (point), 29 (plane) or 30 (weighted plane) order-free 64-bit
-//                  integer sums per problem; k_icp_step -- one lane per problem: fitness / rmse of that association, the
-//                  stop rule, Horn's fit (point) or the 6x6 normal equations by Cholesky (plane) from the sums, T <- U T.
+//                  ORIGINAL sources under the current T, 17 (point), 29 (plane), 30 (weighted plane), 18 (point + scale)
+//                  or 37 (plane + scale) order-free 64-bit integer sums per problem; k_icp_step -- one lane per problem:
+//                  fitness / rmse of that association, the stop rule, Horn's fit (point) or the 6x6 / 7x7 normal equations
+//                  by Cholesky (plane) from the sums, T <- U T.
 // A problem that has stopped raises its device flag; its workgroups leave on it in every later round.
 #include <math.h>
 
@@ -29,16 +32,37 @@ constexpr int ICP_TT = 512;               // target rows per LDS stage of the ex
 constexpr int ICP_NSUM = 17;              // count, sum p' (3), sum q' (3), sum p' q'^T (9), sum d^2
 constexpr int ICP_NSUM_PLANE = 29;        // count, sum J_i J_j (i <= j, 21), sum J_i r (6), sum d^2
 constexpr int ICP_NSUM_ROBUST = 30;       // the 29 plane sums (27 of them weighted) + sum w
-constexpr int ICP_POINT = 0, ICP_PLANE = 1, ICP_ROBUST = 2;
+constexpr int ICP_NSUM_POINT_S = 18;      // the 17 point sums + sum p'.p'
+constexpr int ICP_NSUM_PLANE_S = 37;      // count, sum J_i J_j (i <= j, 28), sum J_i r (7), sum d^2
+constexpr int ICP_POINT = 0, ICP_PLANE = 1, ICP_ROBUST = 2, ICP_POINT_S = 3, ICP_PLANE_S = 4;
+template <int EST>
+constexpr bool icp_is_plane() {
+  return EST == ICP_PLANE || EST == ICP_ROBUST || EST == ICP_PLANE_S;
+}
+template <int EST>
+constexpr bool icp_has_scale() {
+  return EST == ICP_POINT_S || EST == ICP_PLANE_S;
+}
 template <int EST>
 constexpr int icp_nsum() {
-  return EST == ICP_ROBUST ? ICP_NSUM_ROBUST : (EST == ICP_PLANE ? ICP_NSUM_PLANE : ICP_NSUM);
+  return EST == ICP_ROBUST    ? ICP_NSUM_ROBUST
+         : EST == ICP_PLANE   ? ICP_NSUM_PLANE
+         : EST == ICP_POINT_S ? ICP_NSUM_POINT_S
+         : EST == ICP_PLANE_S ? ICP_NSUM_PLANE_S
+                              : ICP_NSUM;
 }
-// sum d^2 is the last point sum and the 29th of both plane layouts
+// columns of the plane Jacobian: (a, n) and, with a scale, p'.n
+template <int EST>
+constexpr int icp_nj() {
+  return EST == ICP_PLANE_S ? 7 : 6;
+}
+// sum d^2 is the 17th of both point layouts and the one after the J_i r sums of every plane layout (the 29th / 37th)
 template <int EST>
 constexpr int icp_d2_at() {
-  return EST == ICP_POINT ? ICP_NSUM - 1 : ICP_NSUM_PLANE - 1;
+  return icp_is_plane<EST>() ? icp_nj<EST>() * (icp_nj<EST>() + 1) / 2 + icp_nj<EST>() + 1 : ICP_NSUM - 1;
 }
+// a rotational column of the plane Jacobian (bounded by 2 M) as opposed to a translational one (bounded by 1)
+__host__ __device__ constexpr bool icp_rot_col(int i) { return i < 3 || i == 6; }
 
 // Fixed-point sums.  A kept pair has |p - q|^2 < max_dist^2 and q inside the bounding box of the target segment, so
 // relative to the box's midpoint o every coordinate obeys |q'_c| <= h_c and |p'_c| <= h_c + max_dist, h = the box's
@@ -70,6 +94,13 @@ constexpr int icp_d2_at() {
 // 0 <= w <= 1 for every kernel below (a NaN weight is replaced by 0) and rounding to nearest is monotone, so
 // |fl(x w)| <= |x|: no weighted term is larger than the unweighted term bounded above.  The 30th sum adds I(w 2^(61 - eN)),
 // at most 2^eN terms of at most 2^(61 - eN).  Nothing leaves 2^61; count and d^2 are not weighted.
+//
+// Point + scale (EST = 3).  The 18th sum is p'.p' = fma(p'_z, p'_z, fma(p'_y, p'_y, p'_x p'_x)) <= 3 M^2 < 2^(2 eM + 2):
+// scale 2^(61 - eN - 2 eM - 2), two bits below s2, so each term stays below 2^(61 - eN) (exponent inside [-772, 259]).
+//
+// Plane + scale (EST = 4).  The seventh column J_6 = p'.n has |J_6| <= |p'| |n| <= sqrt(3) M < 2 M: bounded like a
+// rotational column a_c, so J_6 J_6 and a_i J_6 join the class rot x rot, n_i J_6 the class rot x trans and J_6 r the class
+// rot x r; their bounds are those above and no new scale is needed.
 constexpr int ICP_EM_MIN = -100;
 constexpr int ICP_EM_MAX = 400;
 constexpr int ICP_SUM_BITS = 61;
@@ -90,6 +121,7 @@ struct IcpFrame {
   double sc1, sc2;  // 2^s1, 2^s2
   double inv1, inv2;
   double clamp;     // 2^(61 - eN)
+  double sc_pp, inv_pp;   // 2^(s2 - 2) and its inverse: the sum of p'.p' (EST = 3)
 };
 struct IcpPlaneFrame {   // 2^s and 2^-s of the five product classes of the plane sums
   double sc_rr, inv_rr, sc_rt, inv_rt, sc_tt, inv_tt, sc_rd, inv_rd, sc_td, inv_td;
@@ -101,6 +133,7 @@ struct IcpLoss {     // the robust kernel of EST = 2 (CS_ICP_KERNEL_*), unused o
 struct IcpCriteria {
   double thr2;      // max_dist * max_dist
   double rel_fitness, rel_rmse;
+  double scale_min, scale_max;   // the interval of the accumulated scale (EST = 3, 4)
 };
 
 __global__ __launch_bounds__(256) void k_icp_frame(const IcpProb* __restrict__ probs, const float* __restrict__ tgt,
@@ -160,6 +193,8 @@ __global__ __launch_bounds__(256) void k_icp_frame(const IcpProb* __restrict__ p
   f.sc2 = ldexp(1.0, s2);
   f.inv2 = ldexp(1.0, -s2);
   f.clamp = ldexp(1.0, ICP_SUM_BITS - eN);
+  f.sc_pp = ldexp(1.0, s2 - 2);
+  f.inv_pp = ldexp(1.0, -(s2 - 2));
   frame[blockIdx.x] = f;
   if (pframe) {
     const int b = ICP_SUM_BITS - eN;
@@ -207,7 +242,7 @@ __device__ __forceinline__ double icp_weight(const IcpLoss& ls, double r) {
   return w == w ? w : 0.0;
 }
 
-// The sums of one workgroup (17 for the point estimation, 29 for the plane one, 30 for the weighted one): thread = one
+// The sums of one workgroup (17 point, 29 plane, 30 weighted plane, 18 point + scale, 37 plane + scale): thread = one
 // source (kept or not), wave shuffle, LDS across the four waves, then ONE 64-bit integer atomic per sum.  Integer addition:
 // the same total in any order.  nrow: the normal row of the matched target (plane estimation, kept pairs only).
 template <int EST>
@@ -221,35 +256,38 @@ __device__ __forceinline__ void icp_block_sums(bool kept, double px, double py, 
   long long v[NS];
 #pragma unroll
   for (int k = 0; k < NS; ++k) v[k] = 0;
-  if constexpr (EST != ICP_POINT) {
+  if constexpr (icp_is_plane<EST>()) {
+    constexpr int NJ = icp_nj<EST>(), NJJ = NJ * (NJ + 1) / 2;
     if (kept) {
       const IcpPlaneFrame g = *pfr;
       const double p[3] = {px - fr.o[0], py - fr.o[1], pz - fr.o[2]};
       const double n[3] = {(double)nrow[0], (double)nrow[1], (double)nrow[2]};
       const double e[3] = {px - (double)qx, py - (double)qy, pz - (double)qz};
       const double r = fma(e[2], n[2], fma(e[1], n[1], e[0] * n[0]));
-      const double J[6] = {fma(p[1], n[2], -(p[2] * n[1])), fma(p[2], n[0], -(p[0] * n[2])),
-                           fma(p[0], n[1], -(p[1] * n[0])), n[0], n[1], n[2]};
+      double J[NJ] = {fma(p[1], n[2], -(p[2] * n[1])), fma(p[2], n[0], -(p[0] * n[2])),
+                      fma(p[0], n[1], -(p[1] * n[0])), n[0], n[1], n[2]};
+      if constexpr (NJ == 7) J[6] = fma(p[2], n[2], fma(p[1], n[1], p[0] * n[0]));
       double w = 1.0;
       if constexpr (EST == ICP_ROBUST) w = icp_weight(loss, r);
       v[0] = 1;
       int at = 1;
 #pragma unroll
-      for (int i = 0; i < 6; ++i)
+      for (int i = 0; i < NJ; ++i)
 #pragma unroll
-        for (int j = i; j < 6; ++j) {
+        for (int j = i; j < NJ; ++j) {
           double prod = J[i] * J[j];   // rounded product (no contraction)
           if constexpr (EST == ICP_ROBUST) prod = prod * w;
-          const double sc = j < 3 ? g.sc_rr : (i < 3 ? g.sc_rt : g.sc_tt);
+          const bool ri = icp_rot_col(i), rj = icp_rot_col(j);
+          const double sc = ri && rj ? g.sc_rr : (ri || rj ? g.sc_rt : g.sc_tt);
           v[at++] = icp_fix(prod, sc, fr.clamp);
         }
 #pragma unroll
-      for (int i = 0; i < 6; ++i) {
+      for (int i = 0; i < NJ; ++i) {
         double prod = J[i] * r;
         if constexpr (EST == ICP_ROBUST) prod = prod * w;
-        v[22 + i] = icp_fix(prod, i < 3 ? g.sc_rd : g.sc_td, fr.clamp);
+        v[1 + NJJ + i] = icp_fix(prod, icp_rot_col(i) ? g.sc_rd : g.sc_td, fr.clamp);
       }
-      v[28] = icp_fix(d2, fr.sc2, fr.clamp);
+      v[1 + NJJ + NJ] = icp_fix(d2, fr.sc2, fr.clamp);
       if constexpr (EST == ICP_ROBUST) v[29] = icp_fix(w, fr.clamp, fr.clamp);
     }
   } else if (kept) {
@@ -269,6 +307,7 @@ __device__ __forceinline__ void icp_block_sums(bool kept, double px, double py, 
         v[7 + 3 * a + b] = icp_fix(prod, fr.sc2, fr.clamp);
       }
     v[16] = icp_fix(d2, fr.sc2, fr.clamp);
+    if constexpr (EST == ICP_POINT_S) v[17] = icp_fix(fma(p[2], p[2], fma(p[1], p[1], p[0] * p[0])), fr.sc_pp, fr.clamp);
   }
 #pragma unroll
   for (int k = 0; k < NS; ++k) {
@@ -343,8 +382,8 @@ __global__ __launch_bounds__(256) void k_icp_exact(const IcpWork* __restrict__ w
     qz = tp[2];
   }
   if (corr && active) corr[wk.c0 + tid] = kept ? bidx : -1;
-  icp_block_sums<EST>(kept, px, py, pz, qx, qy, qz, best, frame[wk.prob], EST != ICP_POINT ? pframe + wk.prob : nullptr,
-                      EST != ICP_POINT && kept ? tnrm + (pr.t0 + bidx) * 3 : nullptr, loss,
+  icp_block_sums<EST>(kept, px, py, pz, qx, qy, qz, best, frame[wk.prob], icp_is_plane<EST>() ? pframe + wk.prob : nullptr,
+                      icp_is_plane<EST>() && kept ? tnrm + (pr.t0 + bidx) * 3 : nullptr, loss,
                       sums + (int64_t)wk.prob * icp_nsum<EST>(), part);
 }
 
@@ -567,8 +606,8 @@ __global__ __launch_bounds__(256) void k_icp_f16(const IcpWork* __restrict__ wor
   if (kept) q = trow[my_row];
   if (corr && active) corr[wk.c0 + tid] = kept ? my_row : -1;
   icp_block_sums<EST>(kept, mpx, mpy, mpz, q.x, q.y, q.z, my_e, frame[wk.prob],
-                      EST != ICP_POINT ? pframe + wk.prob : nullptr,
-                      EST != ICP_POINT && kept ? tnrm + (pr.t0 + my_row) * 3 : nullptr, loss,
+                      icp_is_plane<EST>() ? pframe + wk.prob : nullptr,
+                      icp_is_plane<EST>() && kept ? tnrm + (pr.t0 + my_row) * 3 : nullptr, loss,
                       sums + (int64_t)wk.prob * icp_nsum<EST>(), part);
 }
 
@@ -607,9 +646,19 @@ __device__ __forceinline__ void icp_compose(const double (&R)[3][3], const doubl
   }
 }
 
-// The point-to-point update from the 17 sums: Horn's fit about the means.
-__device__ __forceinline__ void icp_update_point(const unsigned long long* __restrict__ S, double dn, const IcpFrame& fr,
-                                                 const double* __restrict__ Tp, double (&Tn)[12]) {
+// The scale step of EST = 3, 4: the problem stops (false) when s_u is not a finite positive number or the accumulated scale
+// s_u * scale would leave [scale_min, scale_max] (a NaN fails both comparisons).
+__device__ __forceinline__ bool icp_scale_ok(double su, double scale, const IcpCriteria& crit, double& scale_new) {
+  scale_new = su * scale;
+  return isfinite(su) && su > 0.0 && scale_new >= crit.scale_min && scale_new <= crit.scale_max;
+}
+
+// The point-to-point update from the 17 sums: Horn's fit about the means.  SCALE: Umeyama's scale from the 18th sum on top
+// of it, U = [s_u R | q_mean - s_u R p_mean]; false = the problem stops on the scale rules.
+template <bool SCALE>
+__device__ __forceinline__ bool icp_update_point(const unsigned long long* __restrict__ S, double dn, const IcpFrame& fr,
+                                                 const double* __restrict__ Tp, double (&Tn)[12], double scale,
+                                                 const IcpCriteria& crit, double& scale_new) {
   double sp[3], sq[3], mp[3], mq[3];
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
@@ -666,9 +715,29 @@ __device__ __forceinline__ void icp_update_point(const unsigned long long* __res
     pm[c] = mp[c] + fr.o[c];
     qm[c] = mq[c] + fr.o[c];
   }
+  if constexpr (SCALE) {
+    // s_u = sum_ab R_ab S_ab / (sum p'.p' - sum_a (sum p'_a) mean p'_a): the variance of the posed sources about their mean
+    double den = (double)(long long)S[17] * fr.inv_pp;
 #pragma unroll
-  for (int a = 0; a < 3; ++a) t[a] = qm[a] - fma(R[a][2], pm[2], fma(R[a][1], pm[1], R[a][0] * pm[0]));
+    for (int a = 0; a < 3; ++a) den = fma(-sp[a], mp[a], den);
+    double num = R[0][0] * Sm[0][0];
+#pragma unroll
+    for (int k = 1; k < 9; ++k) num = fma(R[k / 3][k % 3], Sm[k / 3][k % 3], num);
+    if (!(isfinite(den) && den > 0.0)) return false;
+    const double su = num / den;
+    if (!icp_scale_ok(su, scale, crit, scale_new)) return false;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      t[a] = fma(-su, fma(R[a][2], pm[2], fma(R[a][1], pm[1], R[a][0] * pm[0])), qm[a]);
+#pragma unroll
+      for (int b = 0; b < 3; ++b) R[a][b] = su * R[a][b];
+    }
+  } else {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) t[a] = qm[a] - fma(R[a][2], pm[2], fma(R[a][1], pm[1], R[a][0] * pm[0]));
+  }
   icp_compose(R, t, Tp, Tn);
+  return true;
 }
 
 // A pivot of the Cholesky factorisation must exceed this fraction of its own original diagonal entry.  pivot_j / A_jj is
@@ -679,26 +748,31 @@ constexpr double ICP_PIVOT_MIN = 0x1.0p-30;
 
 // The point-to-plane update from the 29 sums (the weighted layout has the same entries in the same places): A x = -b by an
 // unpivoted Cholesky, x = (alpha, t') about the origin o, the rotation of the quaternion (1, alpha / 2).  false: a pivot is
-// not finite or too small -- the problem stops.
+// not finite or too small -- the problem stops.  NJ = 7 (plane + scale): the 37 sums, a seventh unknown sigma,
+// s_u = 1 + sigma, U = [s_u R | t' + o - s_u R o]; false also when the scale rules stop the problem.
+template <int NJ>
 __device__ __forceinline__ bool icp_update_plane(const unsigned long long* __restrict__ S, const IcpFrame& fr,
-                                                 const IcpPlaneFrame& g, const double* __restrict__ Tp, double (&Tn)[12]) {
-  double A[6][6], L[6][6], bv[6], yv[6], xv[6];
+                                                 const IcpPlaneFrame& g, const double* __restrict__ Tp, double (&Tn)[12],
+                                                 double scale, const IcpCriteria& crit, double& scale_new) {
+  constexpr int NJJ = NJ * (NJ + 1) / 2;
+  double A[NJ][NJ], L[NJ][NJ], bv[NJ], yv[NJ], xv[NJ];
   {
     int at = 1;
 #pragma unroll
-    for (int i = 0; i < 6; ++i)
+    for (int i = 0; i < NJ; ++i)
 #pragma unroll
-      for (int j = i; j < 6; ++j) {
-        const double inv = j < 3 ? g.inv_rr : (i < 3 ? g.inv_rt : g.inv_tt);
+      for (int j = i; j < NJ; ++j) {
+        const bool ri = icp_rot_col(i), rj = icp_rot_col(j);
+        const double inv = ri && rj ? g.inv_rr : (ri || rj ? g.inv_rt : g.inv_tt);
         A[i][j] = (double)(long long)S[at++] * inv;
         A[j][i] = A[i][j];
       }
   }
 #pragma unroll
-  for (int i = 0; i < 6; ++i) bv[i] = (double)(long long)S[22 + i] * (i < 3 ? g.inv_rd : g.inv_td);
+  for (int i = 0; i < NJ; ++i) bv[i] = (double)(long long)S[1 + NJJ + i] * (icp_rot_col(i) ? g.inv_rd : g.inv_td);
   bool ok = true;
 #pragma unroll
-  for (int j = 0; j < 6; ++j) {
+  for (int j = 0; j < NJ; ++j) {
     double d = A[j][j];
 #pragma unroll
     for (int k = 0; k < j; ++k) d = fma(-L[j][k], L[j][k], d);
@@ -706,7 +780,7 @@ __device__ __forceinline__ bool icp_update_plane(const unsigned long long* __res
     const double ljj = sqrt(d);
     L[j][j] = ljj;
 #pragma unroll
-    for (int i = j + 1; i < 6; ++i) {
+    for (int i = j + 1; i < NJ; ++i) {
       double v = A[i][j];
 #pragma unroll
       for (int k = 0; k < j; ++k) v = fma(-L[i][k], L[j][k], v);
@@ -715,25 +789,37 @@ __device__ __forceinline__ bool icp_update_plane(const unsigned long long* __res
   }
   if (!ok) return false;
 #pragma unroll
-  for (int i = 0; i < 6; ++i) {
+  for (int i = 0; i < NJ; ++i) {
     double v = -bv[i];
 #pragma unroll
     for (int k = 0; k < i; ++k) v = fma(-L[i][k], yv[k], v);
     yv[i] = v / L[i][i];
   }
 #pragma unroll
-  for (int i = 5; i >= 0; --i) {
+  for (int i = NJ - 1; i >= 0; --i) {
     double v = yv[i];
 #pragma unroll
-    for (int k = i + 1; k < 6; ++k) v = fma(-L[k][i], xv[k], v);
+    for (int k = i + 1; k < NJ; ++k) v = fma(-L[k][i], xv[k], v);
     xv[i] = v / L[i][i];
   }
   double R[3][3], t[3];
   icp_quat_rotation(1.0, 0.5 * xv[0], 0.5 * xv[1], 0.5 * xv[2], R);
-  // p <- R (p - o) + t' + o:  t = t' + o - R o
+  if constexpr (NJ == 7) {
+    // p <- s_u R (p - o) + t' + o:  t = t' + o - s_u R o
+    const double su = 1.0 + xv[6];
+    if (!icp_scale_ok(su, scale, crit, scale_new)) return false;
 #pragma unroll
-  for (int a = 0; a < 3; ++a)
-    t[a] = (xv[3 + a] + fr.o[a]) - fma(R[a][2], fr.o[2], fma(R[a][1], fr.o[1], R[a][0] * fr.o[0]));
+    for (int a = 0; a < 3; ++a) {
+      t[a] = fma(-su, fma(R[a][2], fr.o[2], fma(R[a][1], fr.o[1], R[a][0] * fr.o[0])), xv[3 + a] + fr.o[a]);
+#pragma unroll
+      for (int b = 0; b < 3; ++b) R[a][b] = su * R[a][b];
+    }
+  } else {
+    // p <- R (p - o) + t' + o:  t = t' + o - R o
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+      t[a] = (xv[3 + a] + fr.o[a]) - fma(R[a][2], fr.o[2], fma(R[a][1], fr.o[1], R[a][0] * fr.o[0]));
+  }
   icp_compose(R, t, Tp, Tn);
   return true;
 }
@@ -745,9 +831,10 @@ __global__ void k_icp_step(const IcpProb* __restrict__ probs, int n_prob, const 
                            const IcpPlaneFrame* __restrict__ pframe, IcpCriteria crit, int round, int last,
                            unsigned long long* __restrict__ sums, int32_t* __restrict__ done, double* __restrict__ T,
                            float* __restrict__ T32, double* __restrict__ fitness, double* __restrict__ rmse,
-                           double* __restrict__ wfitness, int32_t* __restrict__ iters, int32_t* __restrict__ ncorr) {
+                           double* __restrict__ wfitness, double* __restrict__ scale, int32_t* __restrict__ iters,
+                           int32_t* __restrict__ ncorr) {
   constexpr int NS = icp_nsum<EST>();
-  constexpr int MIN_CORR = EST != ICP_POINT ? 6 : 3;
+  constexpr int MIN_CORR = icp_is_plane<EST>() ? icp_nj<EST>() : 3;   // one pair per unknown of the plane system
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= n_prob) return;
   double* Tp = T + (int64_t)p * 16;
@@ -776,13 +863,16 @@ __global__ void k_icp_step(const IcpProb* __restrict__ probs, int n_prob, const 
     if (!stop) {
       double Tn[12];
       bool solved = true;
-      if constexpr (EST != ICP_POINT)
-        solved = icp_update_plane(S, fr, pframe[p], Tp, Tn);
+      double sc_old = 1.0, sc_new = 1.0;   // the accumulated scale before and after this update (EST = 3, 4)
+      if constexpr (icp_has_scale<EST>()) sc_old = scale[p];
+      if constexpr (icp_is_plane<EST>())
+        solved = icp_update_plane<icp_nj<EST>()>(S, fr, pframe[p], Tp, Tn, sc_old, crit, sc_new);
       else
-        icp_update_point(S, dn, fr, Tp, Tn);
+        solved = icp_update_point<EST == ICP_POINT_S>(S, dn, fr, Tp, Tn, sc_old, crit, sc_new);
       if (solved && icp_all_finite(Tn, 12)) {
 #pragma unroll
         for (int i = 0; i < 12; ++i) Tp[i] = Tn[i];
+        if constexpr (icp_has_scale<EST>()) scale[p] = sc_new;
         iters[p] = iters[p] + 1;
 #pragma unroll
         for (int k = 0; k < NS; ++k) S[k] = 0;
@@ -798,14 +888,15 @@ __global__ void k_icp_step(const IcpProb* __restrict__ probs, int n_prob, const 
 }
 
 __global__ void k_icp_init(const float* __restrict__ T0, int n_prob, double* __restrict__ T, double* __restrict__ fitness,
-                           double* __restrict__ rmse, double* __restrict__ wfitness, int32_t* __restrict__ iters,
-                           int32_t* __restrict__ ncorr, int32_t* __restrict__ done) {
+                           double* __restrict__ rmse, double* __restrict__ wfitness, double* __restrict__ scale,
+                           int32_t* __restrict__ iters, int32_t* __restrict__ ncorr, int32_t* __restrict__ done) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= n_prob) return;
   for (int i = 0; i < 16; ++i) T[(int64_t)p * 16 + i] = (double)T0[(int64_t)p * 16 + i];
   fitness[p] = 0.0;
   rmse[p] = 0.0;
   if (wfitness) wfitness[p] = 0.0;
+  if (scale) scale[p] = 1.0;
   iters[p] = 0;
   ncorr[p] = 0;
   done[p] = 0;
@@ -814,13 +905,15 @@ __global__ void k_icp_init(const float* __restrict__ T0, int n_prob, double* __r
 std::atomic<unsigned long long> g_icp_stats[2];
 
 // Every entry: d_tnrm is the normal array of the plane estimations (EST = 1, 2), loss the kernel of EST = 2, d_wfitness the
-// optional weighted inlier share of cs_icp_plane_robust_batch (NULL for the other two entries).
+// optional weighted inlier share of cs_icp_plane_robust_batch (NULL for the other entries), scale_min / scale_max / d_scale
+// the interval and the output of cs_icp_scale_batch (EST = 3, 4).
 template <int EST>
 int icp_run(const char* name, const float* d_src, const int64_t* h_soff, const float* d_tgt, const float* d_tnrm,
             const int64_t* h_toff, const int32_t* h_src_seg, const int32_t* h_tgt_seg, int n_prob, const float* d_T0,
             double max_dist, int max_iter, double relative_fitness, double relative_rmse, double* d_T, float* d_T32,
             double* d_fitness, double* d_rmse, int32_t* d_iters, int32_t* d_ncorr, int32_t* d_corr, void* stream,
-            IcpLoss loss = IcpLoss{CS_ICP_KERNEL_L2, 0.0}, double* d_wfitness = nullptr) {
+            IcpLoss loss = IcpLoss{CS_ICP_KERNEL_L2, 0.0}, double* d_wfitness = nullptr, double scale_min = 1.0,
+            double scale_max = 1.0, double* d_scale = nullptr) {
   constexpr int NS = icp_nsum<EST>();
   CS_REQUIRE(h_soff && h_toff && h_src_seg && h_tgt_seg, CS_ERR_INVALID, "%s: NULL table", name);
   CS_REQUIRE(n_prob >= 0, CS_ERR_INVALID, "%s: negative problem count", name);
@@ -830,6 +923,7 @@ int icp_run(const char* name, const float* d_src, const int64_t* h_soff, const f
              "%s: a convergence threshold is NaN", name);
   if (n_prob == 0) return CS_OK;
   CS_REQUIRE(d_T0 && d_T && d_fitness && d_rmse && d_iters && d_ncorr, CS_ERR_INVALID, "%s: NULL argument", name);
+  CS_REQUIRE(!icp_has_scale<EST>() || d_scale, CS_ERR_INVALID, "%s: NULL scale output", name);
   std::vector<IcpProb> probs(n_prob);
   std::vector<IcpWork> work;
   int64_t nt_rows = 0, n_corr_rows = 0;
@@ -861,7 +955,7 @@ int icp_run(const char* name, const float* d_src, const int64_t* h_soff, const f
   }
   CS_REQUIRE(work.empty() || d_src, CS_ERR_INVALID, "%s: NULL source array", name);
   CS_REQUIRE(nt_rows == 0 || d_tgt, CS_ERR_INVALID, "%s: NULL target array", name);
-  CS_REQUIRE(EST == ICP_POINT || nt_rows == 0 || d_tnrm, CS_ERR_INVALID, "%s: NULL target normal array", name);
+  CS_REQUIRE(!icp_is_plane<EST>() || nt_rows == 0 || d_tnrm, CS_ERR_INVALID, "%s: NULL target normal array", name);
   hipStream_t s = (hipStream_t)stream;
   pool_use_stream(s);
   const bool use_f16 = !env_first_is("CS_ICP_F16", '0');
@@ -874,7 +968,7 @@ int icp_run(const char* name, const float* d_src, const int64_t* h_soff, const f
   PoolBuf<unsigned long long> sums((size_t)n_prob * NS + 2);   // + the two statistics counters
   PoolBuf<int32_t> done((size_t)n_prob);
   CS_REQUIRE(frame.p && sums.p && done.p, CS_ERR_HIP, "%s: scratch allocation failed", name);
-  if (EST != ICP_POINT) CS_REQUIRE(pframe.alloc((size_t)n_prob), CS_ERR_HIP, "%s: scratch allocation failed", name);
+  if (icp_is_plane<EST>()) CS_REQUIRE(pframe.alloc((size_t)n_prob), CS_ERR_HIP, "%s: scratch allocation failed", name);
   int rc = upload(dprob, probs, s);
   if (!rc) rc = upload(dwork, work, s);
   if (rc) return rc;
@@ -882,8 +976,8 @@ int icp_run(const char* name, const float* d_src, const int64_t* h_soff, const f
   ProfScope prof("icp", s, flop * (double)(max_iter + 1));
   CS_HIP_CHECK(hipMemsetAsync(sums.p, 0, sizeof(unsigned long long) * ((size_t)n_prob * NS + 2), s));
   const dim3 pgrid((unsigned)ceil_div(n_prob, 64));
-  hipLaunchKernelGGL(k_icp_init, pgrid, dim3(64), 0, s, d_T0, n_prob, d_T, d_fitness, d_rmse, d_wfitness, d_iters,
-                     d_ncorr, done.p);
+  hipLaunchKernelGGL(k_icp_init, pgrid, dim3(64), 0, s, d_T0, n_prob, d_T, d_fitness, d_rmse, d_wfitness,
+                     icp_has_scale<EST>() ? d_scale : (double*)nullptr, d_iters, d_ncorr, done.p);
   hipLaunchKernelGGL(k_icp_frame, dim3((unsigned)n_prob), dim3(256), 0, s, dprob.p, d_tgt, max_dist, frame.p, pframe.p);
   // the targets do not move: one image for every round
   PoolBuf<_Float16> img16;
@@ -904,6 +998,8 @@ int icp_run(const char* name, const float* d_src, const int64_t* h_soff, const f
   crit.thr2 = max_dist * max_dist;
   crit.rel_fitness = relative_fitness;
   crit.rel_rmse = relative_rmse;
+  crit.scale_min = scale_min;
+  crit.scale_max = scale_max;
   for (int round = 0; round <= max_iter; ++round) {
     if (n_work) {
       if (use_f16) {
@@ -920,8 +1016,8 @@ int icp_run(const char* name, const float* d_src, const int64_t* h_soff, const f
       }
     }
     hipLaunchKernelGGL(k_icp_step<EST>, pgrid, dim3(64), 0, s, dprob.p, n_prob, frame.p, pframe.p, crit, round,
-                       round == max_iter ? 1 : 0, sums.p, done.p, d_T, d_T32, d_fitness, d_rmse, d_wfitness, d_iters,
-                       d_ncorr);
+                       round == max_iter ? 1 : 0, sums.p, done.p, d_T, d_T32, d_fitness, d_rmse, d_wfitness, d_scale,
+                       d_iters, d_ncorr);
   }
   CS_LAUNCH_CHECK();
   if (want_stats) {
@@ -980,6 +1076,25 @@ int cs_icp_plane_robust_batch(const float* d_src, const int64_t* h_soff, const f
   return icp_run<ICP_ROBUST>(name, d_src, h_soff, d_tgt, d_tgt_normal, h_toff, h_src_seg, h_tgt_seg, n_prob, d_T0, max_dist,
                              max_iter, relative_fitness, relative_rmse, d_T, d_T32, d_fitness, d_rmse, d_iters, d_ncorr,
                              d_corr, stream, IcpLoss{kernel, kernel_scale}, d_wfitness);
+}
+
+int cs_icp_scale_batch(const float* d_src, const int64_t* h_soff, const float* d_tgt, const float* d_tgt_normal,
+                       const int64_t* h_toff, const int32_t* h_src_seg, const int32_t* h_tgt_seg, int n_prob,
+                       const float* d_T0, double max_dist, int max_iter, double relative_fitness, double relative_rmse,
+                       double scale_min, double scale_max, double* d_T, float* d_T32, double* d_fitness, double* d_rmse,
+                       double* d_scale, int32_t* d_iters, int32_t* d_ncorr, int32_t* d_corr, void* stream) {
+  const char* name = "cs_icp_scale_batch";
+  CS_REQUIRE(std::isfinite(scale_min) && std::isfinite(scale_max), CS_ERR_INVALID, "%s: a scale bound is not finite", name);
+  CS_REQUIRE(scale_min > 0.0 && scale_min <= 1.0 && scale_max >= 1.0, CS_ERR_INVALID,
+             "%s: the scale interval must satisfy 0 < scale_min <= 1 <= scale_max", name);
+  const IcpLoss l2{CS_ICP_KERNEL_L2, 0.0};
+  if (d_tgt_normal)
+    return icp_run<ICP_PLANE_S>(name, d_src, h_soff, d_tgt, d_tgt_normal, h_toff, h_src_seg, h_tgt_seg, n_prob, d_T0,
+                                max_dist, max_iter, relative_fitness, relative_rmse, d_T, d_T32, d_fitness, d_rmse, d_iters,
+                                d_ncorr, d_corr, stream, l2, nullptr, scale_min, scale_max, d_scale);
+  return icp_run<ICP_POINT_S>(name, d_src, h_soff, d_tgt, nullptr, h_toff, h_src_seg, h_tgt_seg, n_prob, d_T0, max_dist,
+                              max_iter, relative_fitness, relative_rmse, d_T, d_T32, d_fitness, d_rmse, d_iters, d_ncorr,
+                              d_corr, stream, l2, nullptr, scale_min, scale_max, d_scale);
 }
 
 }  // extern "C"

@@ -58,6 +58,10 @@ class Config:
     # which NOBODY HAS TUNED; set it explicitly for real data
     icp_kernel: str = "l2"
     icp_kernel_scale: float = 0.0
+    # the refinement also fits an isotropic scale of the query (cs_icp_scale_batch), either estimation, no robust
+    # kernel.  A query whose accumulated scale would leave icp_scale_bounds stops before that update; (0.5, 2.0) is UNTUNED
+    icp_with_scaling: bool = False
+    icp_scale_bounds: tuple = (0.5, 2.0)
 
     def icp_distance(self):
         return self.icp_max_dist if self.icp_max_dist > 0 else 2.0 * self.voxel_size
@@ -72,6 +76,15 @@ class Config:
             raise ValueError("Config.icp_kernel must be one of %s, got %r" % (ICP_KERNEL_NAMES, self.icp_kernel))
         if self.icp_kernel != "l2" and self.icp_estimation != "plane":
             raise ValueError("Config.icp_kernel %r needs icp_estimation = 'plane'" % (self.icp_kernel,))
+        if self.icp_with_scaling:
+            if self.icp_kernel != "l2":
+                raise ValueError("Config.icp_with_scaling with a robust icp_kernel (%r) is out of scope" % (self.icp_kernel,))
+            if self.icp_max_iter <= 0:
+                raise ValueError("Config.icp_with_scaling needs icp_max_iter > 0 (the refinement is off)")
+            lo, hi = (float(v) for v in self.icp_scale_bounds)
+            if not (np.isfinite(lo) and np.isfinite(hi) and 0.0 < lo <= 1.0 <= hi):
+                raise ValueError("Config.icp_scale_bounds must be finite with 0 < min <= 1 <= max, got %r"
+                                 % (self.icp_scale_bounds,))
         if not 3 <= int(self.icp_normal_k) <= 32:
             raise ValueError("Config.icp_normal_k must lie in [3, 32], got %r" % (self.icp_normal_k,))
         if not 0 <= float(self.icp_normal_radius) < float("inf"):
@@ -206,8 +219,10 @@ class Pipeline:
                                 cads.offsets, syms, c.k_nn, c.max_corr, 0, anchor_ids, 100,
                                 c.ransac_max_iter, c.ransac_confidence, use_symmetry, force_gate,
                                 query_anchors, c.icp_max_iter, c.icp_distance() if c.icp_max_iter > 0 else None,
-                                c.icp_estimation, c.icp_normal_k, cads.normal, c.normal_radius(), c.icp_kernel,
-                                c.icp_scale() if c.icp_kernel != "l2" else None)
+                                c.icp_estimation, c.icp_normal_k, cads.normal, c.normal_radius(),
+                                icp_with_scaling=c.icp_with_scaling,
+                                icp_scale_bounds=tuple(c.icp_scale_bounds) if c.icp_with_scaling else None,
+                                icp_kernel=c.icp_kernel, icp_kernel_scale=c.icp_scale() if c.icp_kernel != "l2" else None)
 
     def with_normals(self, s):
         """`s` with the normals of its origins (one cs_estimate_normals call over the whole set, or one
@@ -295,7 +310,9 @@ def _icp_report(a):
     return (f"\nicp refinement:\ntranslation error: {a['rte_mean']},\n"
             f"rte 0.02: {a['rte_002']}, rte 0.05: {a['rte_005']}, rte 0.10: {a['rte_010']}, rte 0.15: {a['rte_015']}\n"
             f"rotation error: {a['rre_mean_rad']},\nrre 5: {a['rre_5']}, rre 15: {a['rre_15']}, rre 45: {a['rre_45']},\n"
-            f"chamfer distance: {a['chamfer_mean']}\nmean icp updates: {a['iters_mean']}")
+            f"chamfer distance: {a['chamfer_mean']}\nmean icp updates: {a['iters_mean']}" +
+            (f"\nicp scale: mean |s - 1| {a['scale_dev_mean']}, largest |s - 1| {a['scale_dev_max']}"
+             if "scale_dev_mean" in a else ""))
 
 
 def run_eval(pipe, catalog, queries, best_match, table, base_T, lib_T, syms, category="chair",
@@ -326,7 +343,8 @@ def run_eval(pipe, catalog, queries, best_match, table, base_T, lib_T, syms, cat
     stat = retrieval_stat(pipe, qs.desc, cat.desc, best_match, table)
 
     per_query = None if (ignore_cache or cache_dir is None) else \
-        C_.load_results(cache_dir, category, register_top1, icp=cfg.icp_max_iter > 0)
+        C_.load_results(cache_dir, category, register_top1, icp=cfg.icp_max_iter > 0,
+                        icp_scale=bool(getattr(cfg, "icp_with_scaling", False)))
     from_cache = per_query is not None
     if per_query is None:
         pos_idx = np.asarray(stat["top1_predict" if register_top1 else "gt"], dtype=np.int64)
@@ -376,7 +394,9 @@ def register_queries(pipe, qs, query_ids, cat, pos_idx, syms, base_T, lib_T, for
     `query_ids` (they seed the anchor draws, so a query gives the same result whichever rank or batch it lands in):
     sym_pose against CAD pos_idx[q] and eval_pose of both estimates, batched.  Returns the nine arrays of
     evaluation.py:421-441 (cache.NAMES) for these queries, in the order of `query_ids`; with ICP refinement on
-    (pipe.cfg.icp_max_iter > 0) also the arrays of cache.ICP_NAMES.
+    (pipe.cfg.icp_max_iter > 0) also the arrays of cache.ICP_NAMES, and with pipe.cfg.icp_with_scaling those of
+    cache.ICP_SCALE_NAMES; the ICP losses are then eval_pose's on T_icp with its 3x3 block divided by the scale (the trace
+    formula assumes a rotation).
     in_flight > 1: that many batches at a time, each on its own host thread and HIP stream (batches are independent;
     the library's scratch cache is per thread and stream-ordered) -- same results, the host work of one batch hides
     behind the kernels of the others (bench.py's `batches_in_flight`)."""
@@ -387,8 +407,9 @@ def register_queries(pipe, qs, query_ids, cat, pos_idx, syms, base_T, lib_T, for
     icp_on = getattr(pipe.cfg, "icp_max_iter", 0) > 0
     if icp_on and len(query_ids) and hasattr(pipe, "with_normals"):
         cat = pipe.with_normals(cat)     # point-to-plane: the catalog's normals once per evaluation, gathered per batch
-    names = C_.NAMES + (C_.ICP_NAMES if icp_on else ())
-    dtypes = dict(C_.DTYPES, **C_.ICP_DTYPES)
+    scale_on = icp_on and bool(getattr(pipe.cfg, "icp_with_scaling", False))
+    names = C_.NAMES + (C_.ICP_NAMES if icp_on else ()) + (C_.ICP_SCALE_NAMES if scale_on else ())
+    dtypes = dict(C_.DTYPES, **C_.ICP_DTYPES, **C_.ICP_SCALE_DTYPES)
     if not len(query_ids):
         return {k: np.zeros((0, 4, 4) if k.startswith("Ts_est") else 0, dtypes[k]) for k in names}
     batches = [np.arange(s, min(len(query_ids), s + bs)) for s in range(0, len(query_ids), bs)]
@@ -410,8 +431,15 @@ def register_queries(pipe, qs, query_ids, cat, pos_idx, syms, base_T, lib_T, for
                "chamfer_dist_ransac": cdr, "chamfer_dist_sym": cdb}
         if icp_on:
             Ti, cdi, iti = (t.cpu().numpy() for t in (res.T_icp, res.cd_icp, res.icp_iters))
-            t_i, r_i = pose_losses(Ti, T0, T1, cad_sym)
+            Tl = Ti
+            if scale_on:
+                sc = res.icp_scale.cpu().numpy()
+                Tl = Ti.copy()
+                Tl[:, :3, :3] = (Ti[:, :3, :3].astype(np.float64) / sc[:, None, None]).astype(Ti.dtype)
+            t_i, r_i = pose_losses(Tl, T0, T1, cad_sym)
             extra = {"Ts_est_icp": Ti, "t_losses_icp": t_i, "r_losses_icp": r_i, "chamfer_dist_icp": cdi, "icp_iters": iti}
+            if scale_on:
+                extra["icp_scale"] = sc
             out.update({k: np.asarray(v, dtypes[k]) for k, v in extra.items()})
         return out
 
@@ -457,6 +485,10 @@ def finish_eval(stat, per_query, from_cache):
         icp = aggregate(per_query["r_losses_icp"], per_query["t_losses_icp"], per_query["chamfer_dist_icp"])
         icp["rre_mean_rad"] = float(np.mean(np.asarray(per_query["r_losses_icp"], np.float64)))
         icp["iters_mean"] = float(np.mean(per_query["icp_iters"]))
+        if "icp_scale" in per_query:
+            dev = np.abs(np.asarray(per_query["icp_scale"], np.float64) - 1.0)
+            icp["scale_dev_mean"] = float(np.mean(dev)) if len(dev) else 0.0
+            icp["scale_dev_max"] = float(np.max(dev)) if len(dev) else 0.0
         res.icp = icp
         res.report += _icp_report(icp)
     return res
@@ -588,6 +620,12 @@ def build_parser():
                     help="robust kernel on the point-to-plane residual (needs --icp-estimation plane); l2 = none")
     ap.add_argument("--icp-kernel-scale", type=float, default=0.0,
                     help="scale k of --icp-kernel; 0 = 1 * voxel size (an untuned default)")
+    ap.add_argument("--icp-with-scaling", action="store_true",
+                    help="the ICP refinement also fits an isotropic scale of the query (needs --icp-iters > 0, no robust kernel)")
+    ap.add_argument("--icp-scale-min", type=float, default=0.5,
+                    help="lower bound of the scale the ICP may add, in (0, 1] (an untuned default)")
+    ap.add_argument("--icp-scale-max", type=float, default=2.0,
+                    help="upper bound of the scale the ICP may add, >= 1 (an untuned default)")
     ap.add_argument("--in-flight", type=int, default=3, help="registration batches in flight (host threads x HIP streams)")
     ap.add_argument("--device", default="cuda", choices=["cuda"], help="there is no CPU path")
     return ap
@@ -610,7 +648,8 @@ def main(argv=None):
     cfg = Config(n_points=a.n_points, batch_size=a.batch_size, embed_batch_size=a.embed_batch_size,
                  ransac_max_iter=a.ransac_max_iter, icp_max_iter=a.icp_iters, icp_max_dist=a.icp_max_dist,
                  icp_estimation=a.icp_estimation, icp_normal_k=a.icp_normal_k, icp_kernel=a.icp_kernel,
-                 icp_kernel_scale=a.icp_kernel_scale, icp_normal_radius=a.icp_normal_radius)
+                 icp_kernel_scale=a.icp_kernel_scale, icp_normal_radius=a.icp_normal_radius,
+                 icp_with_scaling=a.icp_with_scaling, icp_scale_bounds=(a.icp_scale_min, a.icp_scale_max))
     cfg.check_icp()
     pipe = Pipeline(sd, esd, device=a.device, config=cfg)
     cad_names, catalog = load_cloud_dir(a.catalog_dir, a.n_points, "catalog")

@@ -61,6 +61,7 @@ class SymPoseResult:
     icp_rmse: torch.Tensor = None       # f64 [P]
     icp_iters: torch.Tensor = None      # int32 [P] updates applied
     icp_wfitness: torch.Tensor = None   # f64 [P] weighted inlier share; only with a robust icp_kernel
+    icp_scale: torch.Tensor = None      # f64 [P] the isotropic scale the ICP added to T_best; only with icp_with_scaling
 
     def hypotheses(self, p):
         """Problems of pair p in evaluation order."""
@@ -152,8 +153,8 @@ def part_configs(K, pos_sym):
 def sym_pose_batch(baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_nn=5, max_corr=0.20, seed=0,
                    anchor_ids=None, n_anchor=100, max_iter=100000, confidence=0.999,
                    use_symmetry=True, force_gate=False, query_anchors=None, icp_max_iter=0, icp_max_dist=None,
-                   icp_estimation="point", icp_normal_k=16, normals1=None, icp_normal_radius=None, icp_kernel="l2",
-                   icp_kernel_scale=None):
+                   icp_estimation="point", icp_normal_k=16, normals1=None, icp_normal_radius=None, icp_with_scaling=False,
+                   icp_scale_bounds=None, icp_kernel="l2", icp_kernel_scale=None):
     """baseF f32 [N0,16], xyz0 f32 [N0,3] (query voxels of all pairs, segment p = off0[p]:off0[p+1]);
     posF/xyz1/off1 likewise for the CAD side; pos_syms: symmetry label per pair.
     anchor_ids[p] = (counter0, counter1) seeds the anchor draw of pair p (default (2p, 2p+1)).
@@ -168,7 +169,15 @@ def sym_pose_batch(baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_nn=5, max_co
     icp_normal_k neighbours here; the same result fields are filled.  icp_normal_radius (None = k-NN): those normals
     come from the at most icp_normal_k nearest rows strictly inside that radius instead (cs_estimate_normals_hybrid).
     icp_kernel = "huber" / "cauchy" / "tukey" with icp_kernel_scale > 0 (plane estimation only): the residuals are weighted
-    by that robust kernel (cs_icp_plane_robust_batch) and icp_wfitness is filled too."""
+    by that robust kernel (cs_icp_plane_robust_batch) and icp_wfitness is filled too.
+    icp_with_scaling: either estimation also fits an isotropic scale of the query (cs_icp_scale_batch); T_icp is then a
+    similarity, icp_scale the factor, and cd_icp is cs_chamfer_1dir under that similarity (its pose chain is affine).
+    icp_scale_bounds = (min, max), None = backend.icp_batch's untuned default (0.5, 2.0).  Robust kernels with a scale are
+    out of scope and refused.  These two parameters stand BEFORE icp_kernel / icp_kernel_scale, which stay the last two: a
+    caller that passed icp_kernel by position must pass it by keyword now (such a call fails on the scale bounds, it does
+    not run with other settings)."""
+    if icp_with_scaling and icp_kernel != "l2":
+        raise ValueError("sym_pose_batch: icp_with_scaling with a robust icp_kernel (%r) is out of scope" % (icp_kernel,))
     if icp_kernel not in B.ICP_KERNELS:
         raise ValueError("sym_pose_batch: icp_kernel must be one of %s, got %r" % (sorted(B.ICP_KERNELS), icp_kernel))
     if icp_kernel != "l2" and icp_estimation != "plane":
@@ -340,9 +349,15 @@ def sym_pose_batch(baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_nn=5, max_co
         nrm = None
         if icp_estimation == "plane":
             nrm = normals1 if normals1 is not None else B.estimate_normals(xyz1, off1, icp_normal_k, icp_normal_radius)
+        scaling = {}
+        if icp_with_scaling:
+            scaling = {"with_scaling": True}
+            if icp_scale_bounds is not None:
+                scaling["scale_bounds"] = icp_scale_bounds
         r = B.icp_batch(xyz0, off0, xyz1, off1, pairs, pairs, res.T_best, icp_max_dist, icp_max_iter, tgt_normals=nrm,
-                        kernel=icp_kernel, kernel_scale=icp_kernel_scale)
+                        kernel=icp_kernel, kernel_scale=icp_kernel_scale, **scaling)
         res.T_icp, res.icp_fitness, res.icp_rmse, res.icp_iters = r.T32, r.fitness, r.rmse, r.iters
         res.icp_wfitness = r.wfitness
+        res.icp_scale = r.scale
         res.cd_icp = B.chamfer_1dir(xyz0, off0, xyz1, off1, pairs, pairs, r.T32)
     return res

@@ -45,6 +45,12 @@ class Config:
     # 1 * voxel_size (UNTUNED, as in harness.Config)
     icp_kernel: str = "l2"
     icp_kernel_scale: float = 0.0
+    # > 0: the posed copy is also scaled by exp(u), u uniform in +-max_log_scale (drawn only then: the random stream and
+    # every output of the default are what they were); icp_with_scaling: the refinement fits that isotropic scale
+    # (cs_icp_scale_batch, no robust kernel) inside icp_scale_bounds -- (0.5, 2.0) is UNTUNED, as in harness.Config
+    max_log_scale: float = 0.0
+    icp_with_scaling: bool = False
+    icp_scale_bounds: tuple = (0.5, 2.0)
 
     def icp_distance(self):
         return self.icp_max_dist if self.icp_max_dist > 0 else 2.0 * self.voxel_size
@@ -135,9 +141,19 @@ def get_symmetry_label(pc, cd_threshold):
 def evaluate(pipe, clouds, cfg=None, pairs_per_batch=16, seed=None, force_gate=False):
     """clouds: list of raw [n,3] arrays.  Returns a list of result dicts (one per model x pose) with
     the keys of registration_worker (evaluation-shapenet.py:242-275); with cfg.icp_max_iter > 0 also T_est_icp, rte_icp,
-    rre_icp, chamfer_dist_icp and icp_iters of the refined pose."""
+    rre_icp, chamfer_dist_icp and icp_iters of the refined pose.  cfg.max_log_scale > 0: the posed copy is s R x + t with
+    s = exp(u); the result keys do not change for that alone.  cfg.icp_with_scaling: T_est_icp is a similarity, rte_icp / rre_icp are
+    eval_pose's on it with its 3x3 block divided by the fitted scale, and the results gain scale_gt, scale_icp and
+    scale_err_icp = |scale_icp / scale_gt - 1|."""
     cfg = cfg or Config()
     icp_on = cfg.icp_max_iter > 0
+    scale_on = bool(cfg.icp_with_scaling)
+    if scale_on and not icp_on:
+        raise ValueError("Config.icp_with_scaling needs icp_max_iter > 0 (the refinement is off)")
+    if scale_on and cfg.icp_kernel != "l2":
+        raise ValueError("Config.icp_with_scaling with a robust icp_kernel (%r) is out of scope" % (cfg.icp_kernel,))
+    if not 0 <= float(cfg.max_log_scale) < float("inf"):
+        raise ValueError("Config.max_log_scale must be finite and >= 0, got %r" % (cfg.max_log_scale,))
     rng = np.random.default_rng(cfg.random_seed if seed is None else seed)
     dev = pipe.device
     jobs = []
@@ -148,7 +164,11 @@ def evaluate(pipe, clouds, cfg=None, pairs_per_batch=16, seed=None, force_gate=F
             pose = generate_random_pose(cfg, rng)
             # generate_test_pc_pair (:115-119): the model stays in its own type, the posed copy is the f64
             # product with the f64 pose; quantize_pc (:97-107) floors each in its type and narrows afterwards
-            jobs.append((mi, pi, pc, pc @ pose[:3, :3].T + pose[:3, [3]].T, pose, label))
+            if cfg.max_log_scale > 0:
+                s_gt = float(np.exp(rng.uniform(-cfg.max_log_scale, cfg.max_log_scale)))
+                jobs.append((mi, pi, pc, s_gt * (pc @ pose[:3, :3].T) + pose[:3, [3]].T, pose, label, s_gt))
+            else:
+                jobs.append((mi, pi, pc, pc @ pose[:3, :3].T + pose[:3, [3]].T, pose, label, 1.0))
     results = []
     for s in range(0, len(jobs), pairs_per_batch):
         chunk = jobs[s:s + pairs_per_batch]
@@ -167,28 +187,43 @@ def evaluate(pipe, clouds, cfg=None, pairs_per_batch=16, seed=None, force_gate=F
                                [(2 * (s + i), 2 * (s + i) + 1) for i in range(P)], 100,
                                cfg.ransac_max_iter, cfg.ransac_confidence, True, force_gate, None,
                                cfg.icp_max_iter, cfg.icp_distance() if icp_on else None, cfg.icp_estimation,
-                               cfg.icp_normal_k, None, cfg.normal_radius(), cfg.icp_kernel,
-                               cfg.icp_scale() if cfg.icp_kernel != "l2" else None)
+                               cfg.icp_normal_k, None, cfg.normal_radius(), icp_with_scaling=scale_on,
+                               icp_scale_bounds=tuple(cfg.icp_scale_bounds) if scale_on else None,
+                               icp_kernel=cfg.icp_kernel,
+                               icp_kernel_scale=cfg.icp_scale() if cfg.icp_kernel != "l2" else None)
         Tb, Tr = res.T_best.cpu().numpy(), res.T_ransac.cpu().numpy()
         cdb, cdr = res.cd_best.cpu().numpy(), res.cd_ransac.cpu().numpy()
-        for i, (mi, pi, _, _, pose, label) in enumerate(chunk):
+        for i, (mi, pi, _, _, pose, label, s_gt) in enumerate(chunk):
             rte_s, rre_s = eval_pose(Tb[i], np.eye(4), pose, axis_symmetry=label)
             rte_r, rre_r = eval_pose(Tr[i], np.eye(4), pose, axis_symmetry=label)
             results.append(dict(model=mi, pose_idx=pi, symmetry_label=label, sym_success=bool(res.ok[i]),
                                 T_est_sym=Tb[i], chamfer_dist_sym=float(cdb[i]), T_est_ransac=Tr[i],
                                 chamfer_dist_ransac=float(cdr[i]), rte_sym=float(rte_s), rre_sym=float(rre_s),
                                 rte_ransac=float(rte_r), rre_ransac=float(rre_r), pose_gt=pose))
+            if scale_on:
+                results[-1]["scale_gt"] = s_gt
         if icp_on:
             Ti, cdi, iti = res.T_icp.cpu().numpy(), res.cd_icp.cpu().numpy(), res.icp_iters.cpu().numpy()
-            for i, (_, _, _, _, pose, label) in enumerate(chunk):
-                rte_i, rre_i = eval_pose(Ti[i], np.eye(4), pose, axis_symmetry=label)
+            sci = res.icp_scale.cpu().numpy() if scale_on else None
+            for i, (_, _, _, _, pose, label, s_gt) in enumerate(chunk):
+                Tl = Ti[i]
+                if scale_on:             # eval_pose's trace formula assumes a rotation
+                    Tl = Ti[i].copy()
+                    Tl[:3, :3] = (Ti[i][:3, :3].astype(np.float64) / sci[i]).astype(Ti.dtype)
+                rte_i, rre_i = eval_pose(Tl, np.eye(4), pose, axis_symmetry=label)
                 results[s + i].update(T_est_icp=Ti[i], chamfer_dist_icp=float(cdi[i]), rte_icp=float(rte_i),
                                       rre_icp=float(rre_i), icp_iters=int(iti[i]))
+                if scale_on:
+                    results[s + i].update(scale_icp=float(sci[i]), scale_err_icp=float(abs(sci[i] / s_gt - 1.0)))
     return results
 
 
 def _has_icp(results):
     return bool(results) and "rre_icp" in results[0]
+
+
+def _has_scale(results):
+    return bool(results) and "scale_err_icp" in results[0]
 
 
 def threshold_table(results, rre_deg=(5, 15, 45), rte=(0.02, 0.05, 0.10, 0.15)):
@@ -199,6 +234,9 @@ def threshold_table(results, rre_deg=(5, 15, 45), rte=(0.02, 0.05, 0.10, 0.15)):
         t = np.array([x[f"rte_{tag}"] for x in results])
         out[tag] = {**{f"rre<={d}": float(np.mean(r <= np.deg2rad(d))) for d in rre_deg},
                     **{f"rte<={v}": float(np.mean(t <= v)) for v in rte}}
+    if _has_scale(results):          # (Scan2CAD accepts an alignment whose scale is within 20 %)
+        e = np.array([x["scale_err_icp"] for x in results])
+        out["icp"].update({f"scale<={v}": float(np.mean(e <= v)) for v in SCALE_THRESHOLDS})
     return out
 
 
@@ -206,23 +244,29 @@ def threshold_table(results, rre_deg=(5, 15, 45), rte=(0.02, 0.05, 0.10, 0.15)):
 CSV_COLUMNS = ("model", "pose_idx", "symmetry_label", "sym_success", "rte_sym", "rre_sym", "cd_sym", "rte_ransac",
                "rre_ransac", "cd_ransac")            # evaluation-shapenet.py:323-334
 ICP_CSV_COLUMNS = ("rte_icp", "rre_icp", "cd_icp", "icp_iters")      # trailing, only when the refinement ran
+SCALE_CSV_COLUMNS = ("scale_gt", "scale_icp", "scale_err_icp")       # trailing, only when the refinement fitted a scale
+SCALE_THRESHOLDS = (0.05, 0.10, 0.20)
 
 
 def write_results(results, names, csv_file, npz_file):
     """results-*.csv with the reference's columns and poses-*.npz with poses_gt / poses_pred_sym / poses_pred_ransac
     (evaluation-shapenet.py:345-380); results of a run with ICP refinement add the trailing ICP_CSV_COLUMNS and
-    poses_pred_icp."""
+    poses_pred_icp, those of one with a fitted scale also the SCALE_CSV_COLUMNS and the arrays of the same names."""
     import csv
 
     icp = _has_icp(results)
+    sc = _has_scale(results)
     with open(csv_file, "w", newline="") as f:
         w = csv.writer(f)
-        w.writerow(CSV_COLUMNS + (ICP_CSV_COLUMNS if icp else ()))
+        w.writerow(CSV_COLUMNS + (ICP_CSV_COLUMNS if icp else ()) + (SCALE_CSV_COLUMNS if sc else ()))
         for r in results:
             w.writerow([names[r["model"]], r["pose_idx"], r["symmetry_label"], r["sym_success"], r["rte_sym"], r["rre_sym"],
                         r["chamfer_dist_sym"], r["rte_ransac"], r["rre_ransac"], r["chamfer_dist_ransac"]] +
-                       ([r["rte_icp"], r["rre_icp"], r["chamfer_dist_icp"], r["icp_iters"]] if icp else []))
+                       ([r["rte_icp"], r["rre_icp"], r["chamfer_dist_icp"], r["icp_iters"]] if icp else []) +
+                       ([r[k] for k in SCALE_CSV_COLUMNS] if sc else []))
     extra = {"poses_pred_icp": np.stack([r["T_est_icp"] for r in results])} if icp else {}
+    if sc:
+        extra.update({k: np.asarray([r[k] for r in results], np.float64) for k in SCALE_CSV_COLUMNS})
     with open(npz_file, "wb") as f:
         np.savez(f, poses_gt=np.stack([r["pose_gt"] for r in results]),
                  poses_pred_sym=np.stack([r["T_est_sym"] for r in results]),
@@ -245,6 +289,9 @@ def summary(results):
         ti, ri = r["rte_icp"] <= 0.02, r["rre_icp"] <= five
         for i, f in enumerate((ti, ri, ti & ri)):
             lines[i] += f", icp: {f.sum() / n:.4f}"
+    if _has_scale(results):
+        e = np.asarray([x["scale_err_icp"] for x in results])
+        lines.append("scale error " + ", ".join(f"<= {v:.2f}: {np.mean(e <= v):.4f}" for v in SCALE_THRESHOLDS))
     return "\n".join(lines)
 
 
@@ -276,6 +323,12 @@ def build_parser():
     ap.add_argument("--icp-kernel", default="l2", choices=["l2", "huber", "cauchy", "tukey"],
                     help="robust kernel on the point-to-plane residual (needs --icp-estimation plane); l2 = none")
     ap.add_argument("--icp-kernel-scale", type=float, default=0.0, help="scale of --icp-kernel; 0 = 1 * voxel size (untuned)")
+    ap.add_argument("--max-log-scale", type=float, default=0.0,
+                    help="the posed copy is also scaled by exp(u), u uniform in +-this (0 = the reference's rigid poses)")
+    ap.add_argument("--icp-with-scaling", action="store_true",
+                    help="the ICP refinement also fits an isotropic scale (needs --icp-iters > 0, no robust kernel)")
+    ap.add_argument("--icp-scale-min", type=float, default=0.5, help="lower bound of the fitted scale, in (0, 1] (untuned)")
+    ap.add_argument("--icp-scale-max", type=float, default=2.0, help="upper bound of the fitted scale, >= 1 (untuned)")
     ap.add_argument("--out-dir", default=".")
     ap.add_argument("--device", default="cuda", choices=["cuda"])
     return ap
@@ -305,7 +358,8 @@ def main(argv=None):
                  max_pitch_deg=a.max_pitch_deg, max_yaw_deg=a.max_yaw_deg, max_translation=a.max_translation,
                  ransac_max_iter=a.ransac_max_iter, icp_max_iter=a.icp_iters, icp_max_dist=a.icp_max_dist,
                  icp_estimation=a.icp_estimation, icp_normal_k=a.icp_normal_k, icp_kernel=a.icp_kernel,
-                 icp_kernel_scale=a.icp_kernel_scale, icp_normal_radius=a.icp_normal_radius)
+                 icp_kernel_scale=a.icp_kernel_scale, icp_normal_radius=a.icp_normal_radius, max_log_scale=a.max_log_scale,
+                 icp_with_scaling=a.icp_with_scaling, icp_scale_bounds=(a.icp_scale_min, a.icp_scale_max))
     results = evaluate(pipe, clouds, cfg)
     postfix = f"shapenet-seed{a.random_seed}-{a.category}-{len(files)}-{a.n_poses_per_model}"
     os.makedirs(a.out_dir, exist_ok=True)

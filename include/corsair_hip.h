@@ -610,6 +610,48 @@ int cs_icp_plane_robust_batch(const float* d_src, const int64_t* h_soff, const f
                               int32_t* d_corr, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * cs_icp_scale_batch: cs_icp_batch (d_tgt_normal = NULL) or cs_icp_plane_batch (d_tgt_normal != NULL) with one more unknown,
+ * an isotropic scale of the source: Open3D's TransformationEstimationPointToPoint(with_scaling = true) for the point
+ * estimation; the plane estimation with a scale has no Open3D counterpart (tests/icp_scale_ref.py restates both
+ * bit for bit).  The arguments are those of cs_icp_plane_batch plus scale_min, scale_max and the output d_scale f64 [n_prob].
+ * Problems, pose chain, association (both paths, the strict voucher, CS_ICP_F16, CS_ICP_STATS / cs_icp_stats), evaluation,
+ * loop, stop criteria, outputs, independence, empty-segment answers (scale 1), refusals and stream behaviour are those of
+ * cs_icp_batch: the same code.  T then carries s R in its upper block.  The association only ever sees POSED points
+ * p = T x: the f16 range test (|p_c| < 60), the voucher and its error budget (a function of |p| and of the largest |t|) are
+ * evaluated on p, whatever T produced it, so nothing there assumes a rotation and both paths still return the same bits.
+ * Every operation below is ONE IEEE f64 operation unless a fused fma(a, b, c) is written.
+ *   Point + scale.  18 sums: the 17 of cs_icp_batch and I(pp * 2^(s2 - 2)), pp = fma(p'_z, p'_z, fma(p'_y, p'_y, p'_x * p'_x))
+ *     <= 3 M^2 < 2^(2 eM + 2), so no term reaches the clamp.  sp, sq, mp, mq, S, R as in cs_icp_batch, then
+ *       den = (double)Spp * 2^-(s2 - 2), then den = fma(-sp_a, mp_a, den) for a = x, y, z;
+ *       num = R_00 * S_00, then num = fma(R_ab, S_ab, num) for the other eight (a, b), row-major;   s_u = num / den;
+ *       t_a = fma(-s_u, fma(R_a2, pm_2, fma(R_a1, pm_1, R_a0 * pm_0)), qm_a);   U = [s_u * R_ab | t]
+ *     (Umeyama's fit with R from Horn's quaternion).  The problem stops when an evaluation has n_corr < 3.
+ *   Plane + scale.  The Jacobian gets a seventh column J_6 = fma(p'_z, n_z, fma(p'_y, n_y, p'_x * n_x)) (the derivative of
+ *     the residual by sigma in p <- (1 + sigma) R p' + t'), |J_6| <= sqrt(3) M < 2 M like a rotational column.  37 sums: count;
+ *     I((J_i * J_j) * 2^s) for i <= j < 7, row-major (28); I((J_i * r) * 2^s) (7); I(d2 * 2^s2).  A column is rotational for
+ *     i < 3 or i = 6, translational otherwise, and the exponents of cs_icp_plane_batch apply by class: both rotational
+ *     b - 2 eM - 3, one of them b - eM - 2, none b - 1, J_i r b - 2 eM - 2 (rotational) or b - eM - 1.  The 7x7 system is
+ *     solved by cs_icp_plane_batch's Cholesky sequence with 7 in the place of 6 and its pivot rule on all seven pivots;
+ *       s_u = 1 + x_6;  R the Cayley rotation of (x_0, x_1, x_2);
+ *       t_a = fma(-s_u, fma(R_a2, o_2, fma(R_a1, o_1, R_a0 * o_0)), x_(3+a) + o_a);   U = [s_u * R_ab | t],
+ *     the map x -> s_u R (x - o) + o + t'.  The problem stops when an evaluation has n_corr < 7.
+ *   T <- U T by cs_icp_batch's chain in both.
+ *   Scale: d_scale[p] starts at 1 and becomes s_u * d_scale[p] with every applied update: the factor this call added to T0.
+ *     A problem stops at once, keeping T and its scale, the update NOT applied, when den is not finite or not > 0 (point),
+ *     when s_u is not finite or not > 0, or when s_u * d_scale[p] is not inside [scale_min, scale_max].  The interval is the
+ *     guard against the collapse of a scaled ICP started far from the truth, which shrinks the source onto one target point
+ *     while the rmse falls.  d_iters counts applied updates only.
+ *   Refused (CS_ERR_INVALID) in addition, before anything is launched: bounds that are not finite, scale_min <= 0,
+ *     scale_min > 1, scale_max < 1; a NULL d_scale.
+ * Profile family "icp".
+ * ---------------------------------------------------------------------------------------- */
+int cs_icp_scale_batch(const float* d_src, const int64_t* h_soff, const float* d_tgt, const float* d_tgt_normal,
+                       const int64_t* h_toff, const int32_t* h_src_seg, const int32_t* h_tgt_seg, int n_prob,
+                       const float* d_T0, double max_dist, int max_iter, double relative_fitness, double relative_rmse,
+                       double scale_min, double scale_max, double* d_T, float* d_T32, double* d_fitness, double* d_rmse,
+                       double* d_scale, int32_t* d_iters, int32_t* d_ncorr, int32_t* d_corr, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * cs_estimate_normals: one surface normal per row from the k nearest rows of the row's own segment, the semantics of
  * [O3D-knowledge] Open3D's PointCloud::estimate_normals(KDTreeSearchParamKNN(k)): the eigenvector of the smallest
  * eigenvalue of the neighbourhood's covariance.  The reference has no such step, so this comment is the specification

@@ -29,6 +29,11 @@ exactly 11 full rounds: max_iter 10 with both convergence thresholds 0), mean RR
 `--clutter F` makes the share F of every source clutter first: rows of the pair's target displaced by 0.035 / 0.06 of
 max_dist along +x or +y (two slabs just off the surface, every row inside max_dist of a target row), moved into the
 source's frame.  Without --json the result goes to profiles/icp_robust_<kernel>[_clutter].json.
+`--with-scaling [--scale-mismatch S]` measures, alternating in one process on the same problems: point, plane,
+point + scale and plane + scale (cs_icp_scale_batch), normals supplied.  Every source is shrunk by S about the origin of its
+frame first (default 1.0; the true scale is 1 / S) and the start stays rigid.  Per call: ms, updates, ms per round (both
+definitions of --kernel), the fallback share, mean RRE / RTE (on the rotation: the 3x3 block divided by the fitted scale)
+and the mean scale error |scale * S - 1|.  Without --json the result goes to profiles/icp_scale.json.
 Prints one JSON line."""
 import argparse
 import json
@@ -278,6 +283,58 @@ def robust_report(a, res, x0, off0, x1, off1, T0, truth, max_dist):
     return res
 
 
+def scale_report(a, res, x0, off0, x1, off1, T0, truth, max_dist):
+    """The measurement of DESIGN 16: the two rigid calls and their siblings with a scale, alternating."""
+    pairs = list(range(N_PAIRS))
+    S = a.scale_mismatch
+    x0 = (x0.double() * S).float().contiguous()
+    nrm = B.estimate_normals(x1, off1, a.normal_k)
+    kw = {"point": {}, "plane": {"tgt_normals": nrm}, "point_scale": {"with_scaling": True},
+          "plane_scale": {"tgt_normals": nrm, "with_scaling": True}}
+
+    def call(k, max_iter=MAX_ITER, **more):
+        return B.icp_batch(x0, off0, x1, off1, pairs, pairs, T0, max_dist, max_iter, **kw[k], **more)
+
+    full = dict(relative_fitness=0.0, relative_rmse=0.0)           # no problem converges: max_iter + 1 full rounds
+    fns = {k: (lambda k=k: call(k)) for k in kw}
+    fns.update({k + "_full": (lambda k=k: call(k, 10, **full)) for k in kw})
+    ms = timed_alternating(fns, a.reps)
+    res.update({"normal_k": a.normal_k, "scale_mismatch": S, "true_scale": 1.0 / S, "scale_bounds": [0.5, 2.0]})
+
+    def errs(T, scale):
+        T = T.cpu().numpy().astype(np.float64)
+        rre = [np.degrees(np.arccos(np.clip((np.trace((T[p, :3, :3] / scale[p]) @ truth[p, :3, :3].T) - 1) / 2, -1, 1)))
+               for p in pairs]
+        rte = [np.linalg.norm(T[p, :3, 3] - truth[p, :3, 3]) for p in pairs]
+        return round(float(np.mean(rre)), 4), round(float(np.mean(rte)), 5)
+
+    res["rre_deg_rte_before"] = errs(T0, np.ones(N_PAIRS))
+    os.environ["CS_ICP_STATS"] = "1"
+    for k in kw:
+        B.icp_stats(reset=True)
+        r = call(k)
+        st = B.icp_stats(reset=True)
+        it = r.iters.cpu().numpy()
+        full_it = call(k, 10, **full).iters.cpu().numpy()
+        sc = np.ones(N_PAIRS) if r.scale is None else r.scale.cpu().numpy()
+        res[k] = {"ms": ms[k], "updates": {"mean": round(float(it.mean()), 2), "min": int(it.min()), "max": int(it.max())},
+                  "ms_per_round": round(ms[k] / (float(it.max()) + 1), 4),
+                  "full_rounds_ms": ms[k + "_full"], "full_rounds_updates_min": int(full_it.min()),
+                  "full_rounds_ms_per_round": round(ms[k + "_full"] / 11.0, 4),
+                  "fallback_share": round(st[1] / max(st[0], 1), 5), "rre_deg_rte_after": errs(r.T, sc),
+                  "scale_error_mean": round(float(np.mean(np.abs(sc * S - 1.0))), 6),
+                  "scale_error_max": round(float(np.max(np.abs(sc * S - 1.0))), 6),
+                  "fitness_mean": round(float(r.fitness.mean()), 4)}
+    del os.environ["CS_ICP_STATS"]
+    for k in ("point", "plane"):
+        res["%s_scale_over_%s_per_round" % (k, k)] = round(res[k + "_scale"]["ms_per_round"] / res[k]["ms_per_round"], 4)
+        res["%s_scale_over_%s_per_full_round" % (k, k)] = round(res[k + "_scale"]["full_rounds_ms_per_round"] /
+                                                                res[k]["full_rounds_ms_per_round"], 4)
+    res["plane_scale_over_point_scale_total"] = round(res["plane_scale"]["ms"] / res["point_scale"]["ms"], 4)
+    res["bar_plane_scale_le_point_scale_total"] = bool(res["plane_scale"]["ms"] <= res["point_scale"]["ms"])
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--json", default=None)
@@ -297,7 +354,15 @@ def main():
     ap.add_argument("--kernel-scale", type=float, default=0.0, help="scale of --kernel; 0 = one voxel (untuned)")
     ap.add_argument("--clutter", type=float, default=0.0,
                     help="share of every source that is clutter just off the target's surface (with --kernel)")
+    ap.add_argument("--with-scaling", action="store_true",
+                    help="point / plane against point + scale / plane + scale (cs_icp_scale_batch), alternating (DESIGN 16)")
+    ap.add_argument("--scale-mismatch", type=float, default=1.0,
+                    help="with --with-scaling: every source is shrunk by this factor first; the start stays rigid")
     a = ap.parse_args()
+    if not 0.5 < a.scale_mismatch < 2.0 or (a.scale_mismatch != 1.0 and not a.with_scaling):
+        ap.error("--scale-mismatch needs a factor in (0.5, 2) and --with-scaling")
+    if a.with_scaling and a.kernel != "l2":
+        ap.error("--with-scaling with a robust --kernel is out of scope")
     if not 0.0 <= a.clutter < 1.0 or (a.clutter > 0 and a.kernel == "l2"):
         ap.error("--clutter needs a share in [0, 1) and a --kernel")
     dev = torch.device("cuda:0")
@@ -309,6 +374,12 @@ def main():
     res = {"device": torch.cuda.get_device_name(dev), "hip": torch.version.hip, "pairs": N_PAIRS, "voxel": VOXEL,
            "source_rows": off0[-1], "target_rows": off1[-1], "max_dist": max_dist, "max_iter": MAX_ITER,
            "perturbation": {"deg": a.deg, "trans": a.trans}}
+    if a.with_scaling:
+        res = scale_report(a, res, x0, off0, x1, off1, T0, truth, max_dist)
+        print(json.dumps(res))
+        with open(a.json or os.path.join(ROOT, "profiles", "icp_scale.json"), "w") as f:
+            json.dump(res, f, indent=1)
+        return
     if a.kernel != "l2":
         res = robust_report(a, res, x0, off0, x1, off1, T0, truth, max_dist)
         print(json.dumps(res))
