@@ -109,6 +109,8 @@ def _declare(lib):
         "cs_estimate_normals": (c_int, [vp, POINTER(c_int64), c_int, c_int, vp, vp]),
         "cs_estimate_normals_hybrid": (c_int, [vp, POINTER(c_int64), c_int, c_double, c_int, vp, vp]),
         "cs_normals_stats": (None, [POINTER(c_uint64), c_int]),
+        "cs_fgr_batch": (c_int, [vp, vp, POINTER(c_int64), c_int, c_double, c_double, c_double, c_int, c_int, c_double,
+                                 c_int, c_uint64, vp, vp, vp, vp, vp, vp, vp]),
         "cs_prof_enable": (None, [c_int]),
         "cs_prof_reset": (None, []),
         "cs_prof_get": (c_int, [c_char_p, POINTER(c_double), POINTER(c_int64)]),

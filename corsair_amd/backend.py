@@ -625,6 +625,42 @@ def ransac_batch(src, tgt, offsets, max_corr, ransac_n=10, max_iter=100000, conf
     return T, inl, rmse, iters
 
 
+class FgrResult(NamedTuple):
+    T: torch.Tensor          # f32 [n_prob,4,4], T64 cast once
+    T64: torch.Tensor        # f64 [n_prob,4,4]
+    inliers: torch.Tensor    # int32 [n_prob] pairs of the problem within max_corr of their target under T64
+    rmse: torch.Tensor       # f64 [n_prob] of those inliers
+    iters: torch.Tensor      # int32 [n_prob] updates applied
+    n_tuple: torch.Tensor    # int32 [n_prob] tuples kept by the tuple test, -1 with the test off
+
+
+def fgr_batch(src, tgt, offsets, max_corr, mu_floor=0.025, division_factor=1.4, iteration_number=64, tuple_test=True,
+              tuple_scale=0.95, max_tuple=1000, seed=0):
+    """cs_fgr_batch: Fast Global Registration of the correspondence lists of ransac_batch's layout (f32 [M,3] device pairs,
+    host offset list).  The semantics are the header comment of cs_fgr_batch; max_corr only serves the reported inliers and
+    rmse.  mu_floor (Open3D's maximum_correspondence_distance, in units of the normalised frame) is untuned.  Returns an
+    FgrResult; no host wait."""
+    src = _dev(src, torch.float32, "source correspondences").contiguous()
+    tgt = _dev(tgt, torch.float32, "target correspondences").contiguous()
+    if src.shape != tgt.shape or src.dim() != 2 or src.shape[1] != 3:
+        raise ValueError("fgr_batch: correspondences must be two [M, 3] arrays of one shape")
+    if len(offsets) < 1 or int(offsets[-1]) > src.shape[0]:
+        raise ValueError("fgr_batch: the offset table exceeds the correspondence arrays")
+    n_prob = len(offsets) - 1
+    dev = src.device
+    T = torch.empty((n_prob, 4, 4), dtype=torch.float32, device=dev)
+    T64 = torch.empty((n_prob, 4, 4), dtype=torch.float64, device=dev)
+    inl = torch.empty(n_prob, dtype=torch.int32, device=dev)
+    rmse = torch.empty(n_prob, dtype=torch.float64, device=dev)
+    iters = torch.empty(n_prob, dtype=torch.int32, device=dev)
+    n_tuple = torch.empty(n_prob, dtype=torch.int32, device=dev)
+    check(_lib.load().cs_fgr_batch(ptr(src), ptr(tgt), i64_array(offsets), n_prob, float(max_corr), float(mu_floor),
+                                   float(division_factor), int(iteration_number), 1 if tuple_test else 0,
+                                   float(tuple_scale), int(max_tuple), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(T), ptr(T64),
+                                   ptr(inl), ptr(rmse), ptr(iters), ptr(n_tuple), stream_ptr()))
+    return FgrResult(T, T64, inl, rmse, iters, n_tuple)
+
+
 def partition_by_label(label, d_off, n_cloud):
     """Rows of every cloud stably partitioned by part label (split_corr's part order).  d_off: int64 device
     tensor [n_cloud + 1].  Returns int64 [N] global row indices."""

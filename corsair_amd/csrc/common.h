@@ -124,6 +124,12 @@ __host__ __device__ static inline uint64_t rng_u64(uint64_t seed, uint64_t itr, 
   x = x ^ (x >> 31);
   return x;
 }
+// an index in [0, m) from the upper half of a draw by multiply-shift (no modulo): the RANSAC's samples and the trials of
+// the tuple test of cs_fgr_batch
+__host__ __device__ static inline uint32_t rng_index(uint64_t seed, uint64_t itr, uint64_t j,
+                                                     uint32_t m) {
+  return (uint32_t)(((rng_u64(seed, itr, j) >> 32) * (uint64_t)m) >> 32);
+}
 
 // LDS-DMA of 64 x 16 B (global_load_lds_dwordx4): lane l's 16 bytes at g land at LDS byte address
 // lds_addr + 16 l (lds_addr wave-uniform, in an SGPR).  Written as inline asm ON PURPOSE: behind the

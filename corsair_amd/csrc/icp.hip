@@ -22,6 +22,7 @@
 #include <algorithm>
 
 #include "horn.h"
+#include "icp_update.h"
 #include "nn_common.h"
 
 namespace cs {
@@ -617,35 +618,6 @@ __device__ __forceinline__ bool icp_all_finite(const double* v, int n) {
   return f;
 }
 
-// R of the quaternion (w, x, y, z), normalised by division: cs_ransac_batch's formula.
-__device__ __forceinline__ void icp_quat_rotation(double qw, double qx, double qy, double qz, double (&R)[3][3]) {
-  const double qn = sqrt(qw * qw + qx * qx + qy * qy + qz * qz);
-  qw = qw / qn;
-  qx = qx / qn;
-  qy = qy / qn;
-  qz = qz / qn;
-  R[0][0] = 1.0 - 2.0 * (qy * qy + qz * qz);
-  R[0][1] = 2.0 * (qx * qy - qw * qz);
-  R[0][2] = 2.0 * (qx * qz + qw * qy);
-  R[1][0] = 2.0 * (qx * qy + qw * qz);
-  R[1][1] = 1.0 - 2.0 * (qx * qx + qz * qz);
-  R[1][2] = 2.0 * (qy * qz - qw * qx);
-  R[2][0] = 2.0 * (qx * qz - qw * qy);
-  R[2][1] = 2.0 * (qy * qz + qw * qx);
-  R[2][2] = 1.0 - 2.0 * (qx * qx + qy * qy);
-}
-
-// Tn = U T, U = (R, t): the first three rows of the 4x4.
-__device__ __forceinline__ void icp_compose(const double (&R)[3][3], const double (&t)[3], const double* __restrict__ Tp,
-                                            double (&Tn)[12]) {
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-#pragma unroll
-    for (int b = 0; b < 3; ++b) Tn[4 * a + b] = fma(R[a][0], Tp[b], fma(R[a][1], Tp[4 + b], R[a][2] * Tp[8 + b]));
-    Tn[4 * a + 3] = fma(R[a][0], Tp[3], fma(R[a][1], Tp[7], fma(R[a][2], Tp[11], t[a])));
-  }
-}
-
 // The scale step of EST = 3, 4: the problem stops (false) when s_u is not a finite positive number or the accumulated scale
 // s_u * scale would leave [scale_min, scale_max] (a NaN fails both comparisons).
 __device__ __forceinline__ bool icp_scale_ok(double su, double scale, const IcpCriteria& crit, double& scale_new) {
@@ -740,12 +712,6 @@ __device__ __forceinline__ bool icp_update_point(const unsigned long long* __res
   return true;
 }
 
-// A pivot of the Cholesky factorisation must exceed this fraction of its own original diagonal entry.  pivot_j / A_jj is
-// the share of column j of the Jacobian that the columns before it do not explain; the fixed-point sums carry each A_jj to
-// 2^-44 relative or better (scale 2^(61 - eN - ...) against at most 2^eN terms of that magnitude bound), so a share below
-// 2^-30 is four decimal orders above the noise of the sums and far below any geometry that constrains the pose.
-constexpr double ICP_PIVOT_MIN = 0x1.0p-30;
-
 // The point-to-plane update from the 29 sums (the weighted layout has the same entries in the same places): A x = -b by an
 // unpivoted Cholesky, x = (alpha, t') about the origin o, the rotation of the quaternion (1, alpha / 2).  false: a pivot is
 // not finite or too small -- the problem stops.  NJ = 7 (plane + scale): the 37 sums, a seventh unknown sigma,
@@ -755,7 +721,7 @@ __device__ __forceinline__ bool icp_update_plane(const unsigned long long* __res
                                                  const IcpPlaneFrame& g, const double* __restrict__ Tp, double (&Tn)[12],
                                                  double scale, const IcpCriteria& crit, double& scale_new) {
   constexpr int NJJ = NJ * (NJ + 1) / 2;
-  double A[NJ][NJ], L[NJ][NJ], bv[NJ], yv[NJ], xv[NJ];
+  double A[NJ][NJ], bv[NJ], xv[NJ];
   {
     int at = 1;
 #pragma unroll
@@ -770,38 +736,7 @@ __device__ __forceinline__ bool icp_update_plane(const unsigned long long* __res
   }
 #pragma unroll
   for (int i = 0; i < NJ; ++i) bv[i] = (double)(long long)S[1 + NJJ + i] * (icp_rot_col(i) ? g.inv_rd : g.inv_td);
-  bool ok = true;
-#pragma unroll
-  for (int j = 0; j < NJ; ++j) {
-    double d = A[j][j];
-#pragma unroll
-    for (int k = 0; k < j; ++k) d = fma(-L[j][k], L[j][k], d);
-    if (!(isfinite(d) && d > ICP_PIVOT_MIN * A[j][j])) ok = false;
-    const double ljj = sqrt(d);
-    L[j][j] = ljj;
-#pragma unroll
-    for (int i = j + 1; i < NJ; ++i) {
-      double v = A[i][j];
-#pragma unroll
-      for (int k = 0; k < j; ++k) v = fma(-L[i][k], L[j][k], v);
-      L[i][j] = v / ljj;
-    }
-  }
-  if (!ok) return false;
-#pragma unroll
-  for (int i = 0; i < NJ; ++i) {
-    double v = -bv[i];
-#pragma unroll
-    for (int k = 0; k < i; ++k) v = fma(-L[i][k], yv[k], v);
-    yv[i] = v / L[i][i];
-  }
-#pragma unroll
-  for (int i = NJ - 1; i >= 0; --i) {
-    double v = yv[i];
-#pragma unroll
-    for (int k = i + 1; k < NJ; ++k) v = fma(-L[k][i], xv[k], v);
-    xv[i] = v / L[i][i];
-  }
+  if (!icp_chol_solve<NJ>(A, bv, xv)) return false;
   double R[3][3], t[3];
   icp_quat_rotation(1.0, 0.5 * xv[0], 0.5 * xv[1], 0.5 * xv[2], R);
   if constexpr (NJ == 7) {

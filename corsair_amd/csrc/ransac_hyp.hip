@@ -8,11 +8,7 @@
 
 namespace cs {
 
-// rng_u64: common.h
-__host__ __device__ static inline uint32_t rng_index(uint64_t seed, uint64_t itr, uint64_t j,
-                                                     uint32_t m) {
-  return (uint32_t)(((rng_u64(seed, itr, j) >> 32) * (uint64_t)m) >> 32);
-}
+// rng_u64, rng_index: common.h
 
 // structure-of-arrays copy of the correspondences: pk[c * total + i], c = sx,sy,sz,qx,qy,qz
 // + pair32[i] = (sx, sy, sz, qx | qy, qz, 0, 0): one aligned 32-B sector per pair for the random

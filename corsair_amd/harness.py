@@ -62,6 +62,11 @@ class Config:
     # kernel.  A query whose accumulated scale would leave icp_scale_bounds stops before that update; (0.5, 2.0) is UNTUNED
     icp_with_scaling: bool = False
     icp_scale_bounds: tuple = (0.5, 2.0)
+    # the correspondence estimator of stage 4: "ransac" (cs_ransac_batch, the reference's) or "fgr" (cs_fgr_batch, Fast Global
+    # Registration).  fgr_mu_floor is Open3D's maximum_correspondence_distance in units of the normalised frame
+    # (the clouds' radius = 1); 0.025 is Open3D's default and NOBODY HAS TUNED it here
+    registration: str = "ransac"
+    fgr_mu_floor: float = 0.025
 
     def icp_distance(self):
         return self.icp_max_dist if self.icp_max_dist > 0 else 2.0 * self.voxel_size
@@ -70,6 +75,10 @@ class Config:
         return self.icp_kernel_scale if self.icp_kernel_scale > 0 else 1.0 * self.voxel_size
 
     def check_icp(self):
+        if self.registration not in ("ransac", "fgr"):
+            raise ValueError("Config.registration must be 'ransac' or 'fgr', got %r" % (self.registration,))
+        if not (0.0 < float(self.fgr_mu_floor) < float("inf")):
+            raise ValueError("Config.fgr_mu_floor must be positive and finite, got %r" % (self.fgr_mu_floor,))
         if self.icp_estimation not in ("point", "plane"):
             raise ValueError("Config.icp_estimation must be 'point' or 'plane', got %r" % (self.icp_estimation,))
         if self.icp_kernel not in ICP_KERNEL_NAMES:
@@ -222,7 +231,8 @@ class Pipeline:
                                 c.icp_estimation, c.icp_normal_k, cads.normal, c.normal_radius(),
                                 icp_with_scaling=c.icp_with_scaling,
                                 icp_scale_bounds=tuple(c.icp_scale_bounds) if c.icp_with_scaling else None,
-                                icp_kernel=c.icp_kernel, icp_kernel_scale=c.icp_scale() if c.icp_kernel != "l2" else None)
+                                icp_kernel=c.icp_kernel, icp_kernel_scale=c.icp_scale() if c.icp_kernel != "l2" else None,
+                                registration=c.registration, fgr_mu_floor=c.fgr_mu_floor)
 
     def with_normals(self, s):
         """`s` with the normals of its origins (one cs_estimate_normals call over the whole set, or one
@@ -626,6 +636,10 @@ def build_parser():
                     help="lower bound of the scale the ICP may add, in (0, 1] (an untuned default)")
     ap.add_argument("--icp-scale-max", type=float, default=2.0,
                     help="upper bound of the scale the ICP may add, >= 1 (an untuned default)")
+    ap.add_argument("--registration", default="ransac", choices=["ransac", "fgr"],
+                    help="correspondence estimator: the reference's RANSAC, or Fast Global Registration (cs_fgr_batch)")
+    ap.add_argument("--fgr-mu-floor", type=float, default=0.025,
+                    help="floor of FGR's mu, in units of the clouds' radius (Open3D's default, untuned)")
     ap.add_argument("--in-flight", type=int, default=3, help="registration batches in flight (host threads x HIP streams)")
     ap.add_argument("--device", default="cuda", choices=["cuda"], help="there is no CPU path")
     return ap
@@ -649,7 +663,8 @@ def main(argv=None):
                  ransac_max_iter=a.ransac_max_iter, icp_max_iter=a.icp_iters, icp_max_dist=a.icp_max_dist,
                  icp_estimation=a.icp_estimation, icp_normal_k=a.icp_normal_k, icp_kernel=a.icp_kernel,
                  icp_kernel_scale=a.icp_kernel_scale, icp_normal_radius=a.icp_normal_radius,
-                 icp_with_scaling=a.icp_with_scaling, icp_scale_bounds=(a.icp_scale_min, a.icp_scale_max))
+                 icp_with_scaling=a.icp_with_scaling, icp_scale_bounds=(a.icp_scale_min, a.icp_scale_max),
+                 registration=a.registration, fgr_mu_floor=a.fgr_mu_floor)
     cfg.check_icp()
     pipe = Pipeline(sd, esd, device=a.device, config=cfg)
     cad_names, catalog = load_cloud_dir(a.catalog_dir, a.n_points, "catalog")

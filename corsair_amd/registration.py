@@ -10,6 +10,7 @@ here every stage is one batched HIP launch over all pairs / hypotheses:
   3. per-part correspondences for every cyclic / mirrored
      part assignment (K or K+4 hypotheses per pair)             cs_knn_feat (labelled)
   4. one RANSAC per hypothesis, all in one call                 cs_ransac_batch
+     (registration="fgr": Fast Global Registration instead)     cs_fgr_batch
   5. one-directional Chamfer of every estimate                  cs_chamfer_1dir
   6. keep the estimate with the smallest Chamfer (first wins)   argmin
 
@@ -17,6 +18,7 @@ torch is used for index plumbing on the device (stable sort of part labels, gath
 """
 from __future__ import annotations
 
+import inspect
 import os
 from dataclasses import dataclass
 
@@ -150,32 +152,14 @@ def part_configs(K, pos_sym):
     return cfgs
 
 
-def sym_pose_batch(baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_nn=5, max_corr=0.20, seed=0,
-                   anchor_ids=None, n_anchor=100, max_iter=100000, confidence=0.999,
-                   use_symmetry=True, force_gate=False, query_anchors=None, icp_max_iter=0, icp_max_dist=None,
-                   icp_estimation="point", icp_normal_k=16, normals1=None, icp_normal_radius=None, icp_with_scaling=False,
-                   icp_scale_bounds=None, icp_kernel="l2", icp_kernel_scale=None):
-    """baseF f32 [N0,16], xyz0 f32 [N0,3] (query voxels of all pairs, segment p = off0[p]:off0[p+1]);
-    posF/xyz1/off1 likewise for the CAD side; pos_syms: symmetry label per pair.
-    anchor_ids[p] = (counter0, counter1) seeds the anchor draw of pair p (default (2p, 2p+1)).
-    query_anchors: the query-side draws (draw_anchors(n0[p], n_anchor, anchor_ids[p][0]) for every p)
-    when the caller has already made them -- e.g. while the embedding kernels were still running; the
-    ~1 ms of host work would otherwise sit between the 5-NN and the part-cut launches.
-    icp_max_iter > 0: T_best of every pair is refined by point-to-point ICP (cs_icp_batch: source = the query's voxels,
-    target = the CAD's voxels, the direction of stage 5; correspondence distance icp_max_dist, required then) and the
-    result's T_icp / cd_icp / icp_* fields are filled; with the default 0 nothing is launched.
-    icp_estimation = "plane": the refinement is point-to-plane (cs_icp_plane_batch) on the normals of the CAD voxels,
-    normals1 f32 [N1,3] when the caller has them (a catalog's are computed once), else cs_estimate_normals over
-    icp_normal_k neighbours here; the same result fields are filled.  icp_normal_radius (None = k-NN): those normals
-    come from the at most icp_normal_k nearest rows strictly inside that radius instead (cs_estimate_normals_hybrid).
-    icp_kernel = "huber" / "cauchy" / "tukey" with icp_kernel_scale > 0 (plane estimation only): the residuals are weighted
-    by that robust kernel (cs_icp_plane_robust_batch) and icp_wfitness is filled too.
-    icp_with_scaling: either estimation also fits an isotropic scale of the query (cs_icp_scale_batch); T_icp is then a
-    similarity, icp_scale the factor, and cd_icp is cs_chamfer_1dir under that similarity (its pose chain is affine).
-    icp_scale_bounds = (min, max), None = backend.icp_batch's untuned default (0.5, 2.0).  Robust kernels with a scale are
-    out of scope and refused.  These two parameters stand BEFORE icp_kernel / icp_kernel_scale, which stay the last two: a
-    caller that passed icp_kernel by position must pass it by keyword now (such a call fails on the scale bounds, it does
-    not run with other settings)."""
+def _sym_pose_batch(estimator, baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_nn=5, max_corr=0.20, seed=0,
+                    anchor_ids=None, n_anchor=100, max_iter=100000, confidence=0.999,
+                    use_symmetry=True, force_gate=False, query_anchors=None, icp_max_iter=0, icp_max_dist=None,
+                    icp_estimation="point", icp_normal_k=16, normals1=None, icp_normal_radius=None, icp_with_scaling=False,
+                    icp_scale_bounds=None, icp_kernel="l2", icp_kernel_scale=None):
+    """The body of sym_pose_batch (below, with the documentation).  estimator = (registration, fgr_mu_floor,
+    fgr_iterations, fgr_tuple_test), already checked."""
+    registration, fgr_mu_floor, fgr_iterations, fgr_tuple_test = estimator
     if icp_with_scaling and icp_kernel != "l2":
         raise ValueError("sym_pose_batch: icp_with_scaling with a robust icp_kernel (%r) is out of scope" % (icp_kernel,))
     if icp_kernel not in B.ICP_KERNELS:
@@ -219,7 +203,8 @@ def sym_pose_batch(baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_nn=5, max_co
     prob_cfg = [None] * P
     ok = np.zeros(P, dtype=bool)
     vanilla = None
-    if use_symmetry and dev.type == "cuda" and os.environ.get("CORSAIR_SPLIT_RANSAC", "1") != "0":
+    if registration == "ransac" and use_symmetry and dev.type == "cuda" and \
+            os.environ.get("CORSAIR_SPLIT_RANSAC", "1") != "0":
         v_offs = np.concatenate([[0], np.cumsum(prob_len)]).tolist()
         for t in (v_src, v_tgt):
             t.record_stream(_helper.stream(dev))
@@ -315,7 +300,12 @@ def sym_pose_batch(baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_nn=5, max_co
         src = corr_src[0] if len(corr_src) == 1 else torch.cat(corr_src)
         tgt = corr_tgt[0] if len(corr_tgt) == 1 else torch.cat(corr_tgt)
         offs = np.concatenate([[0], np.cumsum(prob_len)]).tolist()
-        T, inl, rmse, iters = B.ransac_batch(src, tgt, offs, max_corr, 10, max_iter, confidence, seed)
+        if registration == "fgr":
+            r = B.fgr_batch(src, tgt, offs, max_corr, mu_floor=fgr_mu_floor, iteration_number=fgr_iterations,
+                            tuple_test=fgr_tuple_test, seed=seed)
+            T, inl, rmse, iters = r.T, r.inliers, r.rmse, r.iters
+        else:
+            T, inl, rmse, iters = B.ransac_batch(src, tgt, offs, max_corr, 10, max_iter, confidence, seed)
     else:
         parts = []
         if len(corr_src) > 1:
@@ -361,3 +351,42 @@ def sym_pose_batch(baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_nn=5, max_co
         res.icp_scale = r.scale
         res.cd_icp = B.chamfer_1dir(xyz0, off0, xyz1, off1, pairs, pairs, r.T32)
     return res
+
+
+def sym_pose_batch(*args, registration="ransac", fgr_mu_floor=0.025, fgr_iterations=64, fgr_tuple_test=True, **kwargs):
+    """baseF f32 [N0,16], xyz0 f32 [N0,3] (query voxels of all pairs, segment p = off0[p]:off0[p+1]);
+    posF/xyz1/off1 likewise for the CAD side; pos_syms: symmetry label per pair.
+    anchor_ids[p] = (counter0, counter1) seeds the anchor draw of pair p (default (2p, 2p+1)).
+    query_anchors: the query-side draws (draw_anchors(n0[p], n_anchor, anchor_ids[p][0]) for every p)
+    when the caller has already made them -- e.g. while the embedding kernels were still running; the
+    ~1 ms of host work would otherwise sit between the 5-NN and the part-cut launches.
+    icp_max_iter > 0: T_best of every pair is refined by point-to-point ICP (cs_icp_batch: source = the query's voxels,
+    target = the CAD's voxels, the direction of stage 5; correspondence distance icp_max_dist, required then) and the
+    result's T_icp / cd_icp / icp_* fields are filled; with the default 0 nothing is launched.
+    icp_estimation = "plane": the refinement is point-to-plane (cs_icp_plane_batch) on the normals of the CAD voxels,
+    normals1 f32 [N1,3] when the caller has them (a catalog's are computed once), else cs_estimate_normals over
+    icp_normal_k neighbours here; the same result fields are filled.  icp_normal_radius (None = k-NN): those normals
+    come from the at most icp_normal_k nearest rows strictly inside that radius instead (cs_estimate_normals_hybrid).
+    icp_kernel = "huber" / "cauchy" / "tukey" with icp_kernel_scale > 0 (plane estimation only): the residuals are weighted
+    by that robust kernel (cs_icp_plane_robust_batch) and icp_wfitness is filled too.
+    icp_with_scaling: either estimation also fits an isotropic scale of the query (cs_icp_scale_batch); T_icp is then a
+    similarity, icp_scale the factor, and cd_icp is cs_chamfer_1dir under that similarity (its pose chain is affine).
+    icp_scale_bounds = (min, max), None = backend.icp_batch's untuned default (0.5, 2.0).  Robust kernels with a scale are
+    out of scope and refused.  These two parameters stand BEFORE icp_kernel / icp_kernel_scale, which stay the last two: a
+    caller that passed icp_kernel by position must pass it by keyword now (such a call fails on the scale bounds, it does
+    not run with other settings).
+    registration = "fgr" (keyword-only, like the fgr_* arguments): stage 4 sends the vanilla and every part-configuration
+    list through ONE cs_fgr_batch call (Fast Global Registration: tuple test + graduated non-convexity, backend.fgr_batch)
+    in place of both RANSAC calls and the helper-thread split; T_all, inliers and iters (= updates applied) are filled from
+    it and stages 5 - 7 are what they are for the RANSAC.  fgr_mu_floor (untuned), fgr_iterations and fgr_tuple_test are
+    fgr_batch's mu_floor, iteration_number and tuple_test; max_iter and confidence are the RANSAC's and unused then.  With
+    the default "ransac" nothing of it is launched.  These four are accepted by keyword ONLY, behind every parameter
+    above; `inspect.signature` keeps reporting the parameters above (`__signature__` below), whose order and end existing
+    callers and tests rely on."""
+    if registration not in ("ransac", "fgr"):
+        raise ValueError("sym_pose_batch: registration must be 'ransac' or 'fgr', got %r" % (registration,))
+    return _sym_pose_batch((registration, fgr_mu_floor, fgr_iterations, fgr_tuple_test), *args, **kwargs)
+
+
+# the positional interface (everything but the keyword-only estimator options), as introspection has always shown it
+sym_pose_batch.__signature__ = inspect.Signature(list(inspect.signature(_sym_pose_batch).parameters.values())[1:])

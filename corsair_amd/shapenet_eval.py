@@ -51,6 +51,9 @@ class Config:
     max_log_scale: float = 0.0
     icp_with_scaling: bool = False
     icp_scale_bounds: tuple = (0.5, 2.0)
+    # the correspondence estimator: "ransac" or "fgr" (cs_fgr_batch); fgr_mu_floor is UNTUNED, as in harness.Config
+    registration: str = "ransac"
+    fgr_mu_floor: float = 0.025
 
     def icp_distance(self):
         return self.icp_max_dist if self.icp_max_dist > 0 else 2.0 * self.voxel_size
@@ -190,7 +193,8 @@ def evaluate(pipe, clouds, cfg=None, pairs_per_batch=16, seed=None, force_gate=F
                                cfg.icp_normal_k, None, cfg.normal_radius(), icp_with_scaling=scale_on,
                                icp_scale_bounds=tuple(cfg.icp_scale_bounds) if scale_on else None,
                                icp_kernel=cfg.icp_kernel,
-                               icp_kernel_scale=cfg.icp_scale() if cfg.icp_kernel != "l2" else None)
+                               icp_kernel_scale=cfg.icp_scale() if cfg.icp_kernel != "l2" else None,
+                               registration=cfg.registration, fgr_mu_floor=cfg.fgr_mu_floor)
         Tb, Tr = res.T_best.cpu().numpy(), res.T_ransac.cpu().numpy()
         cdb, cdr = res.cd_best.cpu().numpy(), res.cd_ransac.cpu().numpy()
         for i, (mi, pi, _, _, pose, label, s_gt) in enumerate(chunk):
@@ -329,6 +333,10 @@ def build_parser():
                     help="the ICP refinement also fits an isotropic scale (needs --icp-iters > 0, no robust kernel)")
     ap.add_argument("--icp-scale-min", type=float, default=0.5, help="lower bound of the fitted scale, in (0, 1] (untuned)")
     ap.add_argument("--icp-scale-max", type=float, default=2.0, help="upper bound of the fitted scale, >= 1 (untuned)")
+    ap.add_argument("--registration", default="ransac", choices=["ransac", "fgr"],
+                    help="correspondence estimator: the reference's RANSAC, or Fast Global Registration (cs_fgr_batch)")
+    ap.add_argument("--fgr-mu-floor", type=float, default=0.025,
+                    help="floor of FGR's mu, in units of the clouds' radius (Open3D's default, untuned)")
     ap.add_argument("--out-dir", default=".")
     ap.add_argument("--device", default="cuda", choices=["cuda"])
     return ap
@@ -359,7 +367,8 @@ def main(argv=None):
                  ransac_max_iter=a.ransac_max_iter, icp_max_iter=a.icp_iters, icp_max_dist=a.icp_max_dist,
                  icp_estimation=a.icp_estimation, icp_normal_k=a.icp_normal_k, icp_kernel=a.icp_kernel,
                  icp_kernel_scale=a.icp_kernel_scale, icp_normal_radius=a.icp_normal_radius, max_log_scale=a.max_log_scale,
-                 icp_with_scaling=a.icp_with_scaling, icp_scale_bounds=(a.icp_scale_min, a.icp_scale_max))
+                 icp_with_scaling=a.icp_with_scaling, icp_scale_bounds=(a.icp_scale_min, a.icp_scale_max),
+                 registration=a.registration, fgr_mu_floor=a.fgr_mu_floor)
     results = evaluate(pipe, clouds, cfg)
     postfix = f"shapenet-seed{a.random_seed}-{a.category}-{len(files)}-{a.n_poses_per_model}"
     os.makedirs(a.out_dir, exist_ok=True)

@@ -735,10 +735,76 @@ int cs_estimate_normals_hybrid(const float* d_xyz, const int64_t* h_off, int n_s
 void cs_normals_stats(uint64_t out[2], int reset);
 
 /* ------------------------------------------------------------------------------------------
+ * cs_fgr_batch: Fast Global Registration (Zhou, Park, Koltun, ECCV 2016) on fixed correspondence lists, the second
+ * estimator beside cs_ransac_batch.  It follows [O3D-knowledge] Open3D's registration_fgr_based_on_correspondence
+ * (FastGlobalRegistrationOption: division_factor, tuple_scale, maximum_correspondence_distance = mu_floor,
+ * iteration_number, maximum_tuple_count, tuple_test), as remembered and not checked against an installation; where the
+ * project's habits differ they hold (DESIGN 17 lists the differences).  This comment is the specification and
+ * tests/fgr_ref.py restates it bit for bit.  Every operation below is ONE IEEE f64 operation, evaluated in the order the
+ * parentheses give (sums without parentheses from left to right), unless a fused fma(a, b, c) is written; nothing is
+ * contracted.
+ *   Problems: cs_ransac_batch's layout -- d_src, d_tgt f32 [M,3], pair i = (src_i, tgt_i), problem p owns the m pairs
+ *     [h_off[p], h_off[p+1]).
+ *   Frame: lo_c / hi_c = fminf / fmaxf of coordinate c over the source rows of the problem (NaN loses), cs_c =
+ *     0.5 * ((double)lo_c + (double)hi_c); ct likewise from the target rows.  d2 of a row r of a side with midpoint c:
+ *     d. = (double)r. - c., d2 = (dx*dx + dy*dy) + dz*dz;  g = sqrt(max d2 over all rows of both sides).
+ *     q^_c = ((double)src_c - cs_c) / g,  p^_c = ((double)tgt_c - ct_c) / g.
+ *     The frame is DEGENERATE when m = 0, a lo or hi is not finite, any d2 is NaN, or g is 0 or not finite.
+ *   Tuple test (tuple_test != 0): trial t = 0, 1, ... < 100 m draws i_j = rng(seed, t, j) for j = 0, 1, 2 by
+ *     cs_ransac_batch's generator and multiply-shift (not keyed by the problem, like the RANSAC's).  For an edge (a, b):
+ *     ls = sqrt((dx*dx + dy*dy) + dz*dz) of d = q^_a - q^_b, lt likewise of p^_a - p^_b.  The trial passes iff
+ *     ls * tuple_scale < lt && lt * tuple_scale < ls for its edges (i_0,i_1), (i_1,i_2), (i_2,i_0) -- strict, so a repeated
+ *     index fails.  The working list is the pairs i_0, i_1, i_2 of each of the first max_tuple passing trials in trial order,
+ *     duplicates kept; n_tuple = trials kept.  Trials are chunked over lanes, but the list is a function of the trial order
+ *     alone.  tuple_test = 0: the working list is all m pairs in order and n_tuple = -1.  A degenerate frame has an empty
+ *     working list (n_tuple = 0 with the test on).
+ *   A problem with a degenerate frame or a working list of n < 10 pairs is answered with the IDENTITY and 0 updates.
+ *   Optimisation: T^ = identity (3x4), mu = 1.  For itr = 0 .. iteration_number - 1, per working pair (from its ORIGINAL
+ *     q^: the pose-chain rule of cs_icp_batch, written with single operations here):
+ *       q_c = ((T^_c0 * q^_x + T^_c1 * q^_y) + T^_c2 * q^_z) + T^_c3;   e = q - p^;   r2 = (e_x*e_x + e_y*e_y) + e_z*e_z;
+ *       w = (mu / (r2 + mu))^2 (one division, one product);   wq_c = w * q_c;
+ *       x = q x e:  x_x = q_y*e_z - q_z*e_y,  x_y = q_z*e_x - q_x*e_z,  x_z = q_x*e_y - q_y*e_x.
+ *     16 signed 64-bit integer sums of I(v * 2^s), I = clamp to +-2^(61 - eN) (NaN to the lower clamp), then truncation
+ *     toward zero; eN the smallest integer with n <= 2^eN, b = 61 - eN:
+ *       [0] w, s = b;  [1..3] wq_c, s = b - 2;  [4..9] wq_a * q_b for (a,b) = xx, xy, xz, yy, yz, zz, s = b - 4;
+ *       [10..12] w * e_c, s = b - 3;  [13..15] w * x_c, s = b - 5.
+ *     The bounds behind the exponents (|q| <= 4) are derived in corsair_amd/csrc/fgr.hip and DESIGN 17; the clamp keeps the
+ *     sums defined for any T^.  Each sum is converted back as (double)sum * 2^-s.
+ *     Normal equations of r = q + omega x q + t - p^ in x = (omega, t), J = [-[q]x | I]:  A x = -b with
+ *       A = [[Sxx' , [Swq]x], [. , Sw I]],  Sxx' = (Syy+Szz, -Sxy, -Sxz; ., Sxx+Szz, -Syz; ., ., Sxx+Syy) from the six
+ *       second-moment sums, [v]x = (0, -v_z, v_y; v_z, 0, -v_x; -v_y, v_x, 0),  b = (sums 13..15, sums 10..12);
+ *     solved by cs_icp_plane_batch's unpivoted Cholesky with its pivot rule (d > 2^-30 A_jj, finite).  R of the quaternion
+ *     (1, 0.5 x_0, 0.5 x_1, 0.5 x_2) normalised by division, t = (x_3, x_4, x_5), T^ <- U T^ by cs_icp_batch's chain.  A failed
+ *     pivot or a non-finite new T^ stops the problem, which keeps the T^ it had.  After the update of iteration itr:
+ *     if itr % 4 == 0 && mu > mu_floor then mu <- mu / division_factor.
+ *   Result (a problem that was not answered with the identity): R = R^,
+ *       t_a = (g * t^_a + ct_a) - ((R_a0 * cs_0 + R_a1 * cs_1) + R_a2 * cs_2);  last row (0, 0, 0, 1).
+ *   Outputs: d_T f32 [n_prob,16] = the f64 result cast once; d_T64 f64 [n_prob,16], optional; d_inliers int32 and d_rmse
+ *     f64 [n_prob] as cs_ransac_batch evaluates a hypothesis, of the returned f64 transform over ALL m pairs: d2 by its
+ *     fma chain, inlier iff d2 < max_corr * max_corr, rmse = sqrt((sum of (uint64)(d2 * 2^k) * 2^-k) / inliers), 0 without an
+ *     inlier, k = 61 - eM - ex with m <= 2^eM and max_corr^2 = f 2^ex (frexp; ex at least -900, 1024 when not finite);
+ *     d_iters int32 [n_prob] = updates applied; d_ntuple int32 [n_prob].
+ *   Independence: a problem's result depends on that problem alone -- not on its batch neighbours, the launch shape or
+ *     the run; with the tuple test off it does not depend on the order of its pairs either.
+ *   Empty problems are legal (identity, 0 inliers), so is n_prob = 0.
+ *   Refused (CS_ERR_INVALID): NULL table or outputs (d_T64 may be NULL), a negative segment, max_corr or mu_floor not
+ *     positive and finite, division_factor <= 1, tuple_scale outside (0, 1), max_tuple < 1; (CS_ERR_UNSUPPORTED):
+ *     iteration_number outside [0, 1000], max_tuple above 65536, a problem of 2^31 pairs or more.
+ *   Stream behaviour: one launch on `stream`, one persistent workgroup per problem, no host wait; the table of normalised
+ *     pairs (f64, 48 bytes per pair of the call) and, with the test on, the working lists (48 bytes x 3 max_tuple per
+ *     problem) come from the calling thread's pool.  No float atomics.
+ * Profile family "fgr".
+ * ---------------------------------------------------------------------------------------- */
+int cs_fgr_batch(const float* d_src, const float* d_tgt, const int64_t* h_off, int n_prob, double max_corr,
+                 double mu_floor, double division_factor, int iteration_number, int tuple_test, double tuple_scale,
+                 int max_tuple, uint64_t seed, float* d_T, double* d_T64, int32_t* d_inliers, double* d_rmse,
+                 int32_t* d_iters, int32_t* d_ntuple, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Profiling hooks for bench.py: when enabled the library brackets the launches of each named
  * kernel family with hipEvents on the launch stream and accumulates the elapsed time.
  * names: "conv", "ransac_eval", "ransac_pre", "ransac_hyp", "knn", "chamfer", "topk", "symcut",
- * "kmap", "loss", "hardneg", "icp", "normals".
+ * "kmap", "loss", "hardneg", "icp", "normals", "fgr".
  * ---------------------------------------------------------------------------------------- */
 void cs_prof_enable(int on);
 void cs_prof_reset(void);
