@@ -75,6 +75,7 @@ def _declare(lib):
         "cs_symcut_labels": (c_int, [vp, POINTER(c_int64), c_int, POINTER(c_int32), vp, vp, vp]),
         "cs_partition_by_label": (c_int, [vp, vp, c_int, vp, vp]),
         "cs_cfg_bad": (c_int, [vp, c_int, vp, c_int, vp, vp]),
+        "cs_rows_nonfinite": (c_int, [vp, c_int, vp, c_int, vp, vp]),
         "cs_corr_assemble": (c_int, [vp, vp, vp, vp, c_int, vp, c_int, c_int64, vp, vp, vp]),
         "cs_radius_pairs": (c_int, [vp, POINTER(c_int64), vp, POINTER(c_int64), POINTER(c_int32), POINTER(c_int32),
                                     c_int, c_double, c_int, vp, vp, POINTER(vp)]),

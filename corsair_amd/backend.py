@@ -678,6 +678,14 @@ def cfg_bad(nn, d_first, n_cfg):
     return bad
 
 
+def rows_nonfinite(x, d_first, n_seg):
+    """int32 [n_seg]: 1 where rows [first[j], first[j+1]) of x (f32 [n, dim]) hold a NaN or infinite element."""
+    x = _dev(x, torch.float32, "rows").contiguous()
+    bad = torch.empty(n_seg, dtype=torch.int32, device=x.device)
+    check(_lib.load().cs_rows_nonfinite(ptr(x), x.shape[1], ptr(d_first), n_seg, ptr(bad), stream_ptr()))
+    return bad
+
+
 def corr_assemble(xyz0, xyz1, rows, nn, desc, total, max_len):
     """Correspondence lists of the configurations desc (host int64 [n_cfg, 5] = q_first, n_first, t_first, len,
     out_first): returns (src f32 [total * k, 3], tgt f32 [total * k, 3])."""

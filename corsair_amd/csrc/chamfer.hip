@@ -12,6 +12,11 @@
 //     candidates of a source.
 //   * CS_CHAMFER_MFMA=0: k_chamfer, exhaustive on the VALU -- what the tests hold the other two against.
 // k_chamfer_finish turns the tiles' partial results into the mean (Chamfer) or maximum (Hausdorff) of each problem.
+// Non-finite rows (include/corsair_hip.h): a target at NaN or +inf distance is never the nearest -- every search keeps its
+// best with a strict `<` from +inf, the tile minima are fminf / v_min3 (a NaN operand loses), fmin drops a NaN canonical
+// distance.  A source without a target at finite distance keeps +inf, and the problem's sum or maximum is +inf.  The f16
+// kernel cannot vouch for a source or pose that is not finite (in_range), nor for a segment with an infinite or huge row
+// (tmax; a NaN row does not enter it): those workgroups go to k_chamfer_mfma.
 #include <algorithm>
 
 

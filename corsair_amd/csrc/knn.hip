@@ -11,7 +11,11 @@
 //     k_knn_feat<16> (flagged tiles only).  CS_KNN_TWOPASS=0 drops the threshold pass; CS_KNN_STATS=1 counts the
 //     recomputed queries (cs_knn_shortlist_stats; synchronises).
 //   * CS_KNN_MFMA=64: k_knn_mfma16 shortlists on the f64 matrix pipe, k_knn_rescore16 ranks the shortlist with the
-//     canonical chain.
+//     canonical chain; queries with |q|^2 >= KNF_RANGE (or not finite) are recomputed by k_knn_feat<16>.
+// Non-finite rows (include/corsair_hip.h): a candidate whose canonical distance is NaN or +inf is never a neighbour.  Every
+// insertion test is a strict `<` against a list that starts at +inf, the tile minima are fminf / v_min3 (a NaN operand
+// loses), and the budgets take their maxima with fmaxf (a NaN row does not enter seg_t2max; an infinite or huge one
+// makes it +inf, which sends the whole segment to the exhaustive kernel).
 //   * CS_KNN_MFMA=0, and every other shape (3-d, 32-d, k = 7 / 8): k_knn_feat<DIM>, exhaustive on the VALU -- the fallback
 //     of the f16 path and what the tests hold the other two against.
 // Labelled searches (part-to-part correspondences): both shortlist paths visit the targets of a segment in label order
@@ -410,14 +414,26 @@ __global__ __launch_bounds__(256) void k_knn_mfma16(const KnnWork* __restrict__ 
 // One thread per query: canonical distances of its 4 * KNM_KK candidates, k best by (distance, row).
 __global__ void k_knn_rescore16(const KnnWork* __restrict__ work, const float* __restrict__ qf,
                                 const float* __restrict__ tf, const int32_t* __restrict__ cand_i,
-                                int k, int32_t* __restrict__ out_idx, double* __restrict__ out_dist) {
+                                int k, int32_t* __restrict__ out_idx, double* __restrict__ out_dist,
+                                int32_t* __restrict__ qflag, int32_t* __restrict__ tile_flag) {
   const KnnWork wk = work[blockIdx.x];
   const int qloc = threadIdx.x;
   if (qloc >= wk.qn) return;
   const int64_t qrow = wk.q0 + qloc;
-  double q[16];
+  double q[16], qn2 = 0.0;
 #pragma unroll
-  for (int c = 0; c < 16; ++c) q[c] = (double)qf[qrow * 16 + c];
+  for (int c = 0; c < 16; ++c) {
+    q[c] = (double)qf[qrow * 16 + c];
+    qn2 = fma(q[c], q[c], qn2);
+  }
+  // Range of the expansion.  |t|^2 - 2 q.t carries a rounding of ~2^-52 (|q| + |t|)^2: a query far outside the unit
+  // range (1e30 in one element: every canonical distance rounds to the same 1e60 and the (distance, row) rule decides,
+  // while the expansion still ranks by -2 q.t) or a non-finite one (every value NaN: an empty shortlist) is not
+  // shortlisted at all but recomputed by k_knn_feat<16>, like the queries the f16 path cannot verify.  A target row
+  // only affects its own value: a NaN / inf row is never shortlisted, a huge finite one ranks last, as it should.
+  const bool bad = !(qn2 < KNF_RANGE);
+  qflag[wk.o0 + qloc] = bad ? 1 : 0;
+  if (bad) atomicOr(&tile_flag[blockIdx.x], 1);
   double bd[KNN_MAXK];
   int32_t bi[KNN_MAXK];
 #pragma unroll
@@ -1005,9 +1021,12 @@ static int knn_f64(const KnnCall& c) {
              "cs_knn_feat: too many target rows / segments");
   PoolBuf<double> qnorm((size_t)(nq_rows ? nq_rows : 1)), tnorm((size_t)(nt_rows ? nt_rows : 1));
   PoolBuf<int32_t> cand((size_t)(out_row ? out_row : 1) * 4 * KNM_KK);
+  PoolBuf<int32_t> qflag((size_t)(out_row ? out_row : 1)), tile_flag(c.n_work);
   PoolBuf<int32_t> torder, lab_start;
   PoolBuf<int64_t> dtoff;
-  CS_REQUIRE(qnorm.p && tnorm.p && cand.p, CS_ERR_HIP, "cs_knn_feat: scratch allocation failed");
+  CS_REQUIRE(qnorm.p && tnorm.p && cand.p && qflag.p && tile_flag.p, CS_ERR_HIP,
+             "cs_knn_feat: scratch allocation failed");
+  CS_HIP_CHECK(hipMemsetAsync(tile_flag.p, 0, sizeof(int32_t) * c.n_work, s));
   if (nq_rows) row_norms(c.d_qf, nq_rows, 16, qnorm.p, s);
   if (nt_rows) row_norms(c.d_tf, nt_rows, 16, tnorm.p, s);
   if (c.d_tlabel && nt_rows) {
@@ -1021,7 +1040,10 @@ static int knn_f64(const KnnCall& c) {
                      c.d_qlabel, c.d_tlabel, c.d_perm, c.d_tlabel ? torder.p : nullptr,
                      c.d_tlabel ? lab_start.p : nullptr, cand.p);
   hipLaunchKernelGGL(k_knn_rescore16, dim3(c.n_work), dim3(KNM_QT), 0, s, c.d_work, c.d_qf, c.d_tf, cand.p, c.k,
-                     c.d_idx, c.d_dist);
+                     c.d_idx, c.d_dist, qflag.p, tile_flag.p);
+  // exhaustive recomputation of the queries outside the expansion's range (normally none)
+  hipLaunchKernelGGL((k_knn_feat<16>), dim3(c.n_work), dim3(256), 0, s, c.d_work, c.d_qf, c.d_tf, c.k, c.d_qlabel,
+                     c.d_tlabel, c.d_perm, c.d_idx, c.d_dist, tile_flag.p, qflag.p);
   CS_LAUNCH_CHECK();
   return CS_OK;
 }

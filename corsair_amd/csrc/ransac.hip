@@ -7,6 +7,10 @@
 // problem is reproducible anywhere.  Iterations are processed in rounds of growing chunks: [0, 64) (CS_RANSAC_FIRST),
 // [64, 512), then doubling -- [512, 1024), [1024, 2048), ... -- up to 16 384 per round.  The first chunk is counted
 // exactly (there is no best count to prune against yet); every later one goes through the f16 prefilter.
+// Non-finite pairs (include/corsair_hip.h): a pair with a NaN or infinite coordinate is never an inlier (`d2 < thr2` is
+// false in every exact kernel) and puts its problem's largest point norm out of the f16 range, so that problem bypasses
+// the prefilter (ransac_prefilter.hip: smax) and every one of its hypotheses is counted exactly; a hypothesis fitted to
+// such a pair has no inliers, and k_ransac_scan1 takes a best only from a count above zero.
 // The kernels live in four units that share ransac.h (state, constants, launch functions): this one holds the sequential
 // replay (k_ransac_scan1, k_ransac_scan2, k_ransac_finish) and the host driver.  A round:
 //   k_ransac_hyp        (ransac_hyp.hip) one lane per hypothesis: sample ransac_n pairs (packed 32-B rows), closed-form

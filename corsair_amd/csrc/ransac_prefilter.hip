@@ -102,7 +102,10 @@ __device__ __forceinline__ float pf_pair_row(float s0, float s1, float s2, float
   b[7] = qy * sx; b[8] = qy * sy; b[9] = qy * sz;
   b[10] = qz * sx; b[11] = qz * sy; b[12] = qz * sz;
   b[13] = qx; b[14] = qy; b[15] = qz;
-  return 1.0000002f * (float)sqrt(fmax(ss, qq));
+  // fmax drops a NaN operand: a pair with a NaN on ONE side would pass for the other side's norm, its NaN row would enter
+  // the image, and one NaN result ruins the add-based sign counter of k_ransac_prefilter<1, true> for every pair after it.
+  // b_0 = ss + qq is NaN as soon as either side is.
+  return 1.0000002f * (float)sqrt(b[0] == b[0] ? fmax(ss, qq) : b[0]);
 }
 
 // pair side: 80-B rows [bh(0..15) | bl(0..15) | 8 x 0] in exactly the layout the prefilter keeps in LDS

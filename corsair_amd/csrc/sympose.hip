@@ -79,9 +79,12 @@ __global__ __launch_bounds__(256) void k_corr_assemble(const float* __restrict__
     const int64_t i = e / k;
     const int nb = (int)(e - i * k);
     const int64_t q = rows ? rows[d.q_first + i] : d.q_first + i;
-    // a missing neighbour (-1: fewer than k targets) never becomes an address: the callers reject such
-    // configurations (registration.py raises for the vanilla list, cs_cfg_bad drops part configurations); should
-    // one get here anyway it reads the cloud's first row instead of the bytes in front of the buffer
+    // a missing neighbour (-1: fewer than k targets at finite distance -- a short CAD cloud or part, a query row
+    // with a non-finite feature, too few finite CAD rows) never becomes an address.  The callers reject such lists
+    // only AFTER this launch, in stream order with their next download (registration.py: IndexError for a short CAD
+    // cloud before any launch, ValueError for non-finite descriptors from cs_cfg_bad over the vanilla list,
+    // cs_cfg_bad drops part configurations), so a -1 does get here: it reads the cloud's first row instead of the
+    // bytes in front of the buffer, and the pairs made from it are never returned
     const int32_t nbv = nn[(d.n_first + i) * k + nb];
     const int64_t t = d.t_first + (nbv < 0 ? 0 : nbv);
     const int64_t o = (d.out_first * k + e) * 3;
@@ -95,7 +98,8 @@ __global__ __launch_bounds__(256) void k_corr_assemble(const float* __restrict__
 }
 
 // bad[j] = 1 when any neighbour entry of rows [first[j], first[j+1]) is negative (a CAD part with fewer than
-// k voxels: the reference cannot build that configuration)
+// k voxels: the reference cannot build that configuration; over the vanilla list of a pair whose CAD cloud has k
+// voxels or more: a query descriptor row that is not finite, or fewer than k finite CAD rows)
 __global__ __launch_bounds__(256) void k_cfg_bad(const int32_t* __restrict__ nn, int k, const int64_t* __restrict__ first,
                                                  int32_t* __restrict__ bad) {
   const int j = blockIdx.y;
@@ -107,6 +111,18 @@ __global__ __launch_bounds__(256) void k_cfg_bad(const int32_t* __restrict__ nn,
 __global__ void k_zero_i32(int32_t* p, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = 0;
+}
+
+// bad[j] = 1 when an element of rows [first[j], first[j+1]) of x (dim floats per row) is NaN or infinite (a CAD
+// descriptor row that is not finite is no neighbour of any query and leaves no -1 behind: cs_cfg_bad cannot see it)
+__global__ __launch_bounds__(256) void k_rows_nonfinite(const float* __restrict__ x, int dim,
+                                                        const int64_t* __restrict__ first, int32_t* __restrict__ bad) {
+  const int j = blockIdx.y;
+  const int64_t a = first[j] * dim, b = first[j + 1] * dim;
+  int any = 0;
+  for (int64_t e = a + (int64_t)blockIdx.x * 256 + threadIdx.x; e < b; e += (int64_t)gridDim.x * 256)
+    any |= !(fabsf(x[e]) < INFINITY);
+  if (__any(any) && (threadIdx.x & 63) == 0) atomicOr(&bad[j], 1);
 }
 
 }  // namespace cs
@@ -145,6 +161,17 @@ int cs_cfg_bad(const int32_t* d_nn, int k, const int64_t* d_first, int n_cfg, in
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(k_zero_i32, dim3((unsigned)ceil_div(n_cfg, 256)), dim3(256), 0, s, d_bad, n_cfg);
   hipLaunchKernelGGL(k_cfg_bad, dim3(16, (unsigned)n_cfg), dim3(256), 0, s, d_nn, k, d_first, d_bad);
+  CS_LAUNCH_CHECK();
+  return CS_OK;
+}
+
+int cs_rows_nonfinite(const float* d_x, int dim, const int64_t* d_first, int n_seg, int32_t* d_bad, void* stream) {
+  CS_REQUIRE(dim >= 1 && n_seg >= 0, CS_ERR_INVALID, "cs_rows_nonfinite: bad argument");
+  if (n_seg == 0) return CS_OK;
+  CS_REQUIRE(d_x && d_first && d_bad, CS_ERR_INVALID, "cs_rows_nonfinite: NULL tensor");
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_zero_i32, dim3((unsigned)ceil_div(n_seg, 256)), dim3(256), 0, s, d_bad, n_seg);
+  hipLaunchKernelGGL(k_rows_nonfinite, dim3(16, (unsigned)n_seg), dim3(256), 0, s, d_x, dim, d_first, d_bad);
   CS_LAUNCH_CHECK();
   return CS_OK;
 }

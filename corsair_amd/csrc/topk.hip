@@ -10,6 +10,11 @@
 //   * everything else: k_dist_matrix + k_row_topk, the exact slab path -- what the tests hold the other two against.
 // CS_TOPK_MFMA forces a path whatever the size ("0" slab, "1" / "64" f64 shortlist, "16" f16 shortlist where the shape
 // allows); CS_TOPK_XCD=0 turns off the dealing of the f16 shortlist's work items over the XCDs.
+// Non-finite rows (include/corsair_hip.h): a catalog row at NaN or +inf distance is never a neighbour, on any path -- the
+// shortlists never admit it (`dist < bd[..]` is false, fminf drops a NaN), the slab path leaves it a placeholder when it
+// loads the distance (k_row_topk), and a list that runs out of rows ends in (-1, +inf).  The f16 verification hands a
+// query or a catalog outside its range (|q|^2 >= 1e8, max |x|^2 >= 4e8, not finite; a NaN row does not enter the
+// maximum) to the f64 shortlist.
 // k_row_norms lives here; knn.hip reaches it through row_norms().
 #include <algorithm>
 
@@ -99,8 +104,13 @@ __global__ __launch_bounds__(256) void k_row_topk(const double* __restrict__ D2,
         dv = carry_d[qi * k + i];
         iv = carry_i[qi * k + i];
       } else if (i - k < cnt) {
-        dv = (unsigned long long)__double_as_longlong(D2[qi * x_count + base + (i - k)]);
-        iv = (int)(x_begin + base + (i - k));
+        // a NaN or +inf distance is never a neighbour: the row stays a placeholder, as on the shortlist paths (whose
+        // `dist < bd[..]` tests are false for it) -- with its real index an infinite row sorted before the placeholders
+        const double d2 = D2[qi * x_count + base + (i - k)];
+        if (d2 < INFINITY) {
+          dv = (unsigned long long)__double_as_longlong(d2);
+          iv = (int)(x_begin + base + (i - k));
+        }
       }
       sd[i] = dv;
       si[i] = iv;
@@ -339,8 +349,11 @@ __global__ __launch_bounds__(256) void k_topk_rescore(const float* __restrict__ 
       }
     }
     if (i < TKM_MERGE_CAP) {
-      sd[i] = row != 0x7fffffff ? (unsigned long long)__double_as_longlong(acc) : INF_BITS;
-      si[i] = row;
+      // (a shortlisted row has a finite ranking value, hence finite elements; the test keeps the rule "NaN / +inf is
+      // never a neighbour" in this kernel's own terms)
+      const bool have = row != 0x7fffffff && acc < INFINITY;
+      sd[i] = have ? (unsigned long long)__double_as_longlong(acc) : INF_BITS;
+      si[i] = have ? row : 0x7fffffff;
     }
   }
   __syncthreads();

@@ -152,6 +152,15 @@ def part_configs(K, pos_sym):
     return cfgs
 
 
+def _refuse_nonfinite(bad_query, bad_cad):
+    """ValueError for the first pair whose descriptors hold a NaN or an infinite value (flags per pair, see step 1)."""
+    for side, bad, said in (("CAD", bad_cad, "data must be finite"), ("query", bad_query, "'x' must be finite")):
+        hit = np.flatnonzero(np.asarray(bad))
+        if hit.size:
+            raise ValueError("sym_pose_batch: the %s descriptors of pair %d hold a NaN or an infinite value (the "
+                             "reference's KD-tree refuses them: %s)" % (side, int(hit[0]), said))
+
+
 def _sym_pose_batch(estimator, baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_nn=5, max_corr=0.20, seed=0,
                     anchor_ids=None, n_anchor=100, max_iter=100000, confidence=0.999,
                     use_symmetry=True, force_gate=False, query_anchors=None, icp_max_iter=0, icp_max_dist=None,
@@ -186,12 +195,25 @@ def _sym_pose_batch(estimator, baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_
     # ---- 1. vanilla correspondences (find_kcorr, utils/eval_pose.py:48-79) -----------------
     # A CAD cloud with fewer than k voxels has no k-th neighbour: SciPy's KD-tree returns the out-of-range index n
     # there and the reference's fancy indexing raises IndexError (utils/eval_pose.py:66-72).  Same here, before any
-    # launch: the neighbour lists would hold -1 (k_corr_assemble must never read through one).
+    # launch.  (This excludes the -1 entries of SHORT CAD clouds only; those of non-finite descriptors are found on the
+    # device, below, and k_corr_assemble reads the cloud's row 0 through any that is left.)
     short = [p for p in range(P) if n0[p] > 0 and n1[p] < k]
     if short:
         raise IndexError("sym_pose_batch: CAD cloud of pair %d has %d voxels, fewer than k_nn = %d (the reference's "
                          "find_kcorr fails on such a pair too)" % (short[0], n1[short[0]], k))
     nn = B.knn_feat(baseF, off0, posF, off1, k)                     # [N0, k] local CAD rows
+    # Descriptors that are not finite (row_l2_normalize at eps = 0 turns a zero row into NaN): SciPy's KD-tree refuses
+    # them -- "data must be finite" when the CAD tree is built, "'x' must be finite" on the query -- and so does this
+    # function, with ValueError.  Two flags per pair, made on the device behind the search: a query row with a
+    # non-finite element has -1 in its whole list (n1 >= k is known), which is cs_cfg_bad over the vanilla list with
+    # one range per pair; a CAD row leaves no -1, so cs_rows_nonfinite looks at posF itself.  They come to the host
+    # with a download the function waits for anyway (the part-cut statistics, else the Chamfer distances of stage
+    # 6): no wait of their own.  Until then the lists go on as they are -- a -1 reads as the CAD cloud's row 0 --
+    # and nothing made from them is returned.
+    nonfinite = None
+    if P:
+        pair_rows = torch.from_numpy(np.asarray(off0 + off1, dtype=np.int64)).to(dev, non_blocking=True)
+        nonfinite = (B.cfg_bad(nn, pair_rows[:P + 1], P), B.rows_nonfinite(posF, pair_rows[P + 1:], P))
     # correspondence lists straight from the neighbour lists (one launch; rounds 1-2 built index tensors with
     # repeat_interleave / arange / gathers): pair p = query rows off0[p]:off0[p+1] against the CAD cloud at off1[p]
     desc_v = np.asarray([[off0[p], off0[p], off1[p], n0[p], off0[p]] for p in range(P)], dtype=np.int64).reshape(P, 5)
@@ -233,7 +255,12 @@ def _sym_pose_batch(estimator, baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_
                 off_all = off0 + [off0[-1] + o for o in off1[1:]]
                 c, cnt, mcd, mer = B.symcut_fit(torch.cat([baseF, posF]), torch.cat([xyz0, xyz1]), off_all, a_all,
                                                 Ks + Ks, 50, 10, 300)
-                c, cnt, mcd, mer = to_host(c, cnt, mcd, mer)
+                if nonfinite is not None:
+                    c, cnt, mcd, mer, bad_q, bad_c = to_host(c, cnt, mcd, mer, *nonfinite)
+                    nonfinite = None
+                    _refuse_nonfinite(bad_q, bad_c)
+                else:
+                    c, cnt, mcd, mer = to_host(c, cnt, mcd, mer)
                 c0, cnt0, mcd0, mer0 = c[:P], cnt[:P], mcd[:P], mer[:P]
                 c1, cnt1, mcd1, mer1 = c[P:], cnt[P:], mcd[P:], mer[P:]
                 gate = GATE_ANY if force_gate else GATE_REFERENCE
@@ -321,7 +348,11 @@ def _sym_pose_batch(estimator, baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_
     cd = B.chamfer_1dir(xyz0, off0, xyz1, off1, prob_pair, prob_pair, T)
 
     # ---- 6. best hypothesis per pair: first minimum, vanilla first (utils/symmetry.py:322-324) ----
-    cd_h = to_host(cd)[0]
+    if nonfinite is not None:
+        cd_h, bad_q, bad_c = to_host(cd, *nonfinite)   # (every launch above has finished, the helper's RANSAC included)
+        _refuse_nonfinite(bad_q, bad_c)
+    else:
+        cd_h = to_host(cd)[0]
     pair_h = np.asarray(prob_pair)
     best = np.arange(P)
     for j in range(P, len(pair_h)):
@@ -356,6 +387,9 @@ def _sym_pose_batch(estimator, baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_
 def sym_pose_batch(*args, registration="ransac", fgr_mu_floor=0.025, fgr_iterations=64, fgr_tuple_test=True, **kwargs):
     """baseF f32 [N0,16], xyz0 f32 [N0,3] (query voxels of all pairs, segment p = off0[p]:off0[p+1]);
     posF/xyz1/off1 likewise for the CAD side; pos_syms: symmetry label per pair.
+    Refused like the reference: IndexError for a CAD cloud with fewer than k_nn voxels, ValueError (naming the pair and the
+    side, query or CAD) for descriptors with a NaN or infinite value -- raised before the function returns, once every
+    launch it made has finished.
     anchor_ids[p] = (counter0, counter1) seeds the anchor draw of pair p (default (2p, 2p+1)).
     query_anchors: the query-side draws (draw_anchors(n0[p], n_anchor, anchor_ids[p][0]) for every p)
     when the caller has already made them -- e.g. while the embedding kernels were still running; the

@@ -165,6 +165,9 @@ int cs_instance_norm(int64_t n, int c, const float* d_in, int ld_in, const int32
  * the catalog side, CADLib.py:106-121).  d_xyz f32 [n,3]; h_offsets int64 [n_seg+1] (host); d_keep_idx int64 [n] (capacity n, indices
  * into the concatenated cloud); d_grid int32 [n,4] (batch, x, y, z) of kept rows;
  * h_out_offsets int64 [n_seg+1] (host) receives the kept segment boundaries.
+ * Non-finite and far coordinates: a coordinate that is NaN or infinite, or whose grid index is outside
+ * [-32767, 32767], makes the call return CS_ERR_RANGE (cs_last_error names cs_voxelize); the outputs are
+ * unspecified then, nothing faults, and the next call on the thread is unaffected.  (cs_voxelize_f64 alike.)
  * ---------------------------------------------------------------------------------------- */
 int cs_voxelize(const float* d_xyz, const int64_t* h_offsets, int n_seg, double voxel_size,
                 int64_t* d_keep_idx, int32_t* d_grid, int64_t* h_out_offsets, void* stream);
@@ -183,6 +186,12 @@ int cs_voxelize_f64(const double* d_xyz, const int64_t* h_offsets, int n_seg, do
  * broken by smaller catalog index.  Distances are evaluated in f64 exactly as
  * sum_c (double(q_c) - double(x_c))^2 (c ascending, fma chain); d_dist receives sqrt of it.
  * d_q f32 [nq,d], d_x f32 [nx,d]; d_idx int64 [nq,k]; d_dist f64 [nq,k] (may be NULL).
+ * Non-finite rows (cs_l2_topk, cs_l2_topk_sq, cs_l2_topk_catalog, on every path): a catalog row whose canonical
+ * squared distance to the query is NaN or +inf is never a neighbour -- the lists are those of the same call with
+ * such rows taken out of the catalog, indices mapped back.  When fewer than k rows remain the list ends in
+ * (-1, +inf) entries (cs_l2_topk_sq reports +inf too); a query row with a non-finite element gets k of them.
+ * These are the only cases in which -1 appears in d_idx.  A non-finite row changes nothing outside itself: every
+ * other query's list is what it is without the row, bit for bit.  Finite rows of any magnitude are ordinary rows.
  * ---------------------------------------------------------------------------------------- */
 int cs_l2_topk(const float* d_q, int64_t nq, const float* d_x, int64_t nx, int d, int k,
                int64_t* d_idx, double* d_dist, void* stream);
@@ -216,6 +225,11 @@ void cs_topk_catalog_free(cs_topk_catalog* catalog);
  * Output rows are problem-major (all rows of problem 0, then problem 1, ...):
  * d_idx int32 [sum_p nq_p, k] = target row index LOCAL to the target segment, -1 if fewer than k
  * candidates; d_dist f64 same shape, optional (Euclidean distance).
+ * Non-finite rows (all three paths, labelled or not): a candidate whose canonical f64 squared distance is NaN or
+ * +inf is never a neighbour -- the results equal those of the same call with the non-finite target rows removed,
+ * indices mapped back; the (-1, +inf) padding applies when fewer than k candidates at finite distance remain, and a
+ * query row with a non-finite element gets k times (-1, +inf).  A non-finite row changes nothing outside itself:
+ * every other query row, segment and problem has the result it has without it, bit for bit.
  * ---------------------------------------------------------------------------------------- */
 int cs_knn_feat(const float* d_qf, const int64_t* h_qoff, const float* d_tf,
                 const int64_t* h_toff, const int32_t* h_qseg, const int32_t* h_tseg, int n_prob,
@@ -235,6 +249,10 @@ void cs_knn_shortlist_stats(uint64_t out[2], int reset);
  * 4x4 row-major matrix d_T[p] (f64 arithmetic), finds for every source point the Euclidean
  * distance to the nearest target point, writes the mean to d_out[p] (f64).
  * Source / target segments are selected per problem by index into the offset tables.
+ * Non-finite rows (cs_chamfer_1dir and cs_hausdorff_1dir, all three paths): a target row at NaN or +inf distance
+ * is never the nearest; a source row with no target at finite distance (a non-finite source row, a non-finite
+ * entry of d_T[p], no finite target row) contributes +inf, so d_out[p] = +inf.  NaN stays
+ * the result of an empty SOURCE segment alone.  Problems without a non-finite value are unaffected, bit for bit.
  * ---------------------------------------------------------------------------------------- */
 /* Diagnostics of the f16 matrix-core ranking inside cs_chamfer_1dir / cs_hausdorff_1dir (default path): {256-source tiles
  * answered, of those recomputed by the f64 matrix-pipe kernel because a source was within the approximation's error budget
@@ -268,6 +286,11 @@ int cs_hausdorff_1dir(const float* d_src, const int64_t* h_soff, const float* d_
  * d_T f32 [n_prob,16] row-major 4x4 = the best f64 transform cast once at the end, where the reference
  * casts it (utils/symmetry.py:274) (identity if no hypothesis had an inlier);
  * d_inliers int32 [n_prob]; d_rmse f64 [n_prob]; d_iters int32 [n_prob] = iterations consumed.
+ * Non-finite pairs: a pair with a NaN or infinite coordinate is never an inlier (its squared distance is not
+ * below max_corr^2); it still counts in M and can be sampled.  A hypothesis whose fit is not finite has no inliers
+ * and is never the best.  A problem with no finite pair returns the identity, 0 inliers and rmse 0.  With the
+ * prefilter on or off the results are the same, and a problem without a non-finite value has the result it has
+ * in a batch without the others, bit for bit.
  * ---------------------------------------------------------------------------------------- */
 int cs_ransac_batch(const float* d_src, const float* d_tgt, const int64_t* h_off, int n_prob,
                     double max_corr, int ransac_n, int max_iter, double confidence, uint64_t seed,
@@ -315,13 +338,20 @@ int cs_symcut_labels(const float* d_xyz, const int64_t* h_off, int n_cloud, cons
  *     order inside a part).
  *   cs_cfg_bad: d_nn int32 [.., k], d_first int64 [n_cfg+1] (DEVICE, row ranges) -> d_bad int32 [n_cfg]: 1 when a
  *     range holds a negative neighbour (a CAD part with fewer than k voxels; the reference dies there, this
- *     build drops the configuration, DESIGN "Deliberate differences").
+ *     build drops the configuration, DESIGN "Deliberate differences").  Over the vanilla list with one range per
+ *     pair (CAD clouds of k voxels or more) it is the test "a query descriptor row of the pair is not finite".
+ *   cs_rows_nonfinite: d_x f32 [.., dim], d_first int64 [n_seg+1] (DEVICE, row ranges) -> d_bad int32 [n_seg]: 1 when
+ *     a row of the range holds a NaN or infinite element (the CAD side of that test: such a row is nobody's
+ *     neighbour and leaves no -1 behind).  sym_pose_batch raises ValueError on either flag, as SciPy's KD-tree does.
  *   cs_corr_assemble: d_desc int64 [n_cfg,5] (DEVICE) = {q_first, n_first, t_first, len, out_first} per
  *     configuration; writes d_src / d_tgt f32 [sum len * k, 3]: query point of d_rows[q_first + i] (d_rows NULL:
  *     row q_first + i) repeated k times against CAD points t_first + d_nn[n_first + i][0..k).  max_len = largest len.
+ *     A -1 entry is read as the CAD cloud's row 0 (never an address in front of the buffer); the callers discard
+ *     lists that hold one.
  * ---------------------------------------------------------------------------------------- */
 int cs_partition_by_label(const int32_t* d_label, const int64_t* d_off, int n_cloud, int64_t* d_order, void* stream);
 int cs_cfg_bad(const int32_t* d_nn, int k, const int64_t* d_first, int n_cfg, int32_t* d_bad, void* stream);
+int cs_rows_nonfinite(const float* d_x, int dim, const int64_t* d_first, int n_seg, int32_t* d_bad, void* stream);
 int cs_corr_assemble(const float* d_xyz0, const float* d_xyz1, const int64_t* d_rows, const int32_t* d_nn, int k,
                      const int64_t* d_desc, int n_cfg, int64_t max_len, float* d_src, float* d_tgt, void* stream);
 

@@ -106,6 +106,29 @@ def test_cad_cloud_with_fewer_voxels_than_k_is_refused_like_find_kcorr(gpu):
     assert np.array_equal(tgt[:, 3], np.tile(X1[0].cpu().numpy(), (40, 1)))      # the cloud's first row, not stray memory
 
 
+def test_cfg_bad_and_rows_nonfinite_flag_exactly_the_dirty_ranges(gpu):
+    """cs_cfg_bad and cs_rows_nonfinite at the operator level: exactly the row ranges that hold a -1 neighbour (a short CAD
+    part; over the vanilla list, a query row with a non-finite descriptor) or a non-finite element are flagged, at the
+    first and last entry of a range, next to an empty range, and a finite 1e30 is not."""
+    from corsair_amd import backend as B
+
+    rng = np.random.default_rng(9)
+    first = [0, 3, 3, 10, 300, 301, 700]
+    nn = rng.integers(0, 50, (700, 5)).astype(np.int32)
+    nn[2, 4] = -1          # last entry of range 0
+    nn[10, 0] = -1         # first entry of range 3 (not the last of range 2)
+    nn[699, 2] = -1        # last row of the last range
+    first_t = torch.tensor(first, dtype=torch.int64, device=gpu)
+    bad = B.cfg_bad(torch.from_numpy(nn).to(gpu), first_t, 6).cpu().numpy()
+    assert bad.tolist() == [int((nn[a:b] < 0).any()) for a, b in zip(first[:-1], first[1:])] == [1, 0, 0, 1, 0, 1]
+    x = rng.standard_normal((700, 16)).astype(np.float32)
+    x[9, 15] = np.nan
+    x[300, 0] = -np.inf
+    x[500, 7] = 1e30       # finite
+    bad = B.rows_nonfinite(torch.from_numpy(x).to(gpu), first_t, 6).cpu().numpy()
+    assert bad.tolist() == [0, 0, 1, 0, 1, 0]
+
+
 def test_ragged_batch_forward_row_order(gpu):
     """Batch of clouds with very different sizes: per-sample row segments stay in input order."""
     from corsair_amd import engine, synth
