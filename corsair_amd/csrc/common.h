@@ -96,12 +96,17 @@ static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // ---- coordinate packing ---------------------------------------------------------------
 // key = batch(16) | x+32768 (16) | y+32768 (16) | z+32768 (16)
+// No key of a coordinate coord_in_range accepts equals kEmptyKey: all ones would be (65535, 32767, 32767, 32767), and the
+// batch field of an accepted coordinate is at most 65534.  (With batch 65535 allowed, the insert's CAS "claimed" a slot
+// for that voxel without changing it, and a probe of that corner matched the first empty slot and returned its fill value
+// as a neighbour row.)
 __host__ __device__ static inline uint64_t pack_key(int b, int x, int y, int z) {
   return ((uint64_t)(uint16_t)b << 48) | ((uint64_t)(uint16_t)(x + 32768) << 32) |
          ((uint64_t)(uint16_t)(y + 32768) << 16) | (uint64_t)(uint16_t)(z + 32768);
 }
+static constexpr int kMaxBatch = 65535;   // 0 <= batch < kMaxBatch
 __host__ __device__ static inline bool coord_in_range(int b, int x, int y, int z) {
-  return b >= 0 && b < 65536 && x > -32768 && x < 32768 && y > -32768 && y < 32768 &&
+  return b >= 0 && b < kMaxBatch && x > -32768 && x < 32768 && y > -32768 && y < 32768 &&
          z > -32768 && z < 32768;
 }
 __host__ __device__ static inline uint64_t hash64(uint64_t k) {

@@ -295,7 +295,7 @@ int ensure_segments_many(cs_coordmap* const* maps, int n, hipStream_t s) {
   if (e == hipSuccess) keep(hipMemsetAsync(flags.p, 0, k * sizeof(int), s));
   for (size_t i = 0; i < k && e == hipSuccess; ++i) {
     cs_coordmap* m = todo[i];
-    if (last_b[i] < 0 || last_b[i] >= 65536) continue;   // stays -1: the global-table path serves this map
+    if (last_b[i] < 0 || last_b[i] >= kMaxBatch) continue;   // stays -1: the global-table path serves this map
     const int nb = last_b[i] + 1;
     seg[i] = (int32_t*)pool_alloc((size_t)(nb + 1) * sizeof(int32_t));
     if (!seg[i]) {
@@ -402,7 +402,7 @@ int cs_coordmap_create(const int32_t* d_coords, int64_t n, int tensor_stride, vo
     CS_REQUIRE(e == hipSuccess, CS_ERR_HIP, "cs_coordmap_create: %s", hipGetErrorString(e));
   }
   CS_REQUIRE(!h_status[0], CS_ERR_RANGE,
-             "cs_coordmap_create: coordinate out of the supported range (|x|,|y|,|z| < 32768, 0 <= batch < 65536)");
+             "cs_coordmap_create: coordinate out of the supported range (|x|,|y|,|z| < 32768, 0 <= batch < 65535)");
   CS_REQUIRE(!h_status[1], CS_ERR_DUPLICATE,
              "cs_coordmap_create: %d duplicate coordinate rows (quantise the cloud first)", h_status[1]);
   *out = m.release();
@@ -447,7 +447,8 @@ int cs_coordmap_stride(const cs_coordmap* in, int stride, void* stream, cs_coord
       e = download_async(h_status, status.p, sizeof(h_status), s);
     if (e == hipSuccess) e = download_sync(s);
     CS_REQUIRE(e == hipSuccess, CS_ERR_HIP, "cs_coordmap_stride: %s", hipGetErrorString(e));
-    CS_REQUIRE(!h_status[0], CS_ERR_RANGE, "cs_coordmap_stride: coordinate out of the supported range");
+    CS_REQUIRE(!h_status[0], CS_ERR_RANGE,
+               "cs_coordmap_stride: cell out of the supported range (|x|,|y|,|z| < 32768, 0 <= batch < 65535)");
   }
   m->n = (int64_t)h_last[0] + h_last[1];
   m->d_coords = (int32_t*)pool_alloc((m->n ? m->n : 1) * 4 * sizeof(int32_t));
@@ -490,7 +491,7 @@ int cs_coordmap_pyramid(const int32_t* d_coords, int64_t n, int tensor_stride, i
   hipStream_t s = (hipStream_t)stream;
   pool_use_stream(s);
   ProfScope prof("kmap", s);
-  if (n_batch > 65536) n_batch = 0;
+  if (n_batch > kMaxBatch) n_batch = 0;   // (grid.y of the level kernel is n_batch: at most 65535)
   PyrArgs a;
   a.n_levels = n_levels;
   a.n_batch = n_batch;
@@ -547,7 +548,7 @@ int cs_coordmap_pyramid(const int32_t* d_coords, int64_t n, int tensor_stride, i
   if (e == hipSuccess) e = download_sync(s);
   CS_REQUIRE(e == hipSuccess, CS_ERR_HIP, "cs_coordmap_pyramid: %s", hipGetErrorString(e));
   CS_REQUIRE(!h_status[0], CS_ERR_RANGE,
-             "cs_coordmap_pyramid: coordinate out of the supported range (|x|,|y|,|z| < 32768, 0 <= batch < 65536)");
+             "cs_coordmap_pyramid: coordinate out of the supported range (|x|,|y|,|z| < 32768, 0 <= batch < 65535)");
   CS_REQUIRE(!h_status[1], CS_ERR_DUPLICATE,
              "cs_coordmap_pyramid: %d duplicate coordinate rows (quantise the cloud first)", h_status[1]);
   for (int l = 0; l < n_levels; ++l) {

@@ -54,10 +54,15 @@ int cs_device_count(void);
  * Coordinate maps.  Replaces ME.SparseTensor(feat, coords) coordinate-manager creation
  * (evaluation.py:215-218,246-249) and the strided coordinate generation inside
  * ME.MinkowskiConvolution(stride=2) (model/resunet.py:64-72,80-87,95-103).
- * d_coords: int32 [n,4] rows (batch, x, y, z), unique, |x|,|y|,|z| < 32768, 0 <= batch < 65536.
+ * d_coords: int32 [n,4] rows (batch, x, y, z), unique, |x|,|y|,|z| < 32768, 0 <= batch < 65535.
+ * A row outside that range makes cs_coordmap_create / cs_coordmap_pyramid return CS_ERR_RANGE and no map
+ * (batch index 65535 is refused: with it a valid coordinate would pack to the hash tables' empty marker).
  * Row order of the created map == input order (evaluation.py:227-229 relies on it).
  * cs_coordmap_stride: output coords = unique rows of floor(c / (s*ts)) * (s*ts), ordered by
- * FIRST OCCURRENCE in input-row order; new tensor stride s*ts.
+ * FIRST OCCURRENCE in input-row order; new tensor stride s*ts.  The floor cells obey the same range: a
+ * row whose cell falls on -32768 (x = -32767 at cell 2; x < -32764 at cell 4; x < -32760 at cell 8)
+ * makes cs_coordmap_stride return CS_ERR_RANGE and no map; cs_coordmap_pyramid refuses such a batch as a
+ * whole (no level is returned) exactly when the chained calls for its n_levels would.
  * ---------------------------------------------------------------------------------------- */
 int cs_coordmap_create(const int32_t* d_coords, int64_t n, int tensor_stride, void* stream,
                        cs_coordmap** out);

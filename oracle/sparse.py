@@ -29,7 +29,8 @@ def _pack(coords):
     c = np.asarray(coords, dtype=np.int64)
     assert c.ndim == 2 and c.shape[1] == 4
     if c.size:
-        assert (c[:, 0] >= 0).all() and (c[:, 0] < 65536).all(), "batch index out of range"
+        # (batch 65535 is refused like coord_in_range does: (65535, 32767, 32767, 32767) would pack to the empty marker)
+        assert (c[:, 0] >= 0).all() and (c[:, 0] < 65535).all(), "batch index out of range"
         assert (np.abs(c[:, 1:]) < 32768).all(), "coordinate out of range"
     return (c[:, 0] << 48) | ((c[:, 1] + 32768) << 32) | ((c[:, 2] + 32768) << 16) | (c[:, 3] + 32768)
 
