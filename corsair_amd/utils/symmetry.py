@@ -17,7 +17,7 @@ def symmetric_cut4(feat, raw_pc, K, max_sample=100, anchor_counter=0):
     if anchors is None:
         raise ValueError("Cannot take a larger sample than population when 'replace=False'")
     a = torch.from_numpy(anchors[None]).to(f.device)
-    c, cnt, mcd, mer = B.symcut_fit(f, x, [0, n], a, [K], 50, 10, 300, 0)
+    c, cnt, mcd, mer = B.symcut_fit(f, x, [0, n], a, [K], 50, 10, 300)
     sel = R.gate_and_order(c[0].cpu().numpy(), cnt[0].cpu().numpy(), mcd[0].cpu().numpy(),
                            mer[0].cpu().numpy(), n, K)
     if sel is None:

@@ -324,7 +324,23 @@ void cs_ransac_prefilter_stats(uint64_t out[5], int reset);
  *     cloud), d_min_center_dist f64, d_max_error f64 (max over clusters of mean distance of the
  *     50-NN members to their centre).
  *   cs_symcut_labels: labels of every voxel for the chosen centres (d_sel_centers f64 [n_cloud,4,3]),
- *     argmin distance, ties -> smaller centre index.
+ *     argmin distance, ties -> smaller centre index (equidistant voxels and duplicated centres included).
+ *     Rows >= K of a cloud's centres are ignored: they may hold anything, NaN included.  An empty cloud
+ *     writes no label.
+ * Contract (tests/test_gpu_symcut.py, bit for bit against oracle/corsair_oracle.c):
+ *   - accepted: dim 16 or 32, n_nn 4..64, n_init 1..10, max_iter >= 1, n_anchor >= 1, K 2 or 4 per cloud;
+ *     anything else returns CS_ERR_UNSUPPORTED / CS_ERR_INVALID, writes nothing and leaves the library usable.
+ *     Fewer than n_nn rows: the whole cloud is the selection.  Selection ties go to the smaller row.
+ *   - every element of the four outputs is written for every (cloud, anchor).  A cloud with fewer rows than K
+ *     (0 rows included) gets centres 0, counts 0, min centre distance 0.0 and max error +inf: a model the
+ *     reference's gate (dist.min() > 0.15 > max(error)) always refuses.  The anchors of a cloud of 0 rows are
+ *     not read; those of every other cloud must be rows of it.
+ *   - a cloud of K rows or more whose selected voxels take fewer than K distinct positions gets finite centres
+ *     of which two coincide: min centre distance is exactly 0.0 (refused by the gate as well), the counts
+ *     still sum to the cloud's size; when every selected voxel is at ONE position all voxels count for centre 0
+ *     and max error is +inf (the other clusters have no member).  Rows K..3 of the centres and counts are 0.
+ *   - the result of a (cloud, anchor) depends on that cloud, that anchor and the parameters alone: not on the
+ *     other clouds or anchors of the call, their number or their order.
  * ---------------------------------------------------------------------------------------- */
 int cs_symcut_fit(const float* d_feat, int dim, const float* d_xyz, const int64_t* h_off,
                   int n_cloud, const int32_t* d_anchor, int n_anchor, const int32_t* h_K,

@@ -562,6 +562,31 @@ static int oc_nearest(const double cen[4][3], int K, const double* p, double* dm
   return best;
 }
 
+/* Branch census of the Lloyd restarts (tests state "this input takes that branch" on the reference, not on the
+ * code under test).  Counted per restart unless noted; the counters change no result:
+ *   0  an empty cluster was relocated (one count per relocated cluster)
+ *   1  Lloyd stopped because the labels repeated          2  Lloyd stopped on shift <= tol
+ *   3  Lloyd ran out of max_iter                          4  a later restart replaced the best one
+ *   5  a later restart had a smaller inertia but the same clustering, and was not taken */
+static int64_t oc_census[6];
+static inline void oc_census_add(int k, int64_t v) {
+  if (v == 0) return;
+#pragma omp atomic
+  oc_census[k] += v;
+}
+void oc_symcut_census(int64_t out[6], int reset) {
+  for (int k = 0; k < 6; ++k) {
+    int64_t v;
+#pragma omp atomic read
+    v = oc_census[k];
+    out[k] = v;
+    if (reset) {
+#pragma omp atomic write
+      oc_census[k] = 0;
+    }
+  }
+}
+
 void oc_symcut_fit_one(const float* feat, int dim, const float* xyz, int n, int anchor, int K,
                        int n_nn, int n_init, int max_iter, uint64_t seed, double* centers /*12*/,
                        int32_t* counts /*4*/, double* min_cdist, double* max_err,
@@ -679,7 +704,7 @@ void oc_symcut_fit_one(const float* feat, int dim, const float* xyz, int n, int 
     }
     int lab[64], prev[64];
     for (int i = 0; i < n_sel; ++i) prev[i] = -1;
-    int strict = 0;
+    int strict = 0, by_tol = 0, n_reloc = 0;
     for (int it = 0; it < max_iter; ++it) {
       double sum[4][3] = {{0}};
       int cn[4] = {0, 0, 0, 0};
@@ -704,6 +729,7 @@ void oc_symcut_fit_one(const float* feat, int dim, const float* xyz, int n, int 
         }
         cn[c] = 1;
         cn[old] -= 1;
+        ++n_reloc;
       }
       double shift = 0.0;
       for (int c = 0; c < K; ++c) {
@@ -718,9 +744,14 @@ void oc_symcut_fit_one(const float* feat, int dim, const float* xyz, int n, int 
         strict = 1;
         break;
       }
-      if (shift <= tol) break;
+      if (shift <= tol) {
+        by_tol = 1;
+        break;
+      }
       memcpy(prev, lab, sizeof(int) * (size_t)n_sel);
     }
+    oc_census_add(0, n_reloc);
+    oc_census_add(strict ? 1 : by_tol ? 2 : 3, 1);
     double inertia = 0.0;
     for (int i = 0; i < n_sel; ++i) {
       double dm;
@@ -738,6 +769,7 @@ void oc_symcut_fit_one(const float* feat, int dim, const float* xyz, int n, int 
         else if (mapping[lab[i]] != best_lab[i]) same_clu = 0;
       }
       take = !same_clu;
+      oc_census_add(same_clu ? 5 : 4, 1);
     }
     if (take) {
       have_best = 1;

@@ -119,6 +119,7 @@ def load():
         lib.oc_symcut_fit.argtypes = [vp, c_int, vp, c_int, vp, c_int, c_int, c_int, c_int, c_int,
                                       c_uint64, vp, vp, vp, vp]
         lib.oc_symcut_labels.argtypes = [vp, c_int, c_int, vp, vp]
+        lib.oc_symcut_census.argtypes = [vp, c_int]
         lib.oc_voxel_index.argtypes = [vp, c_int64, c_float, vp]
         lib.oc_set_threads.argtypes = [c_int]
         lib.oc_get_threads.restype = c_int
@@ -289,6 +290,18 @@ def symcut_nn_rows(feat, xyz, anchor, K, n_nn=50, n_init=10, max_iter=300, seed=
                           n_init, max_iter, seed, _p(centers), _p(counts), ctypes.byref(a),
                           ctypes.byref(b), _p(rows))
     return rows
+
+
+CENSUS_EVENTS = ("relocated", "stop_labels", "stop_tol", "stop_cap", "switch", "same_clustering_reject")
+
+
+def symcut_census(reset=False):
+    """Branch census of the Lloyd restarts run by symcut_fit / symcut_nn_rows since the last reset: int64 [6], indexed
+    like CENSUS_EVENTS (relocated empty clusters; restarts stopped by repeated labels / shift <= tol / max_iter; a later
+    restart taken as the best; a later restart of smaller inertia refused for the same clustering)."""
+    out = np.zeros(6, dtype=np.int64)
+    load().oc_symcut_census(_p(out), int(bool(reset)))
+    return out
 
 
 def symcut_labels(xyz, K, centers):
