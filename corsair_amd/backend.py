@@ -459,6 +459,33 @@ def chamfer_1dir(src, soff, tgt, toff, src_seg, tgt_seg, T):
     return out
 
 
+def chamfer_2dir(src, soff, tgt, toff, src_seg, tgt_seg, T):
+    """Batched two-directional Chamfer under one pose per problem (cs_chamfer_2dir; profile family "chamfer2"):
+    T f32 [n_prob,4,4] device.  Returns f64 [n_prob,2]: [:, 0] forward (posed source -> target, what chamfer_1dir
+    returns), [:, 1] backward (target -> posed source, in the target's frame)."""
+    src = _dev(src, torch.float32, "source").contiguous()
+    tgt = _dev(tgt, torch.float32, "target").contiguous()
+    T = _dev(T, torch.float32, "transforms").contiguous()
+    n_prob = len(src_seg)
+    if len(tgt_seg) != n_prob or T.numel() != 16 * n_prob:
+        raise ValueError("chamfer_2dir: %d source segments, %d target segments, %d transform entries"
+                         % (n_prob, len(tgt_seg), T.numel()))
+    if src.dim() != 2 or src.shape[1] != 3 or tgt.dim() != 2 or tgt.shape[1] != 3:
+        raise ValueError("chamfer_2dir: clouds must be [n,3]")
+    for name, off, seg, rows in (("source", soff, src_seg, src.shape[0]), ("target", toff, tgt_seg, tgt.shape[0])):
+        if n_prob and not (0 <= min(seg) and max(seg) + 1 < len(off)):
+            raise ValueError("chamfer_2dir: a %s segment id is outside its offset table" % name)
+        if n_prob and not (0 <= int(min(off)) and int(max(off)) <= rows):
+            raise ValueError("chamfer_2dir: the %s offset table exceeds the cloud (%d rows)" % (name, rows))
+    out = torch.empty((n_prob, 2), dtype=torch.float64, device=src.device)
+    if n_prob == 0:
+        return out
+    check(_lib.load().cs_chamfer_2dir(ptr(src), i64_array(soff), ptr(tgt), i64_array(toff),
+                                      i32_array(src_seg), i32_array(tgt_seg), n_prob, ptr(T), ptr(out),
+                                      stream_ptr()))
+    return out
+
+
 def hausdorff_1dir(src, soff, tgt, toff, src_seg, tgt_seg, T):
     """Batched directed Hausdorff distance (max over source points of the nearest-target distance)."""
     src = _dev(src, torch.float32, "source").contiguous()

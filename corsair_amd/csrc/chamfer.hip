@@ -17,6 +17,8 @@
 // distance.  A source without a target at finite distance keeps +inf, and the problem's sum or maximum is +inf.  The f16
 // kernel cannot vouch for a source or pose that is not finite (in_range), nor for a segment with an infinite or huge row
 // (tmax; a NaN row does not enter it): those workgroups go to k_chamfer_mfma.
+// cs_chamfer_2dir (both directions under one pose, the score of the candidate verification) has one path:
+// k_chamfer2, exhaustive on the VALU like k_chamfer, each direction searched with its own rows in registers.
 #include <algorithm>
 
 
@@ -440,6 +442,98 @@ __global__ void k_chamfer_finish(const double* __restrict__ partial,
     out[p] = src_count[p] > 0 ? s / (double)src_count[p] : NAN;
 }
 
+// ------------------------------------------------------------------------------------------
+// two-directional Chamfer (cs_chamfer_2dir): both directions of a problem under ONE pose
+// ------------------------------------------------------------------------------------------
+// A work item is 256 ROWS of one direction of one problem, searched against all of that problem's COLUMNS: dir 0 = rows
+// are posed sources, columns raw targets (k_chamfer's search); dir 1 = rows are raw targets, columns posed sources.  Either
+// way the pair's value is the canonical d2 of (p_i, t_j): the differences of the two directions are exact negatives of each
+// other and only their squares are used.  A row's minimum stays in its thread's register, so a column minimum of the
+// problem is never combined across workgroups: no scratch per target row, no atomics, nothing shared between the problems
+// of a call (DESIGN 18 sizes this against the one-pass form with a 64-bit atomicMin per column).  Columns are staged in
+// LDS as f64 (dir 1: posed while staging), so the inner loop is three subtractions, a product, two fmas and a minimum.
+struct Chamfer2Work {
+  int64_t r0;   // first row of this tile (global row of d_src for dir 0, of d_tgt for dir 1)
+  int64_t c0;   // first column (global row of the other array)
+  int32_t rn;   // rows in this tile (<= 256)
+  int32_t cn;   // columns
+  int32_t prob;
+  int32_t slot; // index into the partial-sum array
+  int32_t dir;  // 0 forward, 1 backward
+  int32_t pad;
+};
+
+__device__ __forceinline__ void chamfer_pose(const float* __restrict__ Tp, const float* __restrict__ s, double* px,
+                                             double* py, double* pz) {
+  const double x = s[0], y = s[1], z = s[2];
+  // row-major 4x4: p = R x + t, evaluated as fma(r0,x, fma(r1,y, fma(r2,z, t))) -- k_chamfer's chain
+  *px = fma((double)Tp[0], x, fma((double)Tp[1], y, fma((double)Tp[2], z, (double)Tp[3])));
+  *py = fma((double)Tp[4], x, fma((double)Tp[5], y, fma((double)Tp[6], z, (double)Tp[7])));
+  *pz = fma((double)Tp[8], x, fma((double)Tp[9], y, fma((double)Tp[10], z, (double)Tp[11])));
+}
+
+__global__ __launch_bounds__(256) void k_chamfer2(const Chamfer2Work* __restrict__ work, const float* __restrict__ src,
+                                                  const float* __restrict__ tgt, const float* __restrict__ T,
+                                                  double* __restrict__ partial) {
+  __shared__ double c_lds[CH_TT * 3];
+  __shared__ double red[256];
+  const Chamfer2Work wk = work[blockIdx.x];
+  const int tid = threadIdx.x;
+  const bool active = tid < wk.rn;
+  const bool fwd = wk.dir == 0;
+  const float* Tp = T + (int64_t)wk.prob * 16;
+  const float* rows = fwd ? src : tgt;
+  const float* cols = fwd ? tgt : src;
+  double rx = 0, ry = 0, rz = 0;
+  if (active) {
+    const float* r = rows + (wk.r0 + tid) * 3;
+    if (fwd) {
+      chamfer_pose(Tp, r, &rx, &ry, &rz);
+    } else {
+      rx = r[0];
+      ry = r[1];
+      rz = r[2];
+    }
+  }
+  double best = INFINITY;
+  for (int cbase = 0; cbase < wk.cn; cbase += CH_TT) {
+    const int ccount = min(CH_TT, wk.cn - cbase);
+    __syncthreads();
+    for (int j = tid; j < ccount; j += 256) {
+      const float* c = cols + (wk.c0 + cbase + j) * 3;
+      double cx, cy, cz;
+      if (fwd) {
+        cx = c[0];
+        cy = c[1];
+        cz = c[2];
+      } else {
+        chamfer_pose(Tp, c, &cx, &cy, &cz);
+      }
+      c_lds[3 * j + 0] = cx;
+      c_lds[3 * j + 1] = cy;
+      c_lds[3 * j + 2] = cz;
+    }
+    __syncthreads();
+    if (!active) continue;
+#pragma unroll 8
+    for (int j = 0; j < ccount; ++j) {
+      const double dx = rx - c_lds[3 * j + 0];
+      const double dy = ry - c_lds[3 * j + 1];
+      const double dz = rz - c_lds[3 * j + 2];
+      const double d = fma(dz, dz, fma(dy, dy, dx * dx));
+      // `best` is never NaN, so fmin is `d < best ? d : best` in one v_min_f64: a NaN d loses, +inf never replaces anything
+      best = fmin(d, best);
+    }
+  }
+  red[tid] = active ? sqrt(best) : 0.0;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if (tid < off) red[tid] = red[tid] + red[tid + off];
+    __syncthreads();
+  }
+  if (tid == 0) partial[wk.slot] = red[0];
+}
+
 }  // namespace cs
 
 using namespace cs;
@@ -567,7 +661,74 @@ static int nn_dist_reduce(const float* d_src, const int64_t* h_soff, const float
   return CS_OK;
 }
 
+// cs_chamfer_2dir: the work list holds, per problem, the forward tiles then the backward tiles; direction h = 2 p + dir is
+// finished like a problem of cs_chamfer_1dir (k_chamfer_finish over 2 n_prob "half problems": tiles left to right, mean,
+// NaN for a direction without rows), which writes d_out[2 p + dir].
+static int chamfer_2dir(const float* d_src, const int64_t* h_soff, const float* d_tgt, const int64_t* h_toff,
+                        const int32_t* h_src_seg, const int32_t* h_tgt_seg, int n_prob, const float* d_T, double* d_out,
+                        void* stream) {
+  CS_REQUIRE(h_soff && h_toff && h_src_seg && h_tgt_seg && d_T && d_out, CS_ERR_INVALID, "cs_chamfer_2dir: NULL argument");
+  if (n_prob <= 0) return CS_OK;
+  CS_REQUIRE(n_prob < (1 << 30), CS_ERR_INVALID, "cs_chamfer_2dir: too many problems");
+  hipStream_t s = (hipStream_t)stream;
+  pool_use_stream(s);
+  std::vector<Chamfer2Work> work;
+  std::vector<int32_t> slot_begin(2 * (size_t)n_prob + 1, 0);
+  std::vector<int64_t> row_count(2 * (size_t)n_prob, 0);
+  double ch_flop = 0.0;
+  for (int p = 0; p < n_prob; ++p) {
+    const int ss = h_src_seg[p], ts = h_tgt_seg[p];
+    CS_REQUIRE(ss >= 0 && ts >= 0, CS_ERR_INVALID, "cs_chamfer_2dir: negative segment id");
+    const int64_t sn = h_soff[ss + 1] - h_soff[ss], tn = h_toff[ts + 1] - h_toff[ts];
+    CS_REQUIRE(sn >= 0 && tn >= 0 && sn < (1LL << 31) && tn < (1LL << 31) && h_soff[ss] >= 0 && h_toff[ts] >= 0,
+               CS_ERR_INVALID, "cs_chamfer_2dir: bad segment in problem %d", p);
+    for (int dir = 0; dir < 2; ++dir) {
+      const int64_t rn = dir ? tn : sn, cn = dir ? sn : tn;
+      slot_begin[2 * (size_t)p + dir] = (int32_t)work.size();
+      row_count[2 * (size_t)p + dir] = rn;
+      for (int64_t q = 0; q < rn; q += 256) {
+        Chamfer2Work w;
+        w.r0 = (dir ? h_toff[ts] : h_soff[ss]) + q;
+        w.c0 = dir ? h_soff[ss] : h_toff[ts];
+        w.rn = (int32_t)(rn - q < 256 ? rn - q : 256);
+        w.cn = (int32_t)cn;
+        w.prob = p;
+        w.slot = (int32_t)work.size();
+        w.dir = dir;
+        w.pad = 0;
+        CS_REQUIRE(work.size() < (size_t)0x7fffffff, CS_ERR_INVALID, "cs_chamfer_2dir: too many tiles");
+        work.push_back(w);
+        ch_flop += 8.0 * (double)w.rn * (double)w.cn;
+      }
+    }
+  }
+  slot_begin[2 * (size_t)n_prob] = (int32_t)work.size();
+  CS_REQUIRE(work.empty() || (d_src && d_tgt), CS_ERR_INVALID, "cs_chamfer_2dir: NULL point array");
+  PoolBuf<Chamfer2Work> dwork;
+  PoolBuf<int32_t> dslot;
+  PoolBuf<int64_t> dcount;
+  PoolBuf<double> partial(work.size() + 1);
+  CS_REQUIRE(partial.p, CS_ERR_HIP, "cs_chamfer_2dir: scratch allocation failed");
+  int rc = upload(dwork, work, s);
+  if (!rc) rc = upload(dslot, slot_begin, s);
+  if (!rc) rc = upload(dcount, row_count, s);
+  if (rc) return rc;
+  ProfScope prof("chamfer2", s, ch_flop);
+  if (!work.empty())
+    hipLaunchKernelGGL(k_chamfer2, dim3((unsigned)work.size()), dim3(256), 0, s, dwork.p, d_src, d_tgt, d_T, partial.p);
+  hipLaunchKernelGGL(k_chamfer_finish, dim3((unsigned)ceil_div(2 * (int64_t)n_prob, 64)), dim3(64), 0, s, partial.p,
+                     dslot.p, dcount.p, 2 * n_prob, 0, d_out);
+  CS_LAUNCH_CHECK();
+  return CS_OK;
+}
+
 extern "C" {
+
+int cs_chamfer_2dir(const float* d_src, const int64_t* h_soff, const float* d_tgt, const int64_t* h_toff,
+                    const int32_t* h_src_seg, const int32_t* h_tgt_seg, int n_prob, const float* d_T, double* d_out,
+                    void* stream) {
+  return chamfer_2dir(d_src, h_soff, d_tgt, h_toff, h_src_seg, h_tgt_seg, n_prob, d_T, d_out, stream);
+}
 
 void cs_chamfer_f16_stats(uint64_t out[2], int reset) { read_stats(g_chamfer_stats, out, reset); }
 

@@ -24,6 +24,8 @@ from . import registration as R
 from .utils.eval_pose import eval_pose
 
 ICP_KERNEL_NAMES = tuple(B.ICP_KERNELS)       # "l2", "huber", "cauchy", "tukey"
+VERIFY_SCORES = ("symmetric", "forward")
+VERIFY_MAX_K = 32
 
 
 @dataclass
@@ -67,6 +69,25 @@ class Config:
     # (the clouds' radius = 1); 0.025 is Open3D's default and NOBODY HAS TUNED it here
     registration: str = "ransac"
     fgr_mu_floor: float = 0.025
+    # candidate verification (run_eval): the first verify_top_k retrieved CADs of every query are registered and
+    # re-ranked by the Chamfer distance of their registered pose (cs_chamfer_2dir).  0 and 1 = off (the descriptor top-1 alone,
+    # the reference's behaviour), 2 .. 32 are valid.  verify_score "symmetric" = forward + backward (the sum the reference's
+    # evaluate_retrieval forms), "forward" = posed query -> CAD alone, meant for scans that see a fraction of the object.
+    # NEITHER DEFAULT HAS BEEN TUNED on real scans: no K is recommended, and which score suits partial scans is not measured
+    verify_top_k: int = 0
+    verify_score: str = "symmetric"
+
+    def verify_k(self):
+        """Candidates per query that are registered and re-ranked; 0 when the verification is off."""
+        self.check_verify()
+        return int(self.verify_top_k) if int(self.verify_top_k) > 1 else 0
+
+    def check_verify(self):
+        k = self.verify_top_k
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 0 <= int(k) <= VERIFY_MAX_K:
+            raise ValueError("Config.verify_top_k must be an integer in [0, %d] (0 and 1 = off), got %r" % (VERIFY_MAX_K, k))
+        if self.verify_score not in VERIFY_SCORES:
+            raise ValueError("Config.verify_score must be one of %s, got %r" % (VERIFY_SCORES, self.verify_score))
 
     def icp_distance(self):
         return self.icp_max_dist if self.icp_max_dist > 0 else 2.0 * self.voxel_size
@@ -325,6 +346,84 @@ def _icp_report(a):
              if "scale_dev_mean" in a else ""))
 
 
+def _verify_report(v):
+    return (f"\ncandidate verification (top-{v['k']} re-ranked by the {v['score']} Chamfer of the registered pose):\n"
+            f"top-1 hit: {v['top1_hit_before']} -> {v['top1_hit']}, queries whose top-1 changed: {v['moved']}\n"
+            f"precision: {v['precision']}\ntop1_error: {v['top1_error']}")
+
+
+# ---- candidate verification --------------------------------------------------------------------------------
+def verify_order(scores):
+    """The order of the candidates of one query (scores [K]) or of every query (scores [Q,K]) by verification score:
+    stable ascending over the FINITE scores (equal scores keep the retrieval order), then every candidate whose score is NaN
+    or infinite, in retrieval order (-inf too, which a sum of distances never is); when nothing is finite nothing moves.
+    Returns int32 column numbers of the shape of `scores`: position 0 is the winner's column."""
+    s = np.asarray(scores, np.float64)
+    key = np.where(np.isfinite(s), s, np.inf)       # every non-finite score ties at the end; the stable sort does the rest
+    return np.argsort(key, axis=-1, kind="stable").astype(np.int32)
+
+
+def verify_scores(fb, score):
+    """Score column of the [.., 2] (forward, backward) pairs of backend.chamfer_2dir: "symmetric" = forward + backward, added
+    in f64 on the host (the sum of evaluate_retrieval, evaluation-scan2cad.py:356-357); "forward" = forward alone."""
+    fb = np.asarray(fb, np.float64)
+    if score == "symmetric":
+        return fb[..., 0] + fb[..., 1]
+    if score == "forward":
+        return fb[..., 0].copy()
+    raise ValueError("verify score must be one of %s, got %r" % (VERIFY_SCORES, score))
+
+
+def verify_rerank(rank, order):
+    """`rank` [Q,R] with its first K = order.shape[1] columns re-ordered by `order` and the remainder untouched."""
+    rank = np.asarray(rank)
+    order = np.asarray(order, np.int64)
+    K = order.shape[1]
+    return np.concatenate([np.take_along_axis(rank[:, :K], order, axis=1), rank[:, K:]], axis=1)
+
+
+def verify_stat(rank, order, table, best_match, pos_n, score="symmetric"):
+    """stat["verify"]: scan2cad_retrieval_eval_rank on the re-ranked list (verify_rerank), plus `moved` (number of queries
+    whose top-1 changed), `top1_hit` / `top1_hit_before` (share of queries whose first CAD after / before is the nearest
+    one of the annotation, stat["gt"]), and the `k` and `score` of the run."""
+    from .utils import retrieval
+
+    rank = np.asarray(rank)
+    new = verify_rerank(rank, order)
+    out = retrieval.scan2cad_retrieval_eval_rank(new, table, best_match, pos_n)
+    gt = np.asarray(out["gt"], np.int64)
+    out["moved"] = int(np.sum(new[:, 0] != rank[:, 0]))
+    out["top1_hit"] = float(np.mean(new[:, 0] == gt))
+    out["top1_hit_before"] = float(np.mean(rank[:, 0] == gt))
+    out["k"] = int(np.asarray(order).shape[1])
+    out["score"] = score
+    return out
+
+
+def verify_queries(pipe, qs, query_ids, cat, cand, syms, base_T, lib_T, force_gate=False, batch_size=None, in_flight=1,
+                   score="symmetric"):
+    """Candidate verification of the embedded queries `qs` (global numbers `query_ids`): every query is registered against
+    each of its K candidates cand[q] (int [Q,K], CAD ids in retrieval order) through the registration path of
+    register_queries -- all Q K pairs, query-major, in batches of batch_size pairs, every candidate of query i on the anchor
+    counters (2 i, 2 i + 1) --, each batch scores its last poses with one backend.chamfer_2dir call, and the candidates are
+    ordered by verify_order.  Returns the arrays of register_queries for the WINNING candidate of every query plus those of
+    cache.VERIFY_NAMES."""
+    from . import cache as C_
+
+    query_ids = np.asarray(query_ids, dtype=np.int64)
+    cand = np.asarray(cand, dtype=np.int64)
+    Q, K = cand.shape
+    pairs = _register_pairs(pipe, qs, np.repeat(np.arange(Q), K), np.repeat(query_ids, K), cat, cand.reshape(-1), syms, base_T,
+                            lib_T, force_gate, batch_size, in_flight, verify=True)
+    sc = verify_scores(pairs.pop("verify_fb"), score).reshape(Q, K)
+    vT = pairs.pop("verify_T").reshape(Q, K, 4, 4)
+    order = verify_order(sc)
+    win = np.arange(Q) * K + order[:, 0] if K else np.zeros(0, np.int64)
+    out = {k: v[win] for k, v in pairs.items()}
+    out.update(verify_cand=cand, verify_score=sc, verify_order=order, verify_T=vT)
+    return {k: (np.asarray(v, C_.VERIFY_DTYPES[k]) if k in C_.VERIFY_DTYPES else v) for k, v in out.items()}
+
+
 def run_eval(pipe, catalog, queries, best_match, table, base_T, lib_T, syms, category="chair",
              register_top1=True, cache_dir=None, ignore_cache=False, force_gate=False, batch_size=None, in_flight=1):
     """The reference's evaluation, end to end (evaluation.py:207-441), on the MI355X path.
@@ -339,10 +438,21 @@ def run_eval(pipe, catalog, queries, best_match, table, base_T, lib_T, syms, cat
          eval_pose of both estimates (evaluation.py:297-331) -- batched, not one Python iteration each;
          skipped when the nine cache files exist (evaluation.py:287, _load_data),
       4. aggregation + the log block (evaluation.py:334-383), 5. the result cache (evaluation.py:421-441).
+    Config.verify_top_k = K > 1: step 3 registers every query against its first K retrieved CADs and re-ranks them
+    by the Chamfer score of the registered pose (verify_queries); the per-query arrays are then those of the winning candidate,
+    cache.VERIFY_NAMES arrays are added and stat["verify"] holds the retrieval statistics of the re-ranked list (verify_stat);
+    every other entry of `stat` is what it is without the verification.  Needs register_top1 and K <= C.
     in_flight: registration batches in flight (host threads x HIP streams; identical results).  Returns an EvalResult."""
     from . import cache as C_
 
     cfg = pipe.cfg
+    K = cfg.verify_k() if hasattr(cfg, "verify_k") else 0
+    if K:
+        if not register_top1:
+            raise ValueError("run_eval: Config.verify_top_k = %d re-ranks the RETRIEVED candidates; it cannot be combined with "
+                             "register_top1=False (the annotated CAD)" % K)
+        if K > len(catalog):
+            raise ValueError("run_eval: Config.verify_top_k = %d exceeds the catalog (%d CADs)" % (K, len(catalog)))
     bs = batch_size or cfg.batch_size
     ebs = cfg.embed_batch_size   # (batch_size is the REGISTRATION batch; the network's forward has its own size)
     cat = catalog if isinstance(catalog, EmbeddedSet) else pipe.embed_clouds(catalog, ebs)
@@ -350,29 +460,46 @@ def run_eval(pipe, catalog, queries, best_match, table, base_T, lib_T, syms, cat
     Q = len(qs)
     best_match = np.asarray(best_match).astype(np.int64)
     syms = np.asarray(syms)
-    stat = retrieval_stat(pipe, qs.desc, cat.desc, best_match, table)
+    if K:
+        # ONE ranking of max(pos_n, K) columns: `stat` consumes its first pos_n columns as without the verification, the
+        # candidates are its first K, so candidate 0 is stat["top1_predict"] by construction
+        stat, rank = retrieval_stat(pipe, qs.desc, cat.desc, best_match, table, min_columns=K, return_rank=True)
+        pos_n = int(0.1 * np.asarray(table).shape[1])
+        cand = rank[:, :K].astype(np.int64)
+    else:
+        stat = retrieval_stat(pipe, qs.desc, cat.desc, best_match, table)
 
     per_query = None if (ignore_cache or cache_dir is None) else \
         C_.load_results(cache_dir, category, register_top1, icp=cfg.icp_max_iter > 0,
-                        icp_scale=bool(getattr(cfg, "icp_with_scaling", False)))
+                        icp_scale=bool(getattr(cfg, "icp_with_scaling", False)), **({"verify": K} if K else {}))
+    if K and per_query is not None and not np.array_equal(per_query["verify_cand"], cand):
+        per_query = None            # written for other candidates (another catalog or other descriptors): a miss
     from_cache = per_query is not None
     if per_query is None:
-        pos_idx = np.asarray(stat["top1_predict" if register_top1 else "gt"], dtype=np.int64)
-        per_query = register_queries(pipe, qs, np.arange(Q), cat, pos_idx, syms, base_T, lib_T, force_gate, bs, in_flight)
+        if K:
+            per_query = verify_queries(pipe, qs, np.arange(Q), cat, cand, syms, base_T, lib_T, force_gate, bs, in_flight,
+                                       cfg.verify_score)
+        else:
+            pos_idx = np.asarray(stat["top1_predict" if register_top1 else "gt"], dtype=np.int64)
+            per_query = register_queries(pipe, qs, np.arange(Q), cat, pos_idx, syms, base_T, lib_T, force_gate, bs, in_flight)
         if cache_dir is not None:
             C_.save_results(cache_dir, category, register_top1, per_query)
+    if K:
+        stat["verify"] = verify_stat(rank, per_query["verify_order"], table, best_match, pos_n, cfg.verify_score)
     return finish_eval(stat, per_query, from_cache)
 
 
-def retrieval_stat(pipe, q_desc, lib_desc, best_match, table):
+def retrieval_stat(pipe, q_desc, lib_desc, best_match, table, min_columns=0, return_rank=False):
     """scan2cad_retrieval_eval with Precision@M, M = int(0.1 C) (evaluation.py:272-283): the ranking comes from
-    pipe.retrieve (cs_l2_topk), the statistics from utils.retrieval."""
+    pipe.retrieve (cs_l2_topk), the statistics from utils.retrieval.  min_columns: the ranking has at least that many columns
+    (the statistics consume the first M only); return_rank: (statistics, ranking int [Q, max(M, 1, min_columns)])."""
     from .utils import retrieval
 
     pos_n = int(0.1 * np.asarray(table).shape[1])
-    rank = pipe.retrieve(q_desc, lib_desc, max(pos_n, 1))
+    rank = pipe.retrieve(q_desc, lib_desc, max(pos_n, 1, int(min_columns)))
     rank = rank.cpu().numpy() if torch.is_tensor(rank) else np.asarray(rank)
-    return retrieval.scan2cad_retrieval_eval_rank(rank, table, best_match, pos_n)
+    stat = retrieval.scan2cad_retrieval_eval_rank(rank, table, best_match, pos_n)
+    return (stat, rank) if return_rank else stat
 
 
 # Worker threads (and one torch stream each per device) of the batches-in-flight mode, kept for the life of the process: the
@@ -410,30 +537,51 @@ def register_queries(pipe, qs, query_ids, cat, pos_idx, syms, base_T, lib_T, for
     in_flight > 1: that many batches at a time, each on its own host thread and HIP stream (batches are independent;
     the library's scratch cache is per thread and stream-ordered) -- same results, the host work of one batch hides
     behind the kernels of the others (bench.py's `batches_in_flight`)."""
+    query_ids = np.asarray(query_ids, dtype=np.int64)
+    return _register_pairs(pipe, qs, np.arange(len(query_ids)), query_ids, cat, np.asarray(pos_idx)[query_ids], syms, base_T,
+                           lib_T, force_gate, batch_size, in_flight)
+
+
+def _register_pairs(pipe, qs, q_loc, query_ids, cat, cad_ids, syms, base_T, lib_T, force_gate=False, batch_size=None,
+                    in_flight=1, verify=False):
+    """register_queries' loop over explicit (query, CAD) PAIRS: pair j registers row q_loc[j] of `qs`, whose global query
+    number query_ids[j] seeds its anchor draws, against CAD cad_ids[j]; a query may occur in several pairs (the candidates of
+    one query then share its anchor counters, so each is registered exactly as if it were that query's only CAD).  Batches of
+    batch_size PAIRS.  verify: every batch also scores the last pose it produced (T_icp when the refinement runs, else
+    T_best) with one backend.chamfer_2dir call; the result then carries "verify_T" f32 [P,4,4] and "verify_fb" f64 [P,2]
+    (forward, backward)."""
     from . import cache as C_
 
     bs = batch_size or pipe.cfg.batch_size
+    q_loc = np.asarray(q_loc, dtype=np.int64)
     query_ids = np.asarray(query_ids, dtype=np.int64)
+    cad_ids = np.asarray(cad_ids, dtype=np.int64)
     icp_on = getattr(pipe.cfg, "icp_max_iter", 0) > 0
     if icp_on and len(query_ids) and hasattr(pipe, "with_normals"):
         cat = pipe.with_normals(cat)     # point-to-plane: the catalog's normals once per evaluation, gathered per batch
     scale_on = icp_on and bool(getattr(pipe.cfg, "icp_with_scaling", False))
-    names = C_.NAMES + (C_.ICP_NAMES if icp_on else ()) + (C_.ICP_SCALE_NAMES if scale_on else ())
-    dtypes = dict(C_.DTYPES, **C_.ICP_DTYPES, **C_.ICP_SCALE_DTYPES)
+    names = C_.NAMES + (C_.ICP_NAMES if icp_on else ()) + (C_.ICP_SCALE_NAMES if scale_on else ()) + \
+        (("verify_T", "verify_fb") if verify else ())
+    dtypes = dict(C_.DTYPES, **C_.ICP_DTYPES, **C_.ICP_SCALE_DTYPES, verify_T=np.float32, verify_fb=np.float64)
     if not len(query_ids):
-        return {k: np.zeros((0, 4, 4) if k.startswith("Ts_est") else 0, dtypes[k]) for k in names}
+        return {k: np.zeros((0, 4, 4) if k.startswith("Ts_est") or k == "verify_T" else ((0, 2) if k == "verify_fb" else 0),
+                            dtypes[k]) for k in names}
     batches = [np.arange(s, min(len(query_ids), s + bs)) for s in range(0, len(query_ids), bs)]
 
     def one(loc):
         ids = query_ids[loc]
-        q = qs.gather(loc)
-        cads = cat.gather(pos_idx[ids])
-        cad_sym = syms[pos_idx[ids]]
+        q = qs.gather(q_loc[loc])
+        cads = cat.gather(cad_ids[loc])
+        cad_sym = syms[cad_ids[loc]]
         res = pipe.register(q, cads, cad_sym, anchor_ids=[(2 * int(i), 2 * int(i) + 1) for i in ids],
                             force_gate=force_gate)
+        if verify:      # enqueued before the downloads below wait for the registration
+            T_last = res.T_icp if icp_on else res.T_best
+            n = list(range(len(loc)))
+            fb = B.chamfer_2dir(q.origin, q.offsets, cads.origin, cads.offsets, n, n, T_last)
         Tr, Tb, cdr, cdb = (t.cpu().numpy() for t in (res.T_ransac, res.T_best, res.cd_ransac, res.cd_best))
         T0 = [base_T[i] for i in ids]
-        T1 = [lib_T[j] for j in pos_idx[ids]]
+        T1 = [lib_T[j] for j in cad_ids[loc]]
         t_r, r_r = pose_losses(Tr, T0, T1, cad_sym)
         t_s, r_s = pose_losses(Tb, T0, T1, cad_sym)
         out = {"Ts_est_ransac": Tr, "Ts_est_best": Tb, "t_losses_ransac": t_r, "t_losses_sym": t_s,
@@ -451,6 +599,9 @@ def register_queries(pipe, qs, query_ids, cat, pos_idx, syms, base_T, lib_T, for
             if scale_on:
                 extra["icp_scale"] = sc
             out.update({k: np.asarray(v, dtypes[k]) for k, v in extra.items()})
+        if verify:
+            out["verify_T"] = Ti if icp_on else Tb
+            out["verify_fb"] = fb.cpu().numpy()
         return out
 
     depth = min(int(in_flight), len(batches))
@@ -484,7 +635,8 @@ def register_queries(pipe, qs, query_ids, cat, pos_idx, syms, base_T, lib_T, for
 
 
 def finish_eval(stat, per_query, from_cache):
-    """Aggregation + the log block (evaluation.py:334-383) over the per-query arrays of ALL queries."""
+    """Aggregation + the log block (evaluation.py:334-383) over the per-query arrays of ALL queries; one more block when the
+    candidate verification ran (stat["verify"])."""
     ransac = aggregate(per_query["r_losses_ransac"], per_query["t_losses_ransac"], per_query["chamfer_dist_ransac"])
     sym = aggregate(per_query["r_losses_sym"], per_query["t_losses_sym"], per_query["chamfer_dist_sym"])
     for a, r in ((ransac, per_query["r_losses_ransac"]), (sym, per_query["r_losses_sym"])):
@@ -501,6 +653,8 @@ def finish_eval(stat, per_query, from_cache):
             icp["scale_dev_max"] = float(np.max(dev)) if len(dev) else 0.0
         res.icp = icp
         res.report += _icp_report(icp)
+    if isinstance(stat, dict) and "verify" in stat:
+        res.report += _verify_report(stat["verify"])
     return res
 
 
@@ -640,6 +794,11 @@ def build_parser():
                     help="correspondence estimator: the reference's RANSAC, or Fast Global Registration (cs_fgr_batch)")
     ap.add_argument("--fgr-mu-floor", type=float, default=0.025,
                     help="floor of FGR's mu, in units of the clouds' radius (Open3D's default, untuned)")
+    ap.add_argument("--verify-top-k", type=int, default=0,
+                    help="register every query against its first K retrieved CADs and re-rank them by the Chamfer score of the "
+                         "registered pose (cs_chamfer_2dir); 0 and 1 = off, 2..32 (untuned; not with --register-gt)")
+    ap.add_argument("--verify-score", default="symmetric", choices=list(VERIFY_SCORES),
+                    help="score of --verify-top-k: forward + backward Chamfer, or forward alone (for partial scans; untuned)")
     ap.add_argument("--in-flight", type=int, default=3, help="registration batches in flight (host threads x HIP streams)")
     ap.add_argument("--device", default="cuda", choices=["cuda"], help="there is no CPU path")
     return ap
@@ -651,6 +810,9 @@ def main(argv=None):
     from .utils import ckpts, pc_dist
 
     a = build_parser().parse_args(argv)
+    if Config(verify_top_k=a.verify_top_k, verify_score=a.verify_score).verify_k() and not a.register_top1:
+        raise ValueError("--verify-top-k %d re-ranks the retrieved candidates; it cannot be combined with --register-gt"
+                         % a.verify_top_k)             # (before anything is loaded or set)
     # (eight hardware queues for the streams of the registration batches in flight: bench.py's note; only effective when
     # nothing has touched the GPU yet -- the command-line entry --, an explicit setting wins)
     import os
@@ -660,6 +822,7 @@ def main(argv=None):
     if esd is None:
         raise SystemExit("checkpoint has no embedding_state_dict: retrieval needs the descriptor head (evaluation.py:199)")
     cfg = Config(n_points=a.n_points, batch_size=a.batch_size, embed_batch_size=a.embed_batch_size,
+                 verify_top_k=a.verify_top_k, verify_score=a.verify_score,
                  ransac_max_iter=a.ransac_max_iter, icp_max_iter=a.icp_iters, icp_max_dist=a.icp_max_dist,
                  icp_estimation=a.icp_estimation, icp_normal_k=a.icp_normal_k, icp_kernel=a.icp_kernel,
                  icp_kernel_scale=a.icp_kernel_scale, icp_normal_radius=a.icp_normal_radius,

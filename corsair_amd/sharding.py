@@ -238,6 +238,9 @@ def run_eval_sharded(pipe, dist, rank, world, catalog, queries, best_match, tabl
         return H.run_eval(pipe, catalog, queries, best_match, table, base_T, lib_T, syms, category, register_top1,
                           cache_dir, True, force_gate, batch_size, in_flight)
     cfg = pipe.cfg
+    if int(getattr(cfg, "verify_top_k", 0) or 0) > 1:
+        raise NotImplementedError("run_eval_sharded: candidate verification (Config.verify_top_k > 1) is not sharded over the "
+                                  "ranks; run it on one rank (harness.run_eval) or set verify_top_k = 0")
     if getattr(cfg, "icp_max_iter", 0) > 0:
         raise ValueError("run_eval_sharded: ICP refinement (Config.icp_max_iter > 0) is not gathered over the ranks yet; "
                          "run it on one rank (harness.run_eval) or set icp_max_iter = 0")

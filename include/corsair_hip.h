@@ -276,6 +276,32 @@ int cs_hausdorff_1dir(const float* d_src, const int64_t* h_soff, const float* d_
                       int n_prob, const float* d_T, double* d_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Two-directional Chamfer of posed clouds: the score of a candidate verification (the two one-directional sums the
+ * reference's evaluate_retrieval adds, evaluation-scan2cad.py:356-357), both directions from ONE pose and one call.
+ * Arguments and problem selection are those of cs_chamfer_1dir; d_out is f64 [n_prob][2].
+ * Problem p, source rows s_i (i < ns), target rows t_j (j < nt), M = d_T[p] (f32, row-major 4x4), everything in f64:
+ *   p_i,c   = fma(M_c0, s_i,x, fma(M_c1, s_i,y, fma(M_c2, s_i,z, M_c3)))            -- the chain of cs_chamfer_1dir
+ *   d2_ij   = fma(dz, dz, fma(dy, dy, dx * dx)),   (dx, dy, dz) = p_i - t_j
+ *   d_out[2p]     = (sum over i of sqrt(min_j d2_ij)) / ns     forward: what cs_chamfer_1dir returns
+ *   d_out[2p + 1] = (sum over j of sqrt(min_i d2_ij)) / nt     backward, measured in the frame of the TARGET (the
+ *                   source is posed, the target is not: no pose is inverted anywhere)
+ * Non-finite rows, both directions, by cs_chamfer_1dir's rules: a pair at NaN or +inf distance is never the nearest
+ * (every minimum starts at +inf and is an fmin, in which a NaN operand loses); a row or column without a partner at finite distance
+ * contributes +inf, so that direction is +inf.  An empty source segment: forward NaN (and backward +inf unless the target
+ * is empty too); an empty target segment: backward NaN, forward +inf as in cs_chamfer_1dir.
+ * Reproducibility: every minimum is an exact canonical d2 (order-free); a direction's sum is added per tile of 256
+ * consecutive rows by a fixed pairwise tree (row i of the tile at leaf i, strides 128, 64, ... 1), the tiles then left to
+ * right.  Two calls return identical bits and a problem's two values do not depend on the other problems of the call.
+ * Problems may share source segments, target segments or both: a column minimum belongs to its problem.
+ * One path: exhaustive, f64 on the vector unit (each direction searches with its own rows in registers).  Scratch: one
+ * f64 per 256-row tile plus the work list, from the calling thread's pool.  Segments hold fewer than 2^31 rows.
+ * Profile family "chamfer2".
+ * ---------------------------------------------------------------------------------------- */
+int cs_chamfer_2dir(const float* d_src, const int64_t* h_soff, const float* d_tgt, const int64_t* h_toff,
+                    const int32_t* h_src_seg, const int32_t* h_tgt_seg, int n_prob, const float* d_T,
+                    double* d_out /* [n_prob][2] */, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Batched correspondence RANSAC.  Replaces registration_based_on_corr ->
  * o3d.pipelines.registration.registration_ransac_based_on_correspondence(src, tgt, corr,
  * max_corr, ransac_n=10) (utils/eval_pose.py:82-100).  Problem p owns correspondences
@@ -855,7 +881,7 @@ int cs_fgr_batch(const float* d_src, const float* d_tgt, const int64_t* h_off, i
  * Profiling hooks for bench.py: when enabled the library brackets the launches of each named
  * kernel family with hipEvents on the launch stream and accumulates the elapsed time.
  * names: "conv", "ransac_eval", "ransac_pre", "ransac_hyp", "knn", "chamfer", "topk", "symcut",
- * "kmap", "loss", "hardneg", "icp", "normals", "fgr".
+ * "kmap", "loss", "hardneg", "icp", "normals", "fgr", "chamfer2".
  * ---------------------------------------------------------------------------------------- */
 void cs_prof_enable(int on);
 void cs_prof_reset(void);
