@@ -109,6 +109,9 @@ def _declare(lib):
         "cs_icp_scale_batch": (c_int, [vp, POINTER(c_int64), vp, vp, POINTER(c_int64), POINTER(c_int32), POINTER(c_int32),
                                        c_int, vp, c_double, c_int, c_double, c_double, c_double, c_double, vp, vp, vp, vp,
                                        vp, vp, vp, vp, vp]),
+        "cs_icp_gicp_batch": (c_int, [vp, vp, POINTER(c_int64), vp, vp, POINTER(c_int64), POINTER(c_int32), POINTER(c_int32),
+                                      c_int, vp, c_double, c_int, c_double, c_double, c_double, vp, vp, vp, vp, vp, vp, vp,
+                                      vp, vp]),
         "cs_estimate_normals": (c_int, [vp, POINTER(c_int64), c_int, c_int, vp, vp]),
         "cs_estimate_normals_hybrid": (c_int, [vp, POINTER(c_int64), c_int, c_double, c_int, vp, vp]),
         "cs_normals_stats": (None, [POINTER(c_uint64), c_int]),

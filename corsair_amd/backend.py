@@ -510,6 +510,17 @@ class IcpResult(NamedTuple):
     corr_off: Optional[list]
     wfitness: Optional[torch.Tensor] = None   # f64 [n_prob] weighted inlier share (a robust kernel was asked for)
     scale: Optional[torch.Tensor] = None      # f64 [n_prob] the factor the call added to T0 (with_scaling was asked for)
+    # f64 [n_prob] Mahalanobis rmse of the last evaluation, filled by estimation = "gicp" (GicpResult below).  An attribute, NOT
+    # a field of the tuple: the tuple keeps the ten fields above, whose layout callers and tests rely on
+    mrmse = None
+
+
+class GicpResult(IcpResult):
+    """The IcpResult of estimation = "gicp": the same ten-field tuple with the attribute `mrmse` set."""
+    def __new__(cls, *fields, mrmse=None):
+        self = super().__new__(cls, *fields)
+        self.mrmse = mrmse
+        return self
 
 
 ICP_KERNELS = {"l2": 0, "huber": 1, "cauchy": 2, "tukey": 3}    # CS_ICP_KERNEL_*
@@ -544,7 +555,7 @@ def normals_stats(reset=False):
 
 def icp_batch(src, soff, tgt, toff, src_seg, tgt_seg, T0, max_dist, max_iter=30, relative_fitness=1e-6,
               relative_rmse=1e-6, return_corr=False, tgt_normals=None, kernel="l2", kernel_scale=None, with_scaling=False,
-              scale_bounds=(0.5, 2.0)):
+              scale_bounds=(0.5, 2.0), *, estimation=None, src_normals=None, gicp_epsilon=1e-3):
     """cs_icp_batch: point-to-point ICP of problem p = source segment src_seg[p] of `src` against target segment
     tgt_seg[p] of `tgt` (f32 [n,3] device, host offset lists), started at T0[p] (f32 [n_prob,4,4] device).  The semantics
     are the header comment of cs_icp_batch.  tgt_normals (f32, the shape of `tgt`; estimate_normals): point-to-plane
@@ -554,7 +565,25 @@ def icp_batch(src, soff, tgt, toff, src_seg, tgt_seg, T0, max_dist, max_iter=30,
     an isotropic scale of the source as one more unknown (Open3D's with_scaling = true for the point estimation); T is then
     a similarity and IcpResult.scale the factor the call added to T0.  A problem whose accumulated scale would leave
     scale_bounds = (min, max), min <= 1 <= max, stops before that update; the default (0.5, 2.0) is untuned.  Robust
-    kernels with a scale are out of scope and refused.  Returns an IcpResult; no host wait."""
+    kernels with a scale are out of scope and refused.  estimation = "gicp" (keyword-only, with src_normals and
+    gicp_epsilon): plane-to-plane Generalized ICP, cs_icp_gicp_batch, on tgt_normals AND src_normals (f32, the shape of
+    `src`, in the source's own frame), both required; gicp_epsilon in [2^-10, 1] is the covariance floor along the normal
+    (Open3D's default 1e-3, untuned here) and IcpResult.mrmse the Mahalanobis rmse.  A robust kernel or with_scaling with
+    GICP is out of scope and refused.  estimation = None keeps the rule above (tgt_normals decide).  Returns an IcpResult;
+    no host wait."""
+    if estimation not in (None, "gicp"):
+        raise ValueError("icp_batch: estimation must be None or 'gicp', got %r" % (estimation,))
+    gicp = estimation == "gicp"
+    if gicp:
+        if kernel != "l2" or with_scaling:
+            raise ValueError("icp_batch: estimation 'gicp' with a robust kernel or with_scaling is out of scope")
+        if tgt_normals is None or src_normals is None:
+            raise ValueError("icp_batch: estimation 'gicp' needs tgt_normals and src_normals")
+        eps = float(gicp_epsilon)
+        if not (np.isfinite(eps) and 2.0 ** -10 <= eps <= 1.0):
+            raise ValueError("icp_batch: gicp_epsilon must lie in [2^-10, 1], got %r" % (gicp_epsilon,))
+    elif src_normals is not None:
+        raise ValueError("icp_batch: src_normals are used by estimation = 'gicp' only")
     if with_scaling:
         if kernel != "l2":
             raise ValueError("icp_batch: with_scaling with a robust kernel (%r) is out of scope: robust kernels exist for "
@@ -608,7 +637,16 @@ def icp_batch(src, soff, tgt, toff, src_seg, tgt_seg, T0, max_dist, max_iter=30,
         nrm = _dev(tgt_normals, torch.float32, "target normals").contiguous()
         if nrm.shape != tgt.shape:
             raise ValueError("icp_batch: tgt_normals must have the shape of the target points")
-    if with_scaling:
+    mrmse = None
+    if gicp:
+        snrm = _dev(src_normals, torch.float32, "source normals").contiguous()
+        if snrm.shape != src.shape:
+            raise ValueError("icp_batch: src_normals must have the shape of the source points")
+        mrmse = torch.empty(n_prob, dtype=torch.float64, device=dev)
+        check(_lib.load().cs_icp_gicp_batch(
+            ptr(src), ptr(snrm), i64_array(soff), ptr(tgt), ptr(nrm), *head, eps, ptr(T), ptr(T32), ptr(fitness), ptr(rmse),
+            ptr(mrmse), ptr(iters), ptr(ncorr), ptr(corr), stream_ptr()))
+    elif with_scaling:
         scale = torch.empty(n_prob, dtype=torch.float64, device=dev)
         check(_lib.load().cs_icp_scale_batch(
             ptr(src), i64_array(soff), ptr(tgt), ptr(nrm), *head, smin, smax, ptr(T), ptr(T32), ptr(fitness), ptr(rmse),
@@ -625,6 +663,8 @@ def icp_batch(src, soff, tgt, toff, src_seg, tgt_seg, T0, max_dist, max_iter=30,
                 ptr(T32), ptr(fitness), ptr(rmse), ptr(wfitness), ptr(iters), ptr(ncorr), ptr(corr), stream_ptr()))
     if corr is not None:
         corr = corr[:corr_off[-1]]
+    if gicp:
+        return GicpResult(T, T32, fitness, rmse, iters, ncorr, corr, corr_off, wfitness, scale, mrmse=mrmse)
     return IcpResult(T, T32, fitness, rmse, iters, ncorr, corr, corr_off, wfitness, scale)
 
 

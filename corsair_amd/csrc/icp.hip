@@ -1,19 +1,20 @@
-// Batched ICP: point-to-point (cs_icp_batch), point-to-plane (cs_icp_plane_batch), point-to-plane
-// with a robust kernel (cs_icp_plane_robust_batch) and both estimations with an isotropic scale (cs_icp_scale_batch).  The
-// specifications are the comments of the four entries in include/corsair_hip.h; tests/icp_ref.py, tests/icp_plane_ref.py,
-// tests/icp_robust_ref.py and tests/icp_scale_ref.py restate them bit for bit.  The estimation is a compile-time parameter
-// EST (0 = point, 1 = plane, 2 = plane with a per-pair weight, 3 = point + scale, 4 = plane + scale) of the sums at the end
-// of the association kernels and of the update; pose chain, association, evaluation, loop and stop rule are one code.  The
-// rigid instantiations are what they were before the others existed: kernel = L2 runs EST = 1, and nothing of EST = 3 / 4
-// is launched unless cs_icp_scale_batch is called.
+// Batched ICP: point-to-point (cs_icp_batch), point-to-plane (cs_icp_plane_batch),
+// point-to-plane with a robust kernel (cs_icp_plane_robust_batch), both estimations with an isotropic scale
+// (cs_icp_scale_batch) and plane-to-plane, Generalized ICP (cs_icp_gicp_batch).  The specifications are the comments of the
+// five entries in include/corsair_hip.h; tests/icp_ref.py, tests/icp_plane_ref.py, tests/icp_robust_ref.py,
+// tests/icp_scale_ref.py and tests/gicp_ref.py restate them bit for bit.  The estimation is a compile-time parameter
+// EST (0 = point, 1 = plane, 2 = plane with a per-pair weight, 3 = point + scale, 4 = plane + scale, 5 = plane-to-plane) of
+// the sums at the end of the association kernels and of the update; pose chain, association, evaluation, loop and stop rule
+// are one code.  The rigid instantiations are what they were before the others existed: kernel = L2 runs EST = 1, nothing of
+// EST = 3 / 4 is launched unless cs_icp_scale_batch is called and nothing of EST = 5 unless cs_icp_gicp_batch is.
 //
 // One call = one target preparation + (max_iter + 1) rounds, all enqueued without a host wait:
 //   k_icp_frame    per problem: the bounding box of its target segment (exact min / max), the origin and the
 //                  power-of-two scales of its fixed-point sums
 //   chamfer_pack16 the f16 hi / lo image, |S t|^2 and the float4 rows of every target, once per call
 //   round r:       k_icp_f16 (+ k_icp_exact for the workgroups it flags) or k_icp_exact alone -- association of the posed
-//                  ORIGINAL sources under the current T, 17 (point), 29 (plane), 30 (weighted plane), 18 (point + scale)
-//                  or 37 (plane + scale) order-free 64-bit integer sums per problem; k_icp_step -- one lane per problem:
+//                  ORIGINAL sources under the current T, 17 (point), 29 (plane), 30 (weighted plane), 18 (point + scale),
+//                  37 (plane + scale) or 30 (GICP) order-free 64-bit integer sums per problem; k_icp_step -- one lane per problem:
 //                  fitness / rmse of that association, the stop rule, Horn's fit (point) or the 6x6 / 7x7 normal equations
 //                  by Cholesky (plane) from the sums, T <- U T.
 // A problem that has stopped raises its device flag; its workgroups leave on it in every later round.
@@ -35,10 +36,13 @@ constexpr int ICP_NSUM_PLANE = 29;        // count, sum J_i J_j (i <= j, 21), su
 constexpr int ICP_NSUM_ROBUST = 30;       // the 29 plane sums (27 of them weighted) + sum w
 constexpr int ICP_NSUM_POINT_S = 18;      // the 17 point sums + sum p'.p'
 constexpr int ICP_NSUM_PLANE_S = 37;      // count, sum J_i J_j (i <= j, 28), sum J_i r (7), sum d^2
-constexpr int ICP_POINT = 0, ICP_PLANE = 1, ICP_ROBUST = 2, ICP_POINT_S = 3, ICP_PLANE_S = 4;
+constexpr int ICP_NSUM_GICP = 30;         // count, sum (J^T W J)_ij (i <= j, 21), sum (J^T W e)_i (6), sum d^2, sum e.We
+constexpr int ICP_POINT = 0, ICP_PLANE = 1, ICP_ROBUST = 2, ICP_POINT_S = 3, ICP_PLANE_S = 4, ICP_GICP = 5;
+// the estimations with a target normal array, the plane frame and the 6x6 / 7x7 normal equations: GICP's 30 sums have the
+// plane layout (count, 21 matrix entries, 6 right-hand sides, d^2) with one more sum behind it
 template <int EST>
 constexpr bool icp_is_plane() {
-  return EST == ICP_PLANE || EST == ICP_ROBUST || EST == ICP_PLANE_S;
+  return EST == ICP_PLANE || EST == ICP_ROBUST || EST == ICP_PLANE_S || EST == ICP_GICP;
 }
 template <int EST>
 constexpr bool icp_has_scale() {
@@ -47,6 +51,7 @@ constexpr bool icp_has_scale() {
 template <int EST>
 constexpr int icp_nsum() {
   return EST == ICP_ROBUST    ? ICP_NSUM_ROBUST
+         : EST == ICP_GICP    ? ICP_NSUM_GICP
          : EST == ICP_PLANE   ? ICP_NSUM_PLANE
          : EST == ICP_POINT_S ? ICP_NSUM_POINT_S
          : EST == ICP_PLANE_S ? ICP_NSUM_PLANE_S
@@ -102,6 +107,22 @@ __host__ __device__ constexpr bool icp_rot_col(int i) { return i < 3 || i == 6; 
 // Plane + scale (EST = 4).  The seventh column J_6 = p'.n has |J_6| <= |p'| |n| <= sqrt(3) M < 2 M: bounded like a
 // rotational column a_c, so J_6 J_6 and a_i J_6 join the class rot x rot, n_i J_6 the class rot x trans and J_6 r the class
 // rot x r; their bounds are those above and no new scale is needed.
+//
+// Plane-to-plane, GICP (EST = 5).  Per kept pair W = Mc^-1 is symmetric with eigenvalues in [1/2, 1/(2 eps)], so
+// |W_ij| <= |W|_2 <= 1/(2 eps) <= 2^eW (eW in [-1, 9] for eps in [2^-10, 1]).  With |p'_c| <= M, |p'| <= sqrt(3) M, and
+// |e| < max_dist <= M:
+//   trans x trans |W_ij|                  <= 2^eW
+//   rot x trans   |K_ij| = |(p' x w_j)_i| <= |p'| |w_j| <= sqrt(3) M 2^eW            < 2^(eM + 1 + eW)
+//   rot x rot     |(p' x k_i)_j|          <= |p'| |[p']x W|_2 <= 3 M^2 2^eW          < 2^(2 eM + 2 + eW)
+//   trans x e     |u_i| <= |W e|          <  2^eW max_dist                           < 2^(eM + eW)
+//   rot x e       |(p' x u)_i|            <  sqrt(3) M 2^eW max_dist                 < 2^(2 eM + 1 + eW)
+//   e . u         <= |e|^2 / (2 eps)                                                  < 2^(2 eM + eW)
+// (w_j a column of W, k_i a row of K; the 3 x 3 contractions are inside the norm bounds, sqrt(3) < 2 and 3 < 4 are the bits
+// they need).  These are the plane classes times 2^eW, so the five plane scales carry -eW and e . u shares the scale of
+// rot x e, one bit above its bound; with the ONE extra bit per class for the roundings (the adjugate inverse has a relative
+// error of a few 2^-53 / eps <= 2^-40) every scaled term is below 2^(61 - eN) and every sum below 2^61 for normals of any
+// length, since the covariances are built from normalised directions.  The clamp keeps the sums defined for any input.
+// The exponents stay inside [-782, 261]: normal f64 powers of two, exact scaling.
 constexpr int ICP_EM_MIN = -100;
 constexpr int ICP_EM_MAX = 400;
 constexpr int ICP_SUM_BITS = 61;
@@ -137,9 +158,10 @@ struct IcpCriteria {
   double scale_min, scale_max;   // the interval of the accumulated scale (EST = 3, 4)
 };
 
+// eW: the exponent the plane scales give up to GICP's weight matrix (0 for every other estimation)
 __global__ __launch_bounds__(256) void k_icp_frame(const IcpProb* __restrict__ probs, const float* __restrict__ tgt,
                                                    double max_dist, IcpFrame* __restrict__ frame,
-                                                   IcpPlaneFrame* __restrict__ pframe) {
+                                                   IcpPlaneFrame* __restrict__ pframe, int eW) {
   __shared__ float red[2][3][4];
   const IcpProb pr = probs[blockIdx.x];
   const int tid = threadIdx.x;
@@ -198,7 +220,7 @@ __global__ __launch_bounds__(256) void k_icp_frame(const IcpProb* __restrict__ p
   f.inv_pp = ldexp(1.0, -(s2 - 2));
   frame[blockIdx.x] = f;
   if (pframe) {
-    const int b = ICP_SUM_BITS - eN;
+    const int b = ICP_SUM_BITS - eN - eW;
     IcpPlaneFrame g;
     g.sc_rr = ldexp(1.0, b - 2 * eM - 3);
     g.inv_rr = ldexp(1.0, -(b - 2 * eM - 3));
@@ -243,21 +265,103 @@ __device__ __forceinline__ double icp_weight(const IcpLoss& ls, double r) {
   return w == w ? w : 0.0;
 }
 
-// The sums of one workgroup (17 point, 29 plane, 30 weighted plane, 18 point + scale, 37 plane + scale): thread = one
-// source (kept or not), wave shuffle, LDS across the four waves, then ONE 64-bit integer atomic per sum.  Integer addition:
-// the same total in any order.  nrow: the normal row of the matched target (plane estimation, kept pairs only).
+// GICP: the gain g of the covariance C = I - g n n^T, g = (1 - eps) / (n . n), of a normal n.  A normal with a non-finite
+// component, or with n . n zero or not finite, is replaced by 0 with g = 0: C = I.
+__device__ __forceinline__ double icp_gicp_gain(double (&n)[3], double ome) {
+  const double nn = fma(n[2], n[2], fma(n[1], n[1], n[0] * n[0]));
+  if (!(isfinite(n[0]) && isfinite(n[1]) && isfinite(n[2]) && isfinite(nn) && nn > 0.0)) {
+    n[0] = n[1] = n[2] = 0.0;
+    return 0.0;
+  }
+  return ome / nn;
+}
+
+// p x v, the fma shape of the plane Jacobian's a = p' x n
+__device__ __forceinline__ void icp_cross(const double (&p)[3], double v0, double v1, double v2, double (&out)[3]) {
+  out[0] = fma(p[1], v2, -(p[2] * v1));
+  out[1] = fma(p[2], v0, -(p[0] * v2));
+  out[2] = fma(p[0], v1, -(p[1] * v0));
+}
+
+// The sums of one workgroup (17 point, 29 plane, 30 weighted plane, 18 point + scale, 37 plane + scale, 30 GICP): thread =
+// one source (kept or not), wave shuffle, LDS across the four waves, then ONE 64-bit integer atomic per sum.  Integer
+// addition: the same total in any order.  nrow: the normal row of the matched target (plane estimations, kept pairs only);
+// srow, Tp, ome: the source's own normal row, the round's T and 1 - eps (GICP, kept pairs only).
 template <int EST>
 __device__ __forceinline__ void icp_block_sums(bool kept, double px, double py, double pz, float qx, float qy, float qz,
                                                double d2, const IcpFrame& fr, const IcpPlaneFrame* __restrict__ pfr,
                                                const float* __restrict__ nrow, const IcpLoss& loss,
                                                unsigned long long* __restrict__ sums,
-                                               unsigned long long (*part)[icp_nsum<EST>()]) {
+                                               unsigned long long (*part)[icp_nsum<EST>()],
+                                               const float* __restrict__ srow = nullptr,
+                                               const double* __restrict__ Tp = nullptr, double ome = 0.0) {
   constexpr int NS = icp_nsum<EST>();
   const int tid = threadIdx.x;
   long long v[NS];
 #pragma unroll
   for (int k = 0; k < NS; ++k) v[k] = 0;
-  if constexpr (icp_is_plane<EST>()) {
+  if constexpr (EST == ICP_GICP) {
+    if (kept) {
+      const IcpPlaneFrame g = *pfr;
+      const double p[3] = {px - fr.o[0], py - fr.o[1], pz - fr.o[2]};
+      const double e[3] = {px - (double)qx, py - (double)qy, pz - (double)qz};
+      double nt[3] = {(double)nrow[0], (double)nrow[1], (double)nrow[2]};
+      // m = A n_s, A the upper 3 x 3 block of T: icp_pose's chain without the translation
+      const double sx = srow[0], sy = srow[1], sz = srow[2];
+      double m[3] = {fma(Tp[0], sx, fma(Tp[1], sy, Tp[2] * sz)), fma(Tp[4], sx, fma(Tp[5], sy, Tp[6] * sz)),
+                     fma(Tp[8], sx, fma(Tp[9], sy, Tp[10] * sz))};
+      const double gt = icp_gicp_gain(nt, ome), gs = icp_gicp_gain(m, ome);
+      const double at[3] = {gt * nt[0], gt * nt[1], gt * nt[2]}, as[3] = {gs * m[0], gs * m[1], gs * m[2]};
+      // Mc = 2 I - g_t n_t n_t^T - g_s m m^T (symmetric, the six entries i <= j)
+      const double M00 = fma(-as[0], m[0], fma(-at[0], nt[0], 2.0)), M01 = fma(-as[0], m[1], -(at[0] * nt[1])),
+                   M02 = fma(-as[0], m[2], -(at[0] * nt[2])), M11 = fma(-as[1], m[1], fma(-at[1], nt[1], 2.0)),
+                   M12 = fma(-as[1], m[2], -(at[1] * nt[2])), M22 = fma(-as[2], m[2], fma(-at[2], nt[2], 2.0));
+      // W = adj(Mc) / det(Mc): cofactors, the determinant along the first row, ONE division
+      const double c00 = fma(M11, M22, -(M12 * M12)), c01 = fma(M02, M12, -(M01 * M22)),
+                   c02 = fma(M01, M12, -(M02 * M11)), c11 = fma(M00, M22, -(M02 * M02)),
+                   c12 = fma(M01, M02, -(M00 * M12)), c22 = fma(M00, M11, -(M01 * M01));
+      const double det = fma(M02, c02, fma(M01, c01, M00 * c00));
+      const double id = 1.0 / det;
+      double W[3][3];
+      W[0][0] = c00 * id;
+      W[0][1] = W[1][0] = c01 * id;
+      W[0][2] = W[2][0] = c02 * id;
+      W[1][1] = c11 * id;
+      W[1][2] = W[2][1] = c12 * id;
+      W[2][2] = c22 * id;
+      double u[3], K[3][3], RR[3][3], bu[3];
+#pragma unroll
+      for (int i = 0; i < 3; ++i) u[i] = fma(W[i][2], e[2], fma(W[i][1], e[1], W[i][0] * e[0]));
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {   // column j of K = p' x column j of W
+        double col[3];
+        icp_cross(p, W[0][j], W[1][j], W[2][j], col);
+        K[0][j] = col[0];
+        K[1][j] = col[1];
+        K[2][j] = col[2];
+      }
+#pragma unroll
+      for (int i = 0; i < 3; ++i) icp_cross(p, K[i][0], K[i][1], K[i][2], RR[i]);   // row i = p' x row i of K
+      icp_cross(p, u[0], u[1], u[2], bu);
+      v[0] = 1;
+      int at_ = 1;
+#pragma unroll
+      for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = i; j < 6; ++j) {
+          const double val = j < 3 ? RR[i][j] : (i < 3 ? K[i][j - 3] : W[i - 3][j - 3]);
+          const double sc = j < 3 ? g.sc_rr : (i < 3 ? g.sc_rt : g.sc_tt);
+          v[at_++] = icp_fix(val, sc, fr.clamp);
+        }
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        v[22 + i] = icp_fix(bu[i], g.sc_rd, fr.clamp);
+        v[25 + i] = icp_fix(u[i], g.sc_td, fr.clamp);
+      }
+      v[28] = icp_fix(d2, fr.sc2, fr.clamp);
+      v[29] = icp_fix(fma(e[2], u[2], fma(e[1], u[1], e[0] * u[0])), g.sc_rd, fr.clamp);
+    }
+  } else if constexpr (icp_is_plane<EST>()) {
     constexpr int NJ = icp_nj<EST>(), NJJ = NJ * (NJ + 1) / 2;
     if (kept) {
       const IcpPlaneFrame g = *pfr;
@@ -344,7 +448,8 @@ __global__ __launch_bounds__(256) void k_icp_exact(const IcpWork* __restrict__ w
                                                    const int32_t* __restrict__ done, double thr2,
                                                    IcpLoss loss, unsigned long long* __restrict__ sums,
                                                    int32_t* __restrict__ corr,
-                                                   const int32_t* __restrict__ only_flagged) {
+                                                   const int32_t* __restrict__ only_flagged,
+                                                   const float* __restrict__ snrm, double ome) {
   __shared__ float t_lds[ICP_TT * 3];
   __shared__ unsigned long long part[4][icp_nsum<EST>()];
   if (only_flagged && !only_flagged[blockIdx.x]) return;
@@ -385,7 +490,8 @@ __global__ __launch_bounds__(256) void k_icp_exact(const IcpWork* __restrict__ w
   if (corr && active) corr[wk.c0 + tid] = kept ? bidx : -1;
   icp_block_sums<EST>(kept, px, py, pz, qx, qy, qz, best, frame[wk.prob], icp_is_plane<EST>() ? pframe + wk.prob : nullptr,
                       icp_is_plane<EST>() && kept ? tnrm + (pr.t0 + bidx) * 3 : nullptr, loss,
-                      sums + (int64_t)wk.prob * icp_nsum<EST>(), part);
+                      sums + (int64_t)wk.prob * icp_nsum<EST>(), part,
+                      EST == ICP_GICP && kept ? snrm + (wk.s0 + tid) * 3 : nullptr, T + (int64_t)wk.prob * 16, ome);
 }
 
 // The association on the f16 matrix cores: k_chamfer_f16's ranking (same image, same operand layout, same error budget;
@@ -403,7 +509,8 @@ __global__ __launch_bounds__(256) void k_icp_f16(const IcpWork* __restrict__ wor
                                                  const int32_t* __restrict__ done, double thr2,
                                                  IcpLoss loss, unsigned long long* __restrict__ sums,
                                                  int32_t* __restrict__ corr, int32_t* __restrict__ flag,
-                                                 unsigned long long* __restrict__ stats) {
+                                                 unsigned long long* __restrict__ stats,
+                                                 const float* __restrict__ snrm, double ome) {
   __shared__ __attribute__((aligned(16))) _Float16 a_s[2][CHF_ROWS * CHF_PITCH];
   __shared__ __attribute__((aligned(16))) float tn_s[2][CHF_ROWS];
   __shared__ unsigned long long part[4][icp_nsum<EST>()];
@@ -609,7 +716,8 @@ __global__ __launch_bounds__(256) void k_icp_f16(const IcpWork* __restrict__ wor
   icp_block_sums<EST>(kept, mpx, mpy, mpz, q.x, q.y, q.z, my_e, frame[wk.prob],
                       icp_is_plane<EST>() ? pframe + wk.prob : nullptr,
                       icp_is_plane<EST>() && kept ? tnrm + (pr.t0 + my_row) * 3 : nullptr, loss,
-                      sums + (int64_t)wk.prob * icp_nsum<EST>(), part);
+                      sums + (int64_t)wk.prob * icp_nsum<EST>(), part,
+                      EST == ICP_GICP && kept ? snrm + (wk.s0 + tid) * 3 : nullptr, Tp, ome);
 }
 
 __device__ __forceinline__ bool icp_all_finite(const double* v, int n) {
@@ -767,7 +875,7 @@ __global__ void k_icp_step(const IcpProb* __restrict__ probs, int n_prob, const 
                            unsigned long long* __restrict__ sums, int32_t* __restrict__ done, double* __restrict__ T,
                            float* __restrict__ T32, double* __restrict__ fitness, double* __restrict__ rmse,
                            double* __restrict__ wfitness, double* __restrict__ scale, int32_t* __restrict__ iters,
-                           int32_t* __restrict__ ncorr) {
+                           int32_t* __restrict__ ncorr, double* __restrict__ mrmse) {
   constexpr int NS = icp_nsum<EST>();
   constexpr int MIN_CORR = icp_is_plane<EST>() ? icp_nj<EST>() : 3;   // one pair per unknown of the plane system
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
@@ -791,6 +899,12 @@ __global__ void k_icp_step(const IcpProb* __restrict__ probs, int n_prob, const 
         wfitness[p] = pr.sn > 0 ? ((double)(long long)S[NS - 1] * (1.0 / fr.clamp)) / (double)pr.sn : 0.0;
       else
         wfitness[p] = fit;
+    }
+    if constexpr (EST == ICP_GICP) {   // the Mahalanobis rmse of this association: sum e.We shares the scale of rot x e
+      if (mrmse) {
+        const double sm = (double)(long long)S[NS - 1] * pframe[p].inv_rd;
+        mrmse[p] = n > 0 && sm > 0.0 ? sqrt(sm / dn) : 0.0;
+      }
     }
     bool stop = last != 0;
     if (round > 0 && fabs(fit - pfit) < crit.rel_fitness && fabs(rm - prm) < crit.rel_rmse) stop = true;
@@ -841,14 +955,16 @@ std::atomic<unsigned long long> g_icp_stats[2];
 
 // Every entry: d_tnrm is the normal array of the plane estimations (EST = 1, 2), loss the kernel of EST = 2, d_wfitness the
 // optional weighted inlier share of cs_icp_plane_robust_batch (NULL for the other entries), scale_min / scale_max / d_scale
-// the interval and the output of cs_icp_scale_batch (EST = 3, 4).
+// the interval and the output of cs_icp_scale_batch (EST = 3, 4), d_snrm / epsilon / d_mrmse the source normals, the
+// covariance floor and the optional Mahalanobis rmse of cs_icp_gicp_batch (EST = 5).
 template <int EST>
 int icp_run(const char* name, const float* d_src, const int64_t* h_soff, const float* d_tgt, const float* d_tnrm,
             const int64_t* h_toff, const int32_t* h_src_seg, const int32_t* h_tgt_seg, int n_prob, const float* d_T0,
             double max_dist, int max_iter, double relative_fitness, double relative_rmse, double* d_T, float* d_T32,
             double* d_fitness, double* d_rmse, int32_t* d_iters, int32_t* d_ncorr, int32_t* d_corr, void* stream,
             IcpLoss loss = IcpLoss{CS_ICP_KERNEL_L2, 0.0}, double* d_wfitness = nullptr, double scale_min = 1.0,
-            double scale_max = 1.0, double* d_scale = nullptr) {
+            double scale_max = 1.0, double* d_scale = nullptr, const float* d_snrm = nullptr, double epsilon = 1.0,
+            double* d_mrmse = nullptr) {
   constexpr int NS = icp_nsum<EST>();
   CS_REQUIRE(h_soff && h_toff && h_src_seg && h_tgt_seg, CS_ERR_INVALID, "%s: NULL table", name);
   CS_REQUIRE(n_prob >= 0, CS_ERR_INVALID, "%s: negative problem count", name);
@@ -891,6 +1007,13 @@ int icp_run(const char* name, const float* d_src, const int64_t* h_soff, const f
   CS_REQUIRE(work.empty() || d_src, CS_ERR_INVALID, "%s: NULL source array", name);
   CS_REQUIRE(nt_rows == 0 || d_tgt, CS_ERR_INVALID, "%s: NULL target array", name);
   CS_REQUIRE(!icp_is_plane<EST>() || nt_rows == 0 || d_tnrm, CS_ERR_INVALID, "%s: NULL target normal array", name);
+  CS_REQUIRE(EST != ICP_GICP || work.empty() || d_snrm, CS_ERR_INVALID, "%s: NULL source normal array", name);
+  // GICP: 1 - eps, and eW = the smallest integer with 1 / (2 eps) <= 2^eW, i.e. 1 <= eps * 2^(eW + 1) (exact); in [-1, 9]
+  const double ome = 1.0 - epsilon;
+  int eW = 0;
+  if (EST == ICP_GICP)
+    for (eW = -1; std::ldexp(epsilon, eW + 1) < 1.0; ++eW) {
+    }
   hipStream_t s = (hipStream_t)stream;
   pool_use_stream(s);
   const bool use_f16 = !env_first_is("CS_ICP_F16", '0');
@@ -913,7 +1036,8 @@ int icp_run(const char* name, const float* d_src, const int64_t* h_soff, const f
   const dim3 pgrid((unsigned)ceil_div(n_prob, 64));
   hipLaunchKernelGGL(k_icp_init, pgrid, dim3(64), 0, s, d_T0, n_prob, d_T, d_fitness, d_rmse, d_wfitness,
                      icp_has_scale<EST>() ? d_scale : (double*)nullptr, d_iters, d_ncorr, done.p);
-  hipLaunchKernelGGL(k_icp_frame, dim3((unsigned)n_prob), dim3(256), 0, s, dprob.p, d_tgt, max_dist, frame.p, pframe.p);
+  hipLaunchKernelGGL(k_icp_frame, dim3((unsigned)n_prob), dim3(256), 0, s, dprob.p, d_tgt, max_dist, frame.p, pframe.p, eW);
+  if (EST == ICP_GICP && d_mrmse) CS_HIP_CHECK(hipMemsetAsync(d_mrmse, 0, sizeof(double) * (size_t)n_prob, s));
   // the targets do not move: one image for every round
   PoolBuf<_Float16> img16;
   PoolBuf<float> tn16;
@@ -940,19 +1064,19 @@ int icp_run(const char* name, const float* d_src, const int64_t* h_soff, const f
       if (use_f16) {
         hipLaunchKernelGGL(k_icp_f16<EST>, dim3(n_work), dim3(256), 0, s, dwork.p, dprob.p, d_src, t4f.p, img16.p, tn16.p,
                            d_tnrm, (const double*)d_T, frame.p, pframe.p, done.p, crit.thr2, loss, sums.p, d_corr, wflag.p,
-                           want_stats ? dstats : (unsigned long long*)nullptr);
+                           want_stats ? dstats : (unsigned long long*)nullptr, d_snrm, ome);
         hipLaunchKernelGGL(k_icp_exact<EST>, dim3(n_work), dim3(256), 0, s, dwork.p, dprob.p, d_src, d_tgt, d_tnrm,
                            (const double*)d_T, frame.p, pframe.p, done.p, crit.thr2, loss, sums.p, d_corr,
-                           (const int32_t*)wflag.p);
+                           (const int32_t*)wflag.p, d_snrm, ome);
       } else {
         hipLaunchKernelGGL(k_icp_exact<EST>, dim3(n_work), dim3(256), 0, s, dwork.p, dprob.p, d_src, d_tgt, d_tnrm,
                            (const double*)d_T, frame.p, pframe.p, done.p, crit.thr2, loss, sums.p, d_corr,
-                           (const int32_t*)nullptr);
+                           (const int32_t*)nullptr, d_snrm, ome);
       }
     }
     hipLaunchKernelGGL(k_icp_step<EST>, pgrid, dim3(64), 0, s, dprob.p, n_prob, frame.p, pframe.p, crit, round,
                        round == max_iter ? 1 : 0, sums.p, done.p, d_T, d_T32, d_fitness, d_rmse, d_wfitness, d_scale,
-                       d_iters, d_ncorr);
+                       d_iters, d_ncorr, d_mrmse);
   }
   CS_LAUNCH_CHECK();
   if (want_stats) {
@@ -1030,6 +1154,19 @@ int cs_icp_scale_batch(const float* d_src, const int64_t* h_soff, const float* d
   return icp_run<ICP_POINT_S>(name, d_src, h_soff, d_tgt, nullptr, h_toff, h_src_seg, h_tgt_seg, n_prob, d_T0, max_dist,
                               max_iter, relative_fitness, relative_rmse, d_T, d_T32, d_fitness, d_rmse, d_iters, d_ncorr,
                               d_corr, stream, l2, nullptr, scale_min, scale_max, d_scale);
+}
+
+int cs_icp_gicp_batch(const float* d_src, const float* d_src_normal, const int64_t* h_soff, const float* d_tgt,
+                      const float* d_tgt_normal, const int64_t* h_toff, const int32_t* h_src_seg, const int32_t* h_tgt_seg,
+                      int n_prob, const float* d_T0, double max_dist, int max_iter, double relative_fitness,
+                      double relative_rmse, double epsilon, double* d_T, float* d_T32, double* d_fitness, double* d_rmse,
+                      double* d_mrmse, int32_t* d_iters, int32_t* d_ncorr, int32_t* d_corr, void* stream) {
+  const char* name = "cs_icp_gicp_batch";
+  CS_REQUIRE(std::isfinite(epsilon) && epsilon >= 0x1.0p-10 && epsilon <= 1.0, CS_ERR_INVALID,
+             "%s: epsilon must lie in [2^-10, 1]", name);
+  return icp_run<ICP_GICP>(name, d_src, h_soff, d_tgt, d_tgt_normal, h_toff, h_src_seg, h_tgt_seg, n_prob, d_T0, max_dist,
+                           max_iter, relative_fitness, relative_rmse, d_T, d_T32, d_fitness, d_rmse, d_iters, d_ncorr, d_corr,
+                           stream, IcpLoss{CS_ICP_KERNEL_L2, 0.0}, nullptr, 1.0, 1.0, nullptr, d_src_normal, epsilon, d_mrmse);
 }
 
 }  // extern "C"

@@ -40,6 +40,8 @@ __device__ __forceinline__ void icp_compose(const double (&R)[3][3], const doubl
 // the share of column j of the Jacobian that the columns before it do not explain; the fixed-point sums carry each A_jj to
 // 2^-44 relative or better (scale 2^(61 - eN - ...) against at most 2^eN terms of that magnitude bound), so a share below
 // 2^-30 is four decimal orders above the noise of the sums and far below any geometry that constrains the pose.
+// cs_icp_gicp_batch's sums give up eW <= 9 bits to the weight matrix; its header comment and DESIGN 19 re-derive the margin
+// (relative noise of a translational A_jj at most 2^-(59 - eN - eW); a pivot share at least epsilon times the geometry's).
 constexpr double ICP_PIVOT_MIN = 0x1.0p-30;
 
 // A x = -b for the symmetric NJ x NJ matrix A by an unpivoted Cholesky (the operation sequence is the header comment of

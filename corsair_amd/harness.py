@@ -50,7 +50,12 @@ class Config:
     icp_max_dist: float = 0.0
     # "point" (cs_icp_batch) or "plane" (cs_icp_plane_batch on the normals of the CAD voxels, cs_estimate_normals over
     # icp_normal_k neighbours).  16 is UNTUNED: 8 and 16 behaved alike in the experiment that motivated it
+    # "gicp" (cs_icp_gicp_batch): plane-to-plane Generalized ICP on the normals of BOTH clouds, the CAD voxels' as
+    # for "plane" (a catalog's are computed once), the query voxels' estimated per batch with the same icp_normal_k /
+    # icp_normal_radius.  gicp_epsilon in [2^-10, 1] is the covariance floor along the normal: 1e-3 is Open3D's default and
+    # NOBODY HAS TUNED it here, nor icp_normal_k for this estimation.  No robust kernel, no scale
     icp_estimation: str = "point"
+    gicp_epsilon: float = 1e-3
     icp_normal_k: int = 16
     # 0.0 = those k nearest rows (the default); > 0: the at most icp_normal_k nearest rows strictly inside this radius
     # (cs_estimate_normals_hybrid), in the units of the clouds.  NO RADIUS HAS BEEN TUNED
@@ -100,8 +105,13 @@ class Config:
             raise ValueError("Config.registration must be 'ransac' or 'fgr', got %r" % (self.registration,))
         if not (0.0 < float(self.fgr_mu_floor) < float("inf")):
             raise ValueError("Config.fgr_mu_floor must be positive and finite, got %r" % (self.fgr_mu_floor,))
-        if self.icp_estimation not in ("point", "plane"):
-            raise ValueError("Config.icp_estimation must be 'point' or 'plane', got %r" % (self.icp_estimation,))
+        if self.icp_estimation not in ("point", "plane", "gicp"):
+            raise ValueError("Config.icp_estimation must be 'point', 'plane' or 'gicp', got %r" % (self.icp_estimation,))
+        if self.icp_estimation == "gicp":
+            if self.icp_kernel != "l2" or self.icp_with_scaling:
+                raise ValueError("Config.icp_estimation 'gicp' with a robust icp_kernel or icp_with_scaling is out of scope")
+            if not (np.isfinite(float(self.gicp_epsilon)) and 2.0 ** -10 <= float(self.gicp_epsilon) <= 1.0):
+                raise ValueError("Config.gicp_epsilon must lie in [2^-10, 1], got %r" % (self.gicp_epsilon,))
         if self.icp_kernel not in ICP_KERNEL_NAMES:
             raise ValueError("Config.icp_kernel must be one of %s, got %r" % (ICP_KERNEL_NAMES, self.icp_kernel))
         if self.icp_kernel != "l2" and self.icp_estimation != "plane":
@@ -125,9 +135,10 @@ class Config:
         return float(self.icp_normal_radius) if self.icp_normal_radius > 0 else None
 
     def icp_plane(self):
-        """True when the run refines with the point-to-plane estimation (and so needs the CAD voxels' normals)."""
+        """True when the run refines with the point-to-plane or the plane-to-plane (GICP) estimation (and so needs the CAD
+        voxels' normals)."""
         self.check_icp()
-        return self.icp_max_iter > 0 and self.icp_estimation == "plane"
+        return self.icp_max_iter > 0 and self.icp_estimation in ("plane", "gicp")
 
 
 @dataclass
@@ -253,12 +264,12 @@ class Pipeline:
                                 icp_with_scaling=c.icp_with_scaling,
                                 icp_scale_bounds=tuple(c.icp_scale_bounds) if c.icp_with_scaling else None,
                                 icp_kernel=c.icp_kernel, icp_kernel_scale=c.icp_scale() if c.icp_kernel != "l2" else None,
-                                registration=c.registration, fgr_mu_floor=c.fgr_mu_floor)
+                                registration=c.registration, fgr_mu_floor=c.fgr_mu_floor, gicp_epsilon=c.gicp_epsilon)
 
     def with_normals(self, s):
         """`s` with the normals of its origins (one cs_estimate_normals call over the whole set, or one
         cs_estimate_normals_hybrid call when the configuration has an icp_normal_radius) when the configuration refines
-        point-to-plane and the set has none yet; `s` itself otherwise."""
+        point-to-plane or plane-to-plane (GICP) and the set has none yet; `s` itself otherwise."""
         if not self.cfg.icp_plane() or s.normal is not None:
             return s
         return EmbeddedSet(s.F, s.origin, s.offsets, s.desc, B.estimate_normals(s.origin, s.offsets, self.cfg.icp_normal_k, self.cfg.normal_radius()))
@@ -774,8 +785,11 @@ def build_parser():
                     help="refine every kept pose with at most N point-to-point ICP updates (0 = off, the reference's behaviour)")
     ap.add_argument("--icp-max-dist", type=float, default=0.0,
                     help="ICP correspondence distance; 0 = 2 * voxel size (an untuned default)")
-    ap.add_argument("--icp-estimation", default="point", choices=["point", "plane"],
-                    help="ICP estimation: point-to-point, or point-to-plane on the CAD voxels' normals")
+    ap.add_argument("--icp-estimation", default="point", choices=["point", "plane", "gicp"],
+                    help="ICP estimation: point-to-point, point-to-plane on the CAD voxels' normals, or plane-to-plane "
+                         "(Generalized ICP) on the normals of both clouds")
+    ap.add_argument("--gicp-epsilon", type=float, default=1e-3,
+                    help="covariance floor along the normal for --icp-estimation gicp, in [2^-10, 1] (Open3D's default, untuned)")
     ap.add_argument("--icp-normal-k", type=int, default=16,
                     help="neighbours of a CAD voxel's normal for --icp-estimation plane, 3..32 (an untuned default)")
     ap.add_argument("--icp-normal-radius", type=float, default=0.0,
@@ -827,7 +841,7 @@ def main(argv=None):
                  icp_estimation=a.icp_estimation, icp_normal_k=a.icp_normal_k, icp_kernel=a.icp_kernel,
                  icp_kernel_scale=a.icp_kernel_scale, icp_normal_radius=a.icp_normal_radius,
                  icp_with_scaling=a.icp_with_scaling, icp_scale_bounds=(a.icp_scale_min, a.icp_scale_max),
-                 registration=a.registration, fgr_mu_floor=a.fgr_mu_floor)
+                 registration=a.registration, fgr_mu_floor=a.fgr_mu_floor, gicp_epsilon=a.gicp_epsilon)
     cfg.check_icp()
     pipe = Pipeline(sd, esd, device=a.device, config=cfg)
     cad_names, catalog = load_cloud_dir(a.catalog_dir, a.n_points, "catalog")

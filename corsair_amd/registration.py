@@ -64,6 +64,7 @@ class SymPoseResult:
     icp_iters: torch.Tensor = None      # int32 [P] updates applied
     icp_wfitness: torch.Tensor = None   # f64 [P] weighted inlier share; only with a robust icp_kernel
     icp_scale: torch.Tensor = None      # f64 [P] the isotropic scale the ICP added to T_best; only with icp_with_scaling
+    icp_mrmse: torch.Tensor = None      # f64 [P] Mahalanobis rmse; only with icp_estimation = "gicp"
 
     def hypotheses(self, p):
         """Problems of pair p in evaluation order."""
@@ -167,8 +168,12 @@ def _sym_pose_batch(estimator, baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_
                     icp_estimation="point", icp_normal_k=16, normals1=None, icp_normal_radius=None, icp_with_scaling=False,
                     icp_scale_bounds=None, icp_kernel="l2", icp_kernel_scale=None):
     """The body of sym_pose_batch (below, with the documentation).  estimator = (registration, fgr_mu_floor,
-    fgr_iterations, fgr_tuple_test), already checked."""
-    registration, fgr_mu_floor, fgr_iterations, fgr_tuple_test = estimator
+    fgr_iterations, fgr_tuple_test, normals0, gicp_epsilon), the keyword-only options; the first four already checked."""
+    registration, fgr_mu_floor, fgr_iterations, fgr_tuple_test, normals0, gicp_epsilon = estimator
+    if icp_estimation == "gicp" and (icp_with_scaling or icp_kernel != "l2"):
+        raise ValueError("sym_pose_batch: icp_estimation 'gicp' with icp_with_scaling or a robust icp_kernel is out of scope")
+    if icp_estimation != "gicp" and normals0 is not None:
+        raise ValueError("sym_pose_batch: normals0 is used by icp_estimation = 'gicp' only")
     if icp_with_scaling and icp_kernel != "l2":
         raise ValueError("sym_pose_batch: icp_with_scaling with a robust icp_kernel (%r) is out of scope" % (icp_kernel,))
     if icp_kernel not in B.ICP_KERNELS:
@@ -177,8 +182,8 @@ def _sym_pose_batch(estimator, baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_
         raise ValueError("sym_pose_batch: icp_kernel %r needs icp_estimation = 'plane'" % (icp_kernel,))
     if icp_max_iter > 0 and icp_kernel != "l2" and not (icp_kernel_scale is not None and icp_kernel_scale > 0):
         raise ValueError("sym_pose_batch: icp_kernel %r needs a positive icp_kernel_scale" % (icp_kernel,))
-    if icp_estimation not in ("point", "plane"):
-        raise ValueError("sym_pose_batch: icp_estimation must be 'point' or 'plane', got %r" % (icp_estimation,))
+    if icp_estimation not in ("point", "plane", "gicp"):
+        raise ValueError("sym_pose_batch: icp_estimation must be 'point', 'plane' or 'gicp', got %r" % (icp_estimation,))
     if icp_normal_radius is not None and not (0 < icp_normal_radius < float("inf")):
         raise ValueError("sym_pose_batch: icp_normal_radius must be positive and finite (None = k-NN), got %r"
                          % (icp_normal_radius,))
@@ -368,18 +373,22 @@ def _sym_pose_batch(estimator, baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_
     if icp_max_iter > 0:
         pairs = list(range(P))
         nrm = None
-        if icp_estimation == "plane":
+        if icp_estimation in ("plane", "gicp"):
             nrm = normals1 if normals1 is not None else B.estimate_normals(xyz1, off1, icp_normal_k, icp_normal_radius)
         scaling = {}
         if icp_with_scaling:
             scaling = {"with_scaling": True}
             if icp_scale_bounds is not None:
                 scaling["scale_bounds"] = icp_scale_bounds
+        if icp_estimation == "gicp":     # the query voxels' normals, in the query's own (posed) frame
+            snrm = normals0 if normals0 is not None else B.estimate_normals(xyz0, off0, icp_normal_k, icp_normal_radius)
+            scaling = {"estimation": "gicp", "src_normals": snrm, "gicp_epsilon": gicp_epsilon}
         r = B.icp_batch(xyz0, off0, xyz1, off1, pairs, pairs, res.T_best, icp_max_dist, icp_max_iter, tgt_normals=nrm,
                         kernel=icp_kernel, kernel_scale=icp_kernel_scale, **scaling)
         res.T_icp, res.icp_fitness, res.icp_rmse, res.icp_iters = r.T32, r.fitness, r.rmse, r.iters
         res.icp_wfitness = r.wfitness
         res.icp_scale = r.scale
+        res.icp_mrmse = r.mrmse
         res.cd_icp = B.chamfer_1dir(xyz0, off0, xyz1, off1, pairs, pairs, r.T32)
     return res
 
@@ -416,10 +425,18 @@ def sym_pose_batch(*args, registration="ransac", fgr_mu_floor=0.025, fgr_iterati
     fgr_batch's mu_floor, iteration_number and tuple_test; max_iter and confidence are the RANSAC's and unused then.  With
     the default "ransac" nothing of it is launched.  These four are accepted by keyword ONLY, behind every parameter
     above; `inspect.signature` keeps reporting the parameters above (`__signature__` below), whose order and end existing
-    callers and tests rely on."""
+    callers and tests rely on.
+    icp_estimation = "gicp": the refinement is plane-to-plane Generalized ICP (cs_icp_gicp_batch), which models a local
+    plane on BOTH clouds: the CAD side works as for "plane" (normals1, else estimated here), the query side takes normals0
+    f32 [N0,3] in the query's own frame, else cs_estimate_normals over the query voxels with the same icp_normal_k /
+    icp_normal_radius.  gicp_epsilon in [2^-10, 1] is the covariance floor along the normal (Open3D's default; untuned here,
+    as is icp_normal_k for this estimation).  normals0 (default None) and gicp_epsilon (default 1e-3) are accepted by keyword
+    only, like the fgr_* options, and are taken out of **kwargs here.  icp_mrmse is filled too.  A robust icp_kernel or icp_with_scaling with "gicp" is out of scope and refused."""
     if registration not in ("ransac", "fgr"):
         raise ValueError("sym_pose_batch: registration must be 'ransac' or 'fgr', got %r" % (registration,))
-    return _sym_pose_batch((registration, fgr_mu_floor, fgr_iterations, fgr_tuple_test), *args, **kwargs)
+    normals0, gicp_epsilon = kwargs.pop("normals0", None), kwargs.pop("gicp_epsilon", 1e-3)
+    return _sym_pose_batch((registration, fgr_mu_floor, fgr_iterations, fgr_tuple_test, normals0, gicp_epsilon), *args,
+                           **kwargs)
 
 
 # the positional interface (everything but the keyword-only estimator options), as introspection has always shown it

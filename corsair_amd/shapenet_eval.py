@@ -37,7 +37,10 @@ class Config:
     # icp_normal_k neighbours of the posed copy's voxels, untuned)
     icp_max_iter: int = 0
     icp_max_dist: float = 0.0
+    # "gicp": plane-to-plane Generalized ICP (cs_icp_gicp_batch) on the normals of both clouds, each over icp_normal_k
+    # neighbours; gicp_epsilon in [2^-10, 1] is Open3D's default covariance floor, UNTUNED as in harness.Config
     icp_estimation: str = "point"
+    gicp_epsilon: float = 1e-3
     icp_normal_k: int = 16
     # 0.0 = k-NN (the default); > 0: the at most icp_normal_k nearest rows strictly inside this radius (UNTUNED)
     icp_normal_radius: float = 0.0
@@ -194,7 +197,8 @@ def evaluate(pipe, clouds, cfg=None, pairs_per_batch=16, seed=None, force_gate=F
                                icp_scale_bounds=tuple(cfg.icp_scale_bounds) if scale_on else None,
                                icp_kernel=cfg.icp_kernel,
                                icp_kernel_scale=cfg.icp_scale() if cfg.icp_kernel != "l2" else None,
-                               registration=cfg.registration, fgr_mu_floor=cfg.fgr_mu_floor)
+                               registration=cfg.registration, fgr_mu_floor=cfg.fgr_mu_floor,
+                               gicp_epsilon=cfg.gicp_epsilon)
         Tb, Tr = res.T_best.cpu().numpy(), res.T_ransac.cpu().numpy()
         cdb, cdr = res.cd_best.cpu().numpy(), res.cd_ransac.cpu().numpy()
         for i, (mi, pi, _, _, pose, label, s_gt) in enumerate(chunk):
@@ -320,7 +324,9 @@ def build_parser():
     ap.add_argument("--icp-iters", type=int, default=0,
                     help="refine every kept pose with at most N ICP updates (0 = off, the reference's behaviour)")
     ap.add_argument("--icp-max-dist", type=float, default=0.0, help="ICP correspondence distance; 0 = 2 * voxel size")
-    ap.add_argument("--icp-estimation", default="point", choices=["point", "plane"])
+    ap.add_argument("--icp-estimation", default="point", choices=["point", "plane", "gicp"])
+    ap.add_argument("--gicp-epsilon", type=float, default=1e-3,
+                    help="covariance floor along the normal for --icp-estimation gicp, in [2^-10, 1] (Open3D's default, untuned)")
     ap.add_argument("--icp-normal-k", type=int, default=16)
     ap.add_argument("--icp-normal-radius", type=float, default=0.0,
                     help="radius of the normals' hybrid search (at most --icp-normal-k rows inside it); 0 = k-NN (untuned)")
@@ -368,7 +374,7 @@ def main(argv=None):
                  icp_estimation=a.icp_estimation, icp_normal_k=a.icp_normal_k, icp_kernel=a.icp_kernel,
                  icp_kernel_scale=a.icp_kernel_scale, icp_normal_radius=a.icp_normal_radius, max_log_scale=a.max_log_scale,
                  icp_with_scaling=a.icp_with_scaling, icp_scale_bounds=(a.icp_scale_min, a.icp_scale_max),
-                 registration=a.registration, fgr_mu_floor=a.fgr_mu_floor)
+                 registration=a.registration, fgr_mu_floor=a.fgr_mu_floor, gicp_epsilon=a.gicp_epsilon)
     results = evaluate(pipe, clouds, cfg)
     postfix = f"shapenet-seed{a.random_seed}-{a.category}-{len(files)}-{a.n_poses_per_model}"
     os.makedirs(a.out_dir, exist_ok=True)

@@ -729,6 +729,70 @@ int cs_icp_scale_batch(const float* d_src, const int64_t* h_soff, const float* d
                        double* d_scale, int32_t* d_iters, int32_t* d_ncorr, int32_t* d_corr, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * cs_icp_gicp_batch: cs_icp_batch with a plane-to-plane estimation, Generalized ICP (Segal, Haehnel, Thrun, RSS 2009;
+ * [O3D-knowledge] Open3D's registration_generalized_icp / TransformationEstimationForGeneralizedICP as remembered, not
+ * checked against Open3D) in the place of the point-to-point estimation (tests/gicp_ref.py restates it bit for
+ * bit).  The arguments are those of cs_icp_plane_batch plus d_src_normal f32 [rows of d_src, 3], the normal of every source
+ * row in the source's OWN frame, `epsilon` and one more optional output, d_mrmse f64 [n_prob].  Problems, pose chain,
+ * association (both paths, the strict voucher, CS_ICP_F16, CS_ICP_STATS / cs_icp_stats), evaluation (fitness and rmse from
+ * the POINT distances d2), loop, stop criteria, outputs, independence, empty-segment answers (mrmse 0), and stream behaviour
+ * are those of cs_icp_batch: the same code.  What differs is the sums and the update.  Every operation below is ONE IEEE f64
+ * operation unless a fused fma(a, b, c) is written; only + - * / sqrt fma appear.
+ *   Covariance of a row with normal n: C(n) = I - g n n^T, g = (1 - epsilon) / nn, nn = fma(n_z, n_z, fma(n_y, n_y, n_x * n_x))
+ *     ([O3D-knowledge] Open3D's Rx diag(epsilon, 1, 1) Rx^T, Rx taking e_1 onto the normal, written without building Rx: valid
+ *     for a normal of any length and either sign).  A normal with a non-finite component, or with nn zero or not finite, is
+ *     replaced by n = 0, g = 0: C = I, the row is weighted isotropically.  1 - epsilon is computed once.
+ *   Per kept pair, with o, M, eM, eN of cs_icp_batch: p' = p - o, e = p - q, n = (double) normal row of the matched
+ *     target, s = (double) normal row of the source, m = A s with A the upper 3 x 3 block of the round's T:
+ *       m_c = fma(T_c0, s_x, fma(T_c1, s_y, T_c2 * s_z))        -- the pose chain without the translation.
+ *     Normalising m by m . m means a similarity T0 only ROTATES the source covariance (deliberate difference: Open3D forms
+ *     T C_s T^T, which also scales it).  With g_t, g_s the gains of n and m, a_i = g_t * n_i, b_i = g_s * m_i:
+ *       Mc = C(n) + C(m):  Mc_ii = fma(-b_i, m_i, fma(-a_i, n_i, 2)),  Mc_ij (i < j) = fma(-b_i, m_j, -(a_i * n_j));
+ *     its eigenvalues lie in [2 epsilon, 2].  W = Mc^-1 by the adjugate over the determinant:
+ *       c00 = fma(M11, M22, -(M12 * M12)),  c01 = fma(M02, M12, -(M01 * M22)),  c02 = fma(M01, M12, -(M02 * M11)),
+ *       c11 = fma(M00, M22, -(M02 * M02)),  c12 = fma(M01, M02, -(M00 * M12)),  c22 = fma(M00, M11, -(M01 * M01)),
+ *       det = fma(M02, c02, fma(M01, c01, M00 * c00)),  id = 1 / det,  W_ij = W_ji = c_ij * id;   |W|_2 <= 1 / (2 epsilon).
+ *     u = W e: u_i = fma(W_i2, e_z, fma(W_i1, e_y, W_i0 * e_x)).  The Jacobian of p <- p + omega x p' + t is
+ *     J = [-[p']x | I], three residual rows per pair; with x(p', v) = (fma(p'_y, v_z, -(p'_z * v_y)),
+ *     fma(p'_z, v_x, -(p'_x * v_z)), fma(p'_x, v_y, -(p'_y * v_x))) the blocks of J^T W J and J^T W e are
+ *       trans x trans: W;   rot x trans: K, column j of K = x(p', column j of W);
+ *       rot x rot: row i of RR = x(p', row i of K), of which the entries j >= i are used;   J^T W e = (x(p', u), u).
+ *     (Deliberate difference: Open3D builds residual rows with W^(1/2); its normal equations are these same J^T Mc^-1 J and
+ *     J^T Mc^-1 e, without a matrix square root.)
+ *   Sums: 30 signed 64-bit integers, in cs_icp_plane_batch's layout: count; the 21 entries i <= j, row-major, of the 6 x 6
+ *     matrix [RR K; K^T W]; the 6 entries of (x(p', u), u); I(d2 * 2^s2); I(mc * 2^s), mc = fma(e_z, u_z, fma(e_y, u_y,
+ *     e_x * u_x)), the Mahalanobis cost.  I clamps to +-2^(61 - eN) and truncates.  With eW the smallest integer with
+ *     1 / (2 epsilon) <= 2^eW (-1 .. 9) and b = 61 - eN - eW the exponents are cs_icp_plane_batch's with that b: rot x rot
+ *     b - 2 eM - 3, rot x trans b - eM - 2, trans x trans b - 1, x(p', u) b - 2 eM - 2, u b - eM - 1, and mc shares
+ *     b - 2 eM - 2.  |p'_c| <= M, |p'| <= sqrt(3) M, |e| < max_dist <= M and |W|_2 <= 2^eW give |K_ij| < 2^(eM + 1 + eW),
+ *     |RR_ij| <= 3 M^2 2^eW < 2^(2 eM + 2 + eW), |u_i| < 2^(eM + eW), |x(p', u)_i| < 2^(2 eM + 1 + eW), mc < 2^(2 eM + eW);
+ *     each class carries one bit for the roundings, so no term reaches the clamp and no sum leaves 2^61 -- for normals of
+ *     any length, since only their directions enter.  The clamp keeps the sums defined for any input.
+ *   Update: cs_icp_plane_batch's, the same code: A and b from the sums, A x = -b by the unpivoted Cholesky sequence, the
+ *     Cayley rotation of (x_0, x_1, x_2), t about o, T <- U T.
+ *   A problem stops at once, keeping T, when an evaluation has n_corr < 6 or a non-finite value, when a pivot d is not
+ *     finite or not greater than 2^-30 * A_jj, or when the update would make T non-finite.  The pivot floor is
+ *     cs_icp_plane_batch's, kept on purpose: A >= (1/2) G and A_jj <= G_jj / (2 epsilon) for the point-to-point normal
+ *     matrix G of the same pairs, so a pivot's share of its diagonal entry is at least epsilon (>= 2^-10) times the share
+ *     the geometry gives G, and the floor only cuts geometry shares below 2^-20; a translational A_jj is at least n / 2 and
+ *     is carried to n units of 2^-(60 - eN - eW), relative 2^-(59 - eN - eW), which stays 2^7 below the floor for segments
+ *     of up to 2^13 sources at the smallest epsilon.  A single plane is NOT singular here: in the plane's
+ *     directions the pairs pull with weight 1/2 like a point-to-point estimation, so the pivot rule does not fire and the
+ *     problem runs to its criteria.
+ *   d_mrmse = sqrt(sm / n_corr), sm = (double)sum_mc * 2^-s, of the last evaluation; 0 when n_corr = 0 or sm <= 0
+ *     ([O3D-knowledge] Open3D's ComputeRMSE of this estimation).  It takes no part in the stop criteria.
+ *   Refused (CS_ERR_INVALID) in addition to what cs_icp_plane_batch refuses: a NULL d_src_normal while a source row exists;
+ *     epsilon not finite or outside [2^-10, 1] (Open3D's default 1e-3 is inside; epsilon = 1 makes every W = I / 2).
+ *   Robust kernels and a scale are out of scope for this estimation.
+ * Profile family "icp".
+ * ---------------------------------------------------------------------------------------- */
+int cs_icp_gicp_batch(const float* d_src, const float* d_src_normal, const int64_t* h_soff, const float* d_tgt,
+                      const float* d_tgt_normal, const int64_t* h_toff, const int32_t* h_src_seg, const int32_t* h_tgt_seg,
+                      int n_prob, const float* d_T0, double max_dist, int max_iter, double relative_fitness,
+                      double relative_rmse, double epsilon, double* d_T, float* d_T32, double* d_fitness, double* d_rmse,
+                      double* d_mrmse, int32_t* d_iters, int32_t* d_ncorr, int32_t* d_corr, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * cs_estimate_normals: one surface normal per row from the k nearest rows of the row's own segment, the semantics of
  * [O3D-knowledge] Open3D's PointCloud::estimate_normals(KDTreeSearchParamKNN(k)): the eigenvector of the smallest
  * eigenvalue of the neighbourhood's covariance.  The reference has no such step, so this comment is the specification
