@@ -1,4 +1,4 @@
-// The rigid-fit eigen-solvers shared by the RANSAC's hypothesis kernel (ransac_hyp.hip) and the ICP's update (icp.hip): the
+// The rigid-fit eigen-solvers shared by the RANSAC's hypothesis kernel (ransac_hyp.hip) and the ICP's update (icp_step.hip): the
 // largest eigenpair of Horn's 4x4 matrix from its characteristic polynomial (horn_qcp), with the cyclic Jacobi solver
 // (jacobi4) as the fallback of the lanes it does not accept.  oracle/corsair_oracle.c (oc_horn_qcp / oc_jacobi4) and
 // tests/icp_ref.py restate both operation sequences.  jacobi3 is jacobi4's 3x3 sibling for the scatter matrices of

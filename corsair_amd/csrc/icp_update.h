@@ -1,4 +1,4 @@
-// The small-pose update shared by the plane ICP (icp.hip) and Fast Global Registration (fgr.hip): the rotation of a
+// The small-pose update shared by the plane ICP (icp_step.hip) and Fast Global Registration (fgr.hip): the rotation of a
 // quaternion normalised by division, the chain T <- U T, and the unpivoted Cholesky solve of the normal equations with its
 // pivot rule.  One lane per problem runs these; every operation is ONE IEEE f64 operation unless an fma is written.
 #pragma once

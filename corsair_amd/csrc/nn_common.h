@@ -1,6 +1,6 @@
-// What knn.hip, topk.hip, chamfer.hip, hardneg.hip and icp.hip share: the matrix-core operand types, the f16 hi / lo cut, the host
-// helpers of their drivers, and the two kernels that two of them launch (each defined once, in one unit, and
-// reached from the other through an ordinary host function).
+// What knn.hip, topk.hip, chamfer.hip, hardneg.hip and two ICP units (icp_assoc.hip: the kernels' side, icp.hip: the driver's)
+// share: the matrix-core operand types, the f16 hi / lo cut, the host helpers of their drivers, and the two kernels that two
+// of them launch (each defined once, in one unit, and reached from the other through an ordinary host function).
 #pragma once
 #include <stdlib.h>
 
@@ -178,7 +178,7 @@ inline bool env_first_is(const char* name, char c) {
   return e && e[0] == c;
 }
 
-// The f16 image of 3-d target rows that k_chamfer_f16 (chamfer.hip) and k_icp_f16 (icp.hip) rank on: row j =
+// The f16 image of 3-d target rows that k_chamfer_f16 (chamfer.hip) and k_icp_f16 (icp_assoc.hip) rank on: row j =
 // [th(3) | tl(3) | th(3) | 0] of the coordinates scaled by CHF_SCALE, tn32[j] = |S t|^2, t4f[j] = (x, y, z, 0).
 constexpr int CHF_PITCH = 24;     // halfs per image row (48 B: conflict-free ds_read_b128 fragments)
 constexpr int CHF_ROWS = 256;     // target rows per LDS stage (8 MFMA row tiles)

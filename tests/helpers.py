@@ -56,6 +56,36 @@ def rot_y_pose(deg, trans=(0.05, -0.02, 0.03)):
     return T
 
 
+# ---- the ICP units' source text ------------------------------------------------------------------
+ICP_UNITS = ("icp.h", "icp_sums.h", "icp_assoc.hip", "icp_step.hip", "icp.hip")
+ICP_KERNELS = ["k_icp_exact", "k_icp_f16", "k_icp_frame", "k_icp_init", "k_icp_step"]
+
+
+def icp_unit_texts():
+    """{file name: text} of the five files the batched ICP is made of (corsair_amd/csrc)."""
+    import os
+
+    from corsair_amd import _lib
+
+    csrc = os.path.join(os.path.dirname(os.path.abspath(_lib.__file__)), "csrc")
+    return {n: open(os.path.join(csrc, n)).read() for n in ICP_UNITS}
+
+
+def assert_five_icp_kernels():
+    """No estimation adds a kernel: over the ICP units together the kernel DEFINITIONS (not mentions in comments) are the five
+    of ICP_KERNELS, each once, the host unit has none, and the estimation is still a template argument of the sums and the
+    step."""
+    import re
+
+    units = icp_unit_texts()
+    text = "\n".join(units.values())
+    kernels = re.findall(r"^__global__ [^\n]*?void (k_\w+)\(", text, flags=re.M)
+    assert sorted(kernels) == ICP_KERNELS
+    assert text.count("__global__") == 5
+    assert "__global__" not in units["icp.hip"]
+    assert "icp_block_sums<EST>" in text and "k_icp_step<EST>" in text
+
+
 # ---- operator-level contract tests: column views of wider buffers ------------------------------------------
 # A quiet NaN whose payload no arithmetic produces: a buffer filled with it shows both a stray WRITE (the bits
 # change) and a stray READ (a NaN reaches the result).

@@ -194,15 +194,21 @@ def test_library_exports_header_and_shared_solver():
         text = f.read()
     for word in ("CS_ICP_F16", "CS_ICP_STATS", '"icp"', "[O3D-knowledge]"):
         assert word in text
-    # one definition of the eigen-solvers, included by both users
+    # one definition of the eigen-solvers, included by both users: the hypothesis unit of the RANSAC and the step unit of the ICP
+    from tests.helpers import ICP_UNITS, assert_five_icp_kernels, icp_unit_texts
+
     csrc = os.path.join(os.path.dirname(_lib.LIB_PATH))
     ransac_units = ("ransac.hip", "ransac_hyp.hip", "ransac_prefilter.hip", "ransac_count.hip", "ransac.h")
-    units = {n: open(os.path.join(csrc, n)).read() for n in ("horn.h", "icp.hip") + ransac_units}
+    units = {n: open(os.path.join(csrc, n)).read() for n in ("horn.h",) + ransac_units}
+    units.update(icp_unit_texts())
     for fn in ("bool horn_qcp(", "void jacobi4("):
         assert fn in units["horn.h"]
-        for n in ("icp.hip",) + ransac_units:
+        for n in ICP_UNITS + ransac_units:
             assert fn not in units[n], n
-    assert '#include "horn.h"' in units["ransac_hyp.hip"] and '#include "horn.h"' in units["icp.hip"]
+    assert '#include "horn.h"' in units["ransac_hyp.hip"] and '#include "horn.h"' in units["icp_step.hip"]
+    for n in ICP_UNITS:
+        assert n == "icp_step.hip" or '#include "horn.h"' not in units[n], n
+    assert_five_icp_kernels()
 
 
 def test_python_surface(tmp_path):

@@ -237,6 +237,6 @@ def test_surface_is_declared():
     assert "tgt_normals" in inspect.signature(B.icp_batch).parameters
     sig = inspect.signature(R.sym_pose_batch).parameters
     assert sig["icp_estimation"].default == "point" and sig["icp_normal_k"].default == 16 and sig["normals1"].default is None
-    unit = open(os.path.join(os.path.dirname(_lib.LIB_PATH), "icp.hip")).read()
-    assert unit.count("__global__") == 5          # frame, exact, f16, step, init: the plane path adds no kernel of its own
-    assert "icp_block_sums<EST>" in unit and "k_icp_step<EST>" in unit
+    from tests.helpers import assert_five_icp_kernels
+
+    assert_five_icp_kernels()          # frame, exact, f16, step, init: the plane path adds no kernel of its own

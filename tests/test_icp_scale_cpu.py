@@ -406,11 +406,9 @@ def test_refused_bounds_and_surface():
         with pytest.raises(ValueError, match="scale_bounds"):
             B.icp_batch(z, [0, 4], z, [0, 4], [0], [0], np.eye(4, dtype=np.float32)[None], 0.1, with_scaling=True,
                         scale_bounds=bad)
-    import re
+    from tests.helpers import assert_five_icp_kernels
 
-    unit = open(os.path.join(os.path.dirname(_lib.LIB_PATH), "icp.hip")).read()
-    kernels = re.findall(r"^__global__ [^\n]*?void (k_\w+)\(", unit, flags=re.M)    # definitions, not mentions in comments
-    assert sorted(kernels) == ["k_icp_exact", "k_icp_f16", "k_icp_frame", "k_icp_init", "k_icp_step"]   # no kernel was added
+    assert_five_icp_kernels()   # no kernel was added
 
 
 # ---- (f) the cache ------------------------------------------------------------------------------------------------------------

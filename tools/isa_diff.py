@@ -1,7 +1,11 @@
 """Per-kernel comparison of two sets of device ISA listings (`hipcc <flags of the object> --cuda-device-only -S`):
     tools/isa_diff.py old.s new.s
     tools/isa_diff.py old.s [old2.s ...] -- new.s [new2.s ...]     (a translation unit that was split or merged)
-Prints SAME / DIFF, the instruction counts and the mangled name of every function of either side.  Comments and assembler
+    tools/isa_diff.py --demangle ...     (functions and kernel metadata are keyed by the demangled name with
+                                          `(anonymous namespace)::` removed, not by the mangled one: a type or a function that
+                                          moved between a named and an anonymous namespace, which changes every mangled name
+                                          it appears in; needs c++filt)
+Prints SAME / DIFF, the instruction counts and the (mangled) name of every function of either side.  Comments and assembler
 directives are dropped and local labels normalised (.LBB<n>_<m>: <n> is the function's index in the file and shifts when a
 function is added or removed), so a refactor of host code or of other kernels must come out as SAME for a kernel it did not touch.
 A function is DIFF as well when it is missing on one side, defined more than once on one side (DUP), or when its kernel
@@ -9,6 +13,7 @@ metadata differ (registers, LDS, scratch, spills: META, with the two values).  T
 status is 1 unless everything is SAME."""
 import hashlib
 import re
+import subprocess
 import sys
 
 META = ("vgpr_count", "sgpr_count", "group_segment_fixed_size", "private_segment_fixed_size", "vgpr_spill_count",
@@ -62,13 +67,41 @@ def digest(body):
     return hashlib.sha1("\n".join(body).encode()).hexdigest() if body is not None else None
 
 
+def demangled(names):
+    """{mangled: demangled name without `(anonymous namespace)::`} through c++filt, one name per line.  DF16_ (_Float16) is
+    handed over as Dh (half), so a _Float16 parameter prints as `half`: a c++filt that does not know DF16_ yet leaves the
+    whole name mangled."""
+    names = sorted(names)
+    out = subprocess.run(["c++filt"], input="\n".join(n.replace("DF16_", "Dh") for n in names) + "\n", capture_output=True,
+                         text=True, check=True).stdout.splitlines()
+    assert len(out) == len(names), "c++filt answered %d lines for %d names" % (len(out), len(names))
+    return {n: d.replace("(anonymous namespace)::", "") for n, d in zip(names, out)}
+
+
+def rekey(body, dup, meta):
+    """the three tables of a side keyed by demangled(); two functions that now share a key are a DUP"""
+    key = demangled(set(body) | set(meta))
+    nbody, ndup = {}, {key[k] for k in dup}
+    for k, v in body.items():
+        if key[k] in nbody:
+            ndup.add(key[k])
+        nbody[key[k]] = v
+    return nbody, ndup, {key[k]: v for k, v in meta.items()}
+
+
 args = sys.argv[1:]
+demangle = "--demangle" in args
+if demangle:
+    args.remove("--demangle")
 if "--" in args:
     old, new = args[:args.index("--")], args[args.index("--") + 1:]
 else:
     old, new = args[:1], args[1:]
 a, adup, ameta = side(old)
 b, bdup, bmeta = side(new)
+if demangle:
+    a, adup, ameta = rekey(a, adup, ameta)
+    b, bdup, bmeta = rekey(b, bdup, bmeta)
 count = {}
 for k in sorted(set(a) | set(b)):
     verdict, note = "SAME", ""
