@@ -1,5 +1,5 @@
-// What knn.hip, topk.hip, chamfer.hip, hardneg.hip and two ICP units (icp_assoc.hip: the kernels' side, icp.hip: the driver's)
-// share: the matrix-core operand types, the f16 hi / lo cut, the host helpers of their drivers, and the two kernels that two
+// What the k-NN units (knn.h: knn.hip, knn_exact.hip, knn_f16.hip), topk.hip, chamfer.hip, hardneg.hip and two ICP units
+// (icp_assoc.hip: the kernels' side, icp.hip: the driver's) share: the matrix-core operand types, the f16 hi / lo cut, the host helpers of their drivers, and the two kernels that two
 // of them launch (each defined once, in one unit, and reached from the other through an ordinary host function).
 #pragma once
 #include <stdlib.h>
@@ -22,7 +22,7 @@ __device__ __forceinline__ void knf_split(float v, _Float16* hi, _Float16* lo) {
 }
 
 // ------------------------------------------------------------------------------------------
-// The f16 matrix-core shortlist scan of 16-d features, shared by k_knn_f16 (knn.hip) and k_hn_f16 (hardneg.hip):
+// The f16 matrix-core shortlist scan of 16-d features, shared by k_knn_f16 (knn_f16.hip) and k_hn_f16 (hardneg.hip):
 // operand rows, the LDS stage, the tile's fragments and MFMAs, the lane's ranked list and its threshold, the error
 // budget.  The kernels differ only in what they do with a value below the threshold.
 //   value v~ = f32(|t|^2) + sum of the 48 products th.(-2qh) + tl.(-2qh) + th.(-2ql), accumulated in f32 by three

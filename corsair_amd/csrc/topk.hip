@@ -15,7 +15,7 @@
 // loads the distance (k_row_topk), and a list that runs out of rows ends in (-1, +inf).  The f16 verification hands a
 // query or a catalog outside its range (|q|^2 >= 1e8, max |x|^2 >= 4e8, not finite; a NaN row does not enter the
 // maximum) to the f64 shortlist.
-// k_row_norms lives here; knn.hip reaches it through row_norms().
+// k_row_norms lives here, behind row_norms() (nn_common.h).
 #include <algorithm>
 
 

@@ -230,7 +230,7 @@ void cs_topk_catalog_free(cs_topk_catalog* catalog);
  * Output rows are problem-major (all rows of problem 0, then problem 1, ...):
  * d_idx int32 [sum_p nq_p, k] = target row index LOCAL to the target segment, -1 if fewer than k
  * candidates; d_dist f64 same shape, optional (Euclidean distance).
- * Non-finite rows (all three paths, labelled or not): a candidate whose canonical f64 squared distance is NaN or
+ * Non-finite rows (both paths, labelled or not): a candidate whose canonical f64 squared distance is NaN or
  * +inf is never a neighbour -- the results equal those of the same call with the non-finite target rows removed,
  * indices mapped back; the (-1, +inf) padding applies when fewer than k candidates at finite distance remain, and a
  * query row with a non-finite element gets k times (-1, +inf).  A non-finite row changes nothing outside itself:
@@ -244,8 +244,8 @@ int cs_knn_feat(const float* d_qf, const int64_t* h_qoff, const float* d_tf,
 /* Diagnostics of cs_knn_feat's default path for 16-d features (f16 matrix-core shortlist, canonical f64
  * re-evaluation, verification, exhaustive recomputation of what could not be verified): out =
  * {queries answered, of those recomputed exhaustively}, counted only while the environment variable
- * CS_KNN_STATS=1.  CS_KNN_MFMA=64 selects the f64 matrix-pipe shortlist, CS_KNN_MFMA=0 the exhaustive
- * all-VALU kernel; all three return the same indices and distances. */
+ * CS_KNN_STATS=1.  CS_KNN_MFMA=0 selects the exhaustive all-VALU kernel (any other value: the default path); both
+ * return the same indices and distances. */
 void cs_knn_shortlist_stats(uint64_t out[2], int reset);
 
 /* ------------------------------------------------------------------------------------------

@@ -86,6 +86,31 @@ def assert_five_icp_kernels():
     assert "icp_block_sums<EST>" in text and "k_icp_step<EST>" in text
 
 
+# ---- the k-NN units' source text -------------------------------------------------------------------------------
+KNN_UNITS = ("knn.h", "knn_exact.hip", "knn_f16.hip", "knn.hip")
+KNN_KERNELS = ["k_count_flags", "k_knf_pack_queries", "k_knf_pack_targets", "k_knn_f16", "k_knn_feat", "k_knn_rescore_f16",
+               "k_label_starts", "k_seg_keys"]
+
+
+def assert_eight_knn_kernels():
+    """cs_knn_feat has two paths and no third: over the k-NN units together the kernel DEFINITIONS (not mentions in comments)
+    are the eight of KNN_KERNELS, each once, the shared header has none, and the radix sort's library is included by one unit."""
+    import os
+    import re
+
+    from corsair_amd import _lib
+
+    csrc = os.path.join(os.path.dirname(os.path.abspath(_lib.__file__)), "csrc")
+    units = {n: open(os.path.join(csrc, n)).read() for n in KNN_UNITS}
+    text = "\n".join(units.values())
+    kernels = re.findall(r"^__global__ [^\n]*?void (k_\w+)\(", text, flags=re.M)
+    assert sorted(kernels) == KNN_KERNELS
+    assert text.count("__global__") == len(KNN_KERNELS)
+    assert "__global__" not in units["knn.h"]
+    assert [n for n in KNN_UNITS if re.search(r"^\s*#\s*include\s*<hipcub", units[n], flags=re.M)] == ["knn_f16.hip"]
+    assert "hipcub" not in "".join(units[n] for n in KNN_UNITS if n != "knn_f16.hip")
+
+
 # ---- operator-level contract tests: column views of wider buffers ------------------------------------------
 # A quiet NaN whose payload no arithmetic produces: a buffer filled with it shows both a stray WRITE (the bits
 # change) and a stray READ (a NaN reaches the result).

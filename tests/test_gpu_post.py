@@ -47,11 +47,11 @@ def test_l2_topk_bit_exact_vs_oracle(gpu, oracle_native, nq, nx, d, k):
     assert np.array_equal(dist.cpu().numpy(), np.sqrt(np.take_along_axis(d2, want, 1)))
 
 
-@pytest.mark.parametrize("mfma", ["1", "64", "0"])
+@pytest.mark.parametrize("mfma", ["1", "0"])
 def test_knn_feat_bit_exact(gpu, oracle_native, monkeypatch, mfma):
-    """All three code paths return the oracle's indices and distances: the f16 matrix-core shortlist with
-    canonical rescore + verification (default for 16-d features), the f64 matrix-pipe shortlist
-    (CS_KNN_MFMA=64) and the exhaustive all-VALU kernel (CS_KNN_MFMA=0)."""
+    """Both code paths return the oracle's indices and distances: the f16 matrix-core shortlist with
+    canonical rescore + verification (default for 16-d features) and the exhaustive all-VALU kernel
+    (CS_KNN_MFMA=0)."""
     from corsair_amd import backend as B
 
     monkeypatch.setenv("CS_KNN_MFMA", mfma)
@@ -118,6 +118,33 @@ def test_knn_f16_shortlist_falls_back_on_ties(gpu, oracle_native, monkeypatch):
     assert np.array_equal(dist.cpu().numpy(), wd)
     assert np.array_equal(wi[3], np.sort(dup)[:5])           # the tie rule is what decides query 3
     assert int(st[0]) == nq and 1 <= int(st[1]) < nq // 4    # some, not most, went through the fallback
+
+
+def test_knn_mfma_64_is_the_f16_path(gpu, monkeypatch):
+    """CS_KNN_MFMA has two meanings: a value that begins with 0 is the exhaustive kernel, anything else -- 64, once a path of
+    its own, included -- the default f16 shortlist.  65 queries x 193 targets: one row past a 64-lane wave and one past the
+    192-row LDS stage."""
+    import ctypes
+
+    from corsair_amd import _lib, backend as B
+
+    rng = np.random.default_rng(65193)
+    nq, nt = 65, 193
+    Q = torch.from_numpy(_feat(rng, nq)).to(gpu)
+    T = torch.from_numpy(_feat(rng, nt)).to(gpu)
+    monkeypatch.setenv("CS_KNN_STATS", "1")
+    st = (ctypes.c_uint64 * 2)()
+    monkeypatch.setenv("CS_KNN_MFMA", "64")
+    _lib.load().cs_knn_shortlist_stats(st, 1)
+    idx, dist = B.knn_feat(Q, [0, nq], T, [0, nt], 5, return_distance=True)
+    _lib.load().cs_knn_shortlist_stats(st, 1)
+    assert int(st[0]) == nq                                  # every query was answered by the f16 path
+    monkeypatch.setenv("CS_KNN_MFMA", "0")
+    widx, wdist = B.knn_feat(Q, [0, nq], T, [0, nt], 5, return_distance=True)
+    _lib.load().cs_knn_shortlist_stats(st, 0)
+    assert int(st[0]) == 0                                   # ... and none of them under CS_KNN_MFMA=0
+    assert np.array_equal(idx.cpu().numpy(), widx.cpu().numpy())
+    assert np.array_equal(dist.cpu().numpy().view(np.int64), wdist.cpu().numpy().view(np.int64))
 
 
 @pytest.mark.parametrize("path", ["f16", "f64", "valu"])

@@ -46,7 +46,7 @@ def test_knn_f16_path_equals_exhaustive_on_ragged_labelled_problems(gpu, monkeyp
         for labelled in (False, True):
             monkeypatch.setenv("CS_KNN_MFMA", "0")
             wi, wd = run(k, labelled)
-            for mode in ("1", "64"):
+            for mode in ("1",):
                 monkeypatch.setenv("CS_KNN_MFMA", mode)
                 gi, gd = run(k, labelled)
                 assert torch.equal(gi, wi), (k, labelled, mode)
