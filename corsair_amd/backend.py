@@ -499,6 +499,54 @@ def hausdorff_1dir(src, soff, tgt, toff, src_seg, tgt_seg, T):
     return out
 
 
+def _packed_points(xyz, offsets, who):
+    xyz = _dev(xyz, torch.float32, "points").contiguous()
+    if xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise ValueError("%s: points must be [n, 3]" % who)
+    if len(offsets) < 1 or int(offsets[-1]) > xyz.shape[0]:
+        raise ValueError("%s: the offset table exceeds the point array" % who)
+    return xyz
+
+
+def orient_normals(xyz, offsets, normals, view=None, away=True):
+    """cs_orient_normals, IN PLACE on `normals` (f32 [n,3] device, contiguous): every normal is flipped to point away from
+    (away=True) or towards the view point of its segment -- view f64 [n_seg,3] (host or device), or None for the segment's
+    centroid (an exact fixed-point sum: a permuted segment gives the same bits).  The semantics are the header comment of
+    cs_orient_normals.  Returns `normals`.  No host wait."""
+    xyz = _packed_points(xyz, offsets, "orient_normals")
+    if normals.dtype != torch.float32 or normals.shape != xyz.shape or not normals.is_contiguous() or \
+            normals.device != xyz.device:
+        raise ValueError("orient_normals: normals must be a contiguous f32 tensor of the points' shape and device")
+    if view is not None:
+        view = torch.as_tensor(view, dtype=torch.float64).to(xyz.device).contiguous()
+        if tuple(view.shape) != (len(offsets) - 1, 3):
+            raise ValueError("orient_normals: view must be [n_seg, 3]")
+    check(_lib.load().cs_orient_normals(ptr(xyz), i64_array(offsets), len(offsets) - 1, ptr(view), 1 if away else 0,
+                                        ptr(normals), stream_ptr()))
+    return normals
+
+
+def fpfh(xyz, offsets, normals, radius, max_nn=100):
+    """cs_fpfh: Fast Point Feature Histograms, f32 [n,33] device, of packed clouds (host offset list) with ORIENTED normals
+    (orient_normals), from the at most max_nn - 1 nearest other rows strictly inside `radius`; 4 <= max_nn <= 128.  The
+    semantics are the header comment of cs_fpfh.  No host wait."""
+    xyz = _packed_points(xyz, offsets, "fpfh")
+    normals = _dev(normals, torch.float32, "normals").contiguous()
+    if normals.shape != xyz.shape:
+        raise ValueError("fpfh: normals must have the shape of the points")
+    out = torch.zeros((xyz.shape[0], 33), dtype=torch.float32, device=xyz.device)
+    check(_lib.load().cs_fpfh(ptr(xyz), ptr(normals), i64_array(offsets), len(offsets) - 1, float(radius), int(max_nn),
+                              ptr(out), stream_ptr()))
+    return out
+
+
+def fpfh_stats(reset=False):
+    """cs_fpfh_stats: (neighbours found, rows whose on-chip list was ranked in parts); counts only under CS_FPFH_STATS=1."""
+    out = (ctypes.c_uint64 * 2)()
+    _lib.load().cs_fpfh_stats(out, 1 if reset else 0)
+    return int(out[0]), int(out[1])
+
+
 class IcpResult(NamedTuple):
     T: torch.Tensor          # f64 [n_prob,4,4]
     T32: torch.Tensor        # f32 [n_prob,4,4], T cast once

@@ -29,6 +29,20 @@ struct CellTable {
   uint64_t mask;
 };
 
+// The [beg, end) range of the sorted rows of cell (x, y, z) of problem p; false when the cell holds no row or lies outside
+// the key range.  cg_probe's lookup, also for callers that walk a cell's rows themselves (fpfh.hip: a wave per query).
+__device__ __forceinline__ bool cg_lookup(const CellTable& tb, int p, int x, int y, int z, int32_t& beg, int32_t& end) {
+  if (x < -32767 || x > 32767 || y < -32767 || y > 32767 || z < -32767 || z > 32767) return false;
+  const uint64_t key = pack_key(p, x, y, z);
+  uint64_t slot = hash64(key) & tb.mask;
+  uint64_t k;
+  while ((k = tb.keys[slot]) != key && k != kEmptyKey) slot = (slot + 1) & tb.mask;
+  if (k != key) return false;
+  beg = tb.beg[slot];
+  end = tb.end[slot];
+  return true;
+}
+
 // Calls f(d2, m) for every sorted row m of problem p in the 27 cells around (qx, qy, qz) with d2 < r2, in no particular
 // order.  rows = the sorted coordinates, STRIDE values of T per row; d2_of(t) is the caller's distance chain from the
 // query to the row at t (pairs.hip and normals.hip each keep their own).  NaN and, for a finite r2, inf never pass.
@@ -40,14 +54,9 @@ __device__ __forceinline__ void cg_probe(const CellTable& tb, const T* __restric
     for (int dy = -1; dy <= 1; ++dy)
       for (int dx = -1; dx <= 1; ++dx) {
         const int x = cx + dx, y = cy + dy, z = cz + dz;
-        if (x < -32767 || x > 32767 || y < -32767 || y > 32767 || z < -32767 || z > 32767) continue;
-        const uint64_t key = pack_key(p, x, y, z);
-        uint64_t slot = hash64(key) & tb.mask;
-        uint64_t k;
-        while ((k = tb.keys[slot]) != key && k != kEmptyKey) slot = (slot + 1) & tb.mask;
-        if (k != key) continue;
-        const int32_t e = tb.end[slot];
-        for (int32_t m = tb.beg[slot]; m < e; ++m) {
+        int32_t b, e;
+        if (!cg_lookup(tb, p, x, y, z, b, e)) continue;
+        for (int32_t m = b; m < e; ++m) {
           const double d2 = d2_of(rows + (int64_t)STRIDE * m);
           if (d2 < r2) f(d2, m);
         }

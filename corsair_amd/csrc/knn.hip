@@ -10,7 +10,7 @@
 //     canonical chain, ranks it and VERIFIES it against the shortlist threshold; the queries that fail are recomputed by
 //     k_knn_feat<16> (flagged tiles only).  CS_KNN_TWOPASS=0 drops the threshold pass; CS_KNN_STATS=1 counts the
 //     recomputed queries (cs_knn_shortlist_stats; synchronises).
-//   * CS_KNN_MFMA=0, and every other shape (3-d, 32-d, k = 7 / 8; knn_exact.hip): k_knn_feat<DIM>, exhaustive on the
+//   * CS_KNN_MFMA=0, and every other shape (3-d, 32-d, 33-d, k = 7 / 8; knn_exact.hip): k_knn_feat<DIM>, exhaustive on the
 //     VALU -- the fallback of the f16 path and what the tests hold it against.
 // Non-finite rows (include/corsair_hip.h): a candidate whose canonical distance is NaN or +inf is never a neighbour.  Every
 // insertion test is a strict `<` against a list that starts at +inf, the tile minima are fminf / v_min3 (a NaN operand
@@ -69,8 +69,8 @@ int cs_knn_feat(const float* d_qf, const int64_t* h_qoff, const float* d_tf,
              "cs_knn_feat: NULL argument");
   CS_REQUIRE(k >= 1 && k <= KNN_MAXK, CS_ERR_UNSUPPORTED, "cs_knn_feat: k = %d not in [1, %d]", k,
              KNN_MAXK);
-  CS_REQUIRE(dim == 16 || dim == 32 || dim == 3, CS_ERR_UNSUPPORTED,
-             "cs_knn_feat: feature dimension %d not supported (3, 16, 32)", dim);
+  CS_REQUIRE(dim == 16 || dim == 32 || dim == 33 || dim == 3, CS_ERR_UNSUPPORTED,
+             "cs_knn_feat: feature dimension %d not supported (3, 16, 32, 33)", dim);
   CS_REQUIRE((d_qlabel == nullptr) == (d_tlabel == nullptr) &&
                  (d_qlabel == nullptr) == (d_perm == nullptr),
              CS_ERR_INVALID, "cs_knn_feat: labels and perm must be given together");
@@ -123,7 +123,7 @@ int cs_knn_feat(const float* d_qf, const int64_t* h_qoff, const float* d_tf,
     }
     return rc16;
   }
-  // CS_KNN_MFMA=0, and every shape the shortlist does not take (3-d, 32-d, k > 6): the exhaustive VALU kernel
+  // CS_KNN_MFMA=0, and every shape the shortlist does not take (3-d, 32-d, 33-d, k > 6): the exhaustive VALU kernel
   ProfScope prof("knn", s, knn_flop);
   knn_exact_launch(call, nullptr, nullptr);
   CS_LAUNCH_CHECK();

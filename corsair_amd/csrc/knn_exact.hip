@@ -1,5 +1,5 @@
 // The exhaustive feature k-NN kernel: every target row gets the canonical evaluation (knn.hip: the contract).  It is the
-// whole of cs_knn_feat for 3-d and 32-d features, k = 7 / 8 and CS_KNN_MFMA=0, the fallback of the f16 shortlist path
+// whole of cs_knn_feat for 3-d, 32-d and 33-d (FPFH) features, k = 7 / 8 and CS_KNN_MFMA=0, the fallback of the f16 shortlist path
 // (knn_f16.hip: flagged tiles only), and what the tests hold that path against.
 #include "knn.h"
 
@@ -112,6 +112,7 @@ static void launch(const KnnCall& c, const int32_t* tile_flag, const int32_t* qf
 void knn_exact_launch(const KnnCall& c, const int32_t* tile_flag, const int32_t* qflag) {
   if (c.dim == 16) launch<16>(c, tile_flag, qflag);
   else if (c.dim == 32) launch<32>(c, tile_flag, qflag);
+  else if (c.dim == 33) launch<33>(c, tile_flag, qflag);
   else launch<3>(c, tile_flag, qflag);
 }
 

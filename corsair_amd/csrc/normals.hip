@@ -17,6 +17,7 @@
 #include "cellgrid.h"
 #include "horn.h"
 #include "nn_common.h"
+#include "normals_grid.h"
 
 namespace cs {
 namespace {
@@ -28,12 +29,6 @@ struct NrmWork {
   int64_t seg0;   // first row of the segment (global)
   int32_t sn;     // rows of the segment
   int32_t r0;     // first row of this workgroup, local to the segment
-};
-
-// what the grid kernels know of a chunk segment (written on the device: no host wait)
-struct NrmSeg {
-  double cell;   // cell size; 0 = the segment is not on the grid (the exhaustive kernel answers it)
-  double r2;     // the probe's strict bound on d2: radius^2 (hybrid), the covered distance squared (k-NN)
 };
 
 // Everything after the neighbour list, for cs_estimate_normals and cs_estimate_normals_hybrid alike: the scatter matrix
@@ -451,8 +446,6 @@ __global__ __launch_bounds__(64) void k_normals_redo(const int32_t* __restrict__
   }
 }
 
-constexpr int NRM_CHUNK_SEGS = 65535;        // chunk segments 0..65534: (65535, 32767, 32767, 32767) is kEmptyKey
-constexpr int64_t NRM_CHUNK_ROWS = 1LL << 30;   // rows of a chunk of more than one segment; one segment (< 2^31) is a chunk
 // A segment of fewer rows than this goes to the exhaustive kernel: the sort, the table and the scattered probe cannot pay
 // where the scan reads the segment from one LDS stage (hybrid) or from two (k-NN, whose cells are 1.5 times wider and
 // whose unvouched rows cost a second scan).  Choices by the kernels' shapes; they have not been tuned.
@@ -491,38 +484,20 @@ int grid_chunk(bool knn, const float* d_xyz, const int64_t* h_off, int n_seg, in
                float* d_normal, unsigned long long* d_stats, hipStream_t s) {
   const char* who = knn ? "cs_estimate_normals: scratch allocation failed"
                         : "cs_estimate_normals_hybrid: scratch allocation failed";
-  const int64_t m_total = h_off[n_seg] - h_off[0];
-  PoolBuf<int64_t> doff;
-  int rc = upload(doff, std::vector<int64_t>(h_off, h_off + n_seg + 1), s);
+  NrmGrid gr;
+  int rc = nrm_grid_build(gr, d_xyz, h_off, n_seg, grid_min, knn ? k : 0, cell, r2, s, who);
   if (rc) return rc;
-  uint64_t cap = 1024;
-  while (cap < (uint64_t)(2 * m_total)) cap <<= 1;
-  PoolBuf<NrmSeg> segs(n_seg);
-  PoolBuf<uint64_t> keys(m_total), skeys(m_total), tkeys(cap);
-  PoolBuf<int32_t> vals(m_total), svals(m_total), sj(m_total), tbeg(cap), tend(cap), redo(knn ? m_total : 1);
-  PoolBuf<float> sxyz(3 * (size_t)m_total);
+  const int64_t m_total = gr.m_total;
+  PoolBuf<int32_t> redo(knn ? m_total : 1);
   PoolBuf<unsigned> redo_count(1);
-  CS_REQUIRE(segs.p && keys.p && skeys.p && tkeys.p && vals.p && svals.p && sj.p && tbeg.p && tend.p && redo.p && sxyz.p &&
-                 redo_count.p,
-             CS_ERR_HIP, "%s", who);
+  CS_REQUIRE(redo.p && redo_count.p, CS_ERR_HIP, "%s", who);
   CS_HIP_CHECK(hipMemsetAsync(redo_count.p, 0, sizeof(unsigned), s));
-  const unsigned g = (unsigned)ceil_div(m_total, 256);
-  cellgrid_table_fill(tkeys.p, cap, s);
-  hipLaunchKernelGGL(k_nrm_segs, dim3((unsigned)n_seg), dim3(256), 0, s, d_xyz, doff.p, grid_min, knn ? k : 0, cell, r2,
-                     segs.p);
-  hipLaunchKernelGGL(k_nrm_keys, dim3(g), dim3(256), 0, s, d_xyz, doff.p, n_seg, m_total, segs.p, keys.p, vals.p);
-  CS_LAUNCH_CHECK();
-  size_t tmp_bytes = 0;
-  CS_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys.p, skeys.p, vals.p, svals.p, (int)m_total, 0,
-                                                  64, s));
-  PoolBuf<char> tmp(tmp_bytes);
-  CS_REQUIRE(tmp.p, CS_ERR_HIP, "%s", who);
-  CS_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp.p, tmp_bytes, keys.p, skeys.p, vals.p, svals.p, (int)m_total, 0, 64,
-                                                  s));
-  hipLaunchKernelGGL(k_nrm_gather, dim3(g), dim3(256), 0, s, d_xyz, doff.p, skeys.p, svals.p, m_total, sxyz.p, sj.p);
-  cellgrid_insert_ranges(skeys.p, m_total, tkeys.p, tbeg.p, tend.p, cap - 1, s);
-  CS_LAUNCH_CHECK();
-  const CellTable tb{tkeys.p, tbeg.p, tend.p, cap - 1};
+  const CellTable tb = gr.table();
+  PoolBuf<float>& sxyz = gr.sxyz;
+  PoolBuf<int32_t>& sj = gr.sj;
+  PoolBuf<uint64_t>& skeys = gr.skeys;
+  PoolBuf<int64_t>& doff = gr.doff;
+  PoolBuf<NrmSeg>& segs = gr.segs;
 #define NRM_GRID(KC)                                                                                                      \
   (knn ? launch_grid<KC, true>(tb, sxyz.p, sj.p, skeys.p, m_total, d_xyz, doff.p, segs.p, k, d_normal, redo.p,            \
                                redo_count.p, d_stats, s)                                                                  \
@@ -578,6 +553,48 @@ int grid_chunks(bool knn, const float* d_xyz, const int64_t* h_off, int n_seg, i
 }
 
 }  // namespace
+
+int nrm_grid_build(NrmGrid& gr, const float* d_xyz, const int64_t* h_off, int n_seg, int grid_min, int k, double cell,
+                   double r2, hipStream_t s, const char* who) {
+  const int64_t m_total = h_off[n_seg] - h_off[0];
+  gr.m_total = m_total;
+  int rc = upload(gr.doff, std::vector<int64_t>(h_off, h_off + n_seg + 1), s);
+  if (rc) return rc;
+  uint64_t cap = 1024;
+  while (cap < (uint64_t)(2 * m_total)) cap <<= 1;
+  gr.cap = cap;
+  PoolBuf<uint64_t> keys(m_total);
+  PoolBuf<int32_t> vals(m_total), svals(m_total);
+  gr.segs.alloc(n_seg);
+  gr.skeys.alloc(m_total);
+  gr.tkeys.alloc(cap);
+  gr.sj.alloc(m_total);
+  gr.tbeg.alloc(cap);
+  gr.tend.alloc(cap);
+  gr.sxyz.alloc(3 * (size_t)m_total);
+  CS_REQUIRE(gr.segs.p && keys.p && gr.skeys.p && gr.tkeys.p && vals.p && svals.p && gr.sj.p && gr.tbeg.p && gr.tend.p &&
+                 gr.sxyz.p,
+             CS_ERR_HIP, "%s", who);
+  const unsigned g = (unsigned)ceil_div(m_total, 256);
+  cellgrid_table_fill(gr.tkeys.p, cap, s);
+  hipLaunchKernelGGL(k_nrm_segs, dim3((unsigned)n_seg), dim3(256), 0, s, d_xyz, gr.doff.p, grid_min, k, cell, r2,
+                     gr.segs.p);
+  hipLaunchKernelGGL(k_nrm_keys, dim3(g), dim3(256), 0, s, d_xyz, gr.doff.p, n_seg, m_total, gr.segs.p, keys.p, vals.p);
+  CS_LAUNCH_CHECK();
+  size_t tmp_bytes = 0;
+  CS_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys.p, gr.skeys.p, vals.p, svals.p, (int)m_total, 0,
+                                                  64, s));
+  PoolBuf<char> tmp(tmp_bytes);
+  CS_REQUIRE(tmp.p, CS_ERR_HIP, "%s", who);
+  CS_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp.p, tmp_bytes, keys.p, gr.skeys.p, vals.p, svals.p, (int)m_total, 0,
+                                                  64, s));
+  hipLaunchKernelGGL(k_nrm_gather, dim3(g), dim3(256), 0, s, d_xyz, gr.doff.p, gr.skeys.p, svals.p, m_total, gr.sxyz.p,
+                     gr.sj.p);
+  cellgrid_insert_ranges(gr.skeys.p, m_total, gr.tkeys.p, gr.tbeg.p, gr.tend.p, cap - 1, s);
+  CS_LAUNCH_CHECK();
+  return CS_OK;
+}
+
 }  // namespace cs
 
 using namespace cs;

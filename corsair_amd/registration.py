@@ -189,6 +189,9 @@ def _sym_pose_batch(estimator, baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_
                          % (icp_normal_radius,))
     if icp_max_iter > 0 and not (icp_max_dist is not None and icp_max_dist > 0):
         raise ValueError("sym_pose_batch: icp_max_iter > 0 needs a positive icp_max_dist")
+    if use_symmetry and baseF.shape[1] not in (16, 32):
+        raise ValueError("sym_pose_batch: use_symmetry needs 16- or 32-wide descriptors (cs_symcut_fit), got %d columns; "
+                         "FPFH descriptors (33) register with use_symmetry=False" % (baseF.shape[1],))
     dev = baseF.device
     P = len(off0) - 1
     off0 = [int(v) for v in off0]
@@ -431,7 +434,9 @@ def sym_pose_batch(*args, registration="ransac", fgr_mu_floor=0.025, fgr_iterati
     f32 [N0,3] in the query's own frame, else cs_estimate_normals over the query voxels with the same icp_normal_k /
     icp_normal_radius.  gicp_epsilon in [2^-10, 1] is the covariance floor along the normal (Open3D's default; untuned here,
     as is icp_normal_k for this estimation).  normals0 (default None) and gicp_epsilon (default 1e-3) are accepted by keyword
-    only, like the fgr_* options, and are taken out of **kwargs here.  icp_mrmse is filled too.  A robust icp_kernel or icp_with_scaling with "gicp" is out of scope and refused."""
+    only, like the fgr_* options, and are taken out of **kwargs here.  icp_mrmse is filled too.  A robust icp_kernel or icp_with_scaling with "gicp" is out of scope and refused.
+    Descriptors of another width (fpfh_features: 33 columns) register with use_symmetry=False; with use_symmetry the part
+    cut takes 16 or 32 columns and anything else is refused with ValueError before any launch."""
     if registration not in ("ransac", "fgr"):
         raise ValueError("sym_pose_batch: registration must be 'ransac' or 'fgr', got %r" % (registration,))
     normals0, gicp_epsilon = kwargs.pop("normals0", None), kwargs.pop("gicp_epsilon", 1e-3)
@@ -441,3 +446,14 @@ def sym_pose_batch(*args, registration="ransac", fgr_mu_floor=0.025, fgr_iterati
 
 # the positional interface (everything but the keyword-only estimator options), as introspection has always shown it
 sym_pose_batch.__signature__ = inspect.Signature(list(inspect.signature(_sym_pose_batch).parameters.values())[1:])
+
+
+def fpfh_features(xyz, offsets, radius, max_nn=100, normal_radius=None, normal_k=16):
+    """Fast Point Feature Histograms of packed clouds, the descriptor that needs no weights: normals
+    (backend.estimate_normals over normal_k neighbours, inside normal_radius when one is given), oriented away from each
+    cloud's centroid (backend.orient_normals: cs_estimate_normals' sign rule depends on the pose and FPFH is not invariant to a
+    flipped normal), then backend.fpfh at `radius` / `max_nn`.  xyz f32 [n,3] device, offsets a host list.  Returns
+    (features f32 [n,33], normals f32 [n,3]); the features go to sym_pose_batch with use_symmetry=False.  No host wait."""
+    normals = B.estimate_normals(xyz, offsets, normal_k, normal_radius)
+    B.orient_normals(xyz, offsets, normals, None, True)
+    return B.fpfh(xyz, offsets, normals, radius, max_nn), normals

@@ -57,6 +57,12 @@ class Config:
     # the correspondence estimator: "ransac" or "fgr" (cs_fgr_batch); fgr_mu_floor is UNTUNED, as in harness.Config
     registration: str = "ransac"
     fgr_mu_floor: float = 0.025
+    # the descriptors: "network" (the ResUNet forward, needs a checkpoint) or "fpfh" (registration.fpfh_features: no weights;
+    # sym_pose_batch then runs with use_symmetry=False, the part cut takes the network's widths only).  fpfh_radius is in
+    # VOXELS, 5 is Open3D's example value, UNTUNED; fpfh_max_nn is cs_fpfh's max_nn
+    features: str = "network"
+    fpfh_radius: float = 5.0
+    fpfh_max_nn: int = 100
 
     def icp_distance(self):
         return self.icp_max_dist if self.icp_max_dist > 0 else 2.0 * self.voxel_size
@@ -69,6 +75,30 @@ class Config:
             raise ValueError("Config.icp_normal_radius must be finite and >= 0 (0 = k-NN), got %r"
                              % (self.icp_normal_radius,))
         return float(self.icp_normal_radius) if self.icp_normal_radius > 0 else None
+
+
+class FpfhPipe:
+    """Stands where harness.Pipeline stands in `evaluate` when Config.features = "fpfh": the same `device` / `embed_groups`
+    surface, voxelisation and cs_fpfh descriptors (normals over 16 neighbours, oriented away from each cloud's centroid) in
+    the place of the forward.  No weights, no global descriptors."""
+
+    def __init__(self, device="cuda", radius_voxels=5.0, max_nn=100):
+        self.device = torch.device(device)
+        self.radius_voxels = float(radius_voxels)
+        self.max_nn = int(max_nn)
+
+    def embed_groups(self, groups, voxel_size):
+        from .harness import EmbeddedSet
+
+        origins, out_off = [], [0]
+        for xyz, offsets in groups:
+            keep, _, off = B.voxelize(xyz, offsets, voxel_size)
+            origins.append(xyz[keep].to(torch.float32))
+            out_off += [out_off[-1] + int(o) for o in off[1:]]
+        origin = torch.cat(origins).contiguous()
+        F, normal = R.fpfh_features(origin, out_off, self.radius_voxels * voxel_size, self.max_nn)
+        return EmbeddedSet(F, origin, out_off, torch.zeros((len(out_off) - 1, 0), dtype=torch.float32, device=origin.device),
+                           normal)
 
 
 def load_pc(pc):
@@ -150,8 +180,15 @@ def evaluate(pipe, clouds, cfg=None, pairs_per_batch=16, seed=None, force_gate=F
     rre_icp, chamfer_dist_icp and icp_iters of the refined pose.  cfg.max_log_scale > 0: the posed copy is s R x + t with
     s = exp(u); the result keys do not change for that alone.  cfg.icp_with_scaling: T_est_icp is a similarity, rte_icp / rre_icp are
     eval_pose's on it with its 3x3 block divided by the fitted scale, and the results gain scale_gt, scale_icp and
-    scale_err_icp = |scale_icp / scale_gt - 1|."""
+    scale_err_icp = |scale_icp / scale_gt - 1|.  cfg.features = "fpfh": the descriptors are cs_fpfh's (FpfhPipe; `pipe` may
+    be None, no checkpoint is needed) and the registration runs without the symmetry hypotheses, so the *_sym entries equal
+    the *_ransac ones; the result keys do not change."""
     cfg = cfg or Config()
+    if cfg.features not in ("network", "fpfh"):
+        raise ValueError("Config.features must be 'network' or 'fpfh', got %r" % (cfg.features,))
+    fpfh_on = cfg.features == "fpfh"
+    if fpfh_on:
+        pipe = FpfhPipe("cuda" if pipe is None else pipe.device, cfg.fpfh_radius, cfg.fpfh_max_nn)
     icp_on = cfg.icp_max_iter > 0
     scale_on = bool(cfg.icp_with_scaling)
     if scale_on and not icp_on:
@@ -191,7 +228,7 @@ def evaluate(pipe, clouds, cfg=None, pairs_per_batch=16, seed=None, force_gate=F
         res = R.sym_pose_batch(base.F, base.origin, base.offsets, posed.F, posed.origin, posed.offsets,
                                labels, cfg.k_nn, cfg.max_corr, 0,
                                [(2 * (s + i), 2 * (s + i) + 1) for i in range(P)], 100,
-                               cfg.ransac_max_iter, cfg.ransac_confidence, True, force_gate, None,
+                               cfg.ransac_max_iter, cfg.ransac_confidence, not fpfh_on, force_gate, None,
                                cfg.icp_max_iter, cfg.icp_distance() if icp_on else None, cfg.icp_estimation,
                                cfg.icp_normal_k, None, cfg.normal_radius(), icp_with_scaling=scale_on,
                                icp_scale_bounds=tuple(cfg.icp_scale_bounds) if scale_on else None,
@@ -318,7 +355,11 @@ def build_parser():
     ap.add_argument("--max-pitch-deg", type=float, default=360)
     ap.add_argument("--max-yaw-deg", type=float, default=360)
     ap.add_argument("--max-translation", type=float, default=1.0)
-    ap.add_argument("--model-ckpt", "--ckpt", required=True, dest="ckpt")
+    ap.add_argument("--model-ckpt", "--ckpt", dest="ckpt", help="required unless --features fpfh")
+    ap.add_argument("--features", default="network", choices=["network", "fpfh"],
+                    help="descriptors: the network's, or FPFH (cs_fpfh: no checkpoint, no symmetry hypotheses)")
+    ap.add_argument("--fpfh-radius", type=float, default=5.0, help="FPFH radius in voxels (Open3D's example value, untuned)")
+    ap.add_argument("--fpfh-max-nn", type=int, default=100, help="FPFH max_nn, in [4, 128]")
     ap.add_argument("--random-seed", type=int, default=0)
     ap.add_argument("--ransac-max-iter", type=int, default=100000)
     ap.add_argument("--icp-iters", type=int, default=0,
@@ -366,15 +407,21 @@ def main(argv=None):
     if 0 < a.n_models < len(files):                                   # evaluation-shapenet.py:200-203
         files = sorted(rng.choice(files, a.n_models, replace=False).tolist())
     clouds = [np.load(os.path.join(a.data_dir, f)) for f in files]
-    sd, esd = ckpts.load_state_dicts(a.ckpt)
-    pipe = harness.Pipeline(sd, esd, device=a.device)
+    if a.features == "fpfh":
+        pipe = None
+    else:
+        if not a.ckpt:
+            raise SystemExit("--ckpt is required with --features network")
+        sd, esd = ckpts.load_state_dicts(a.ckpt)
+        pipe = harness.Pipeline(sd, esd, device=a.device)
     cfg = Config(random_seed=a.random_seed, n_poses_per_model=a.n_poses_per_model, max_roll_deg=a.max_roll_deg,
                  max_pitch_deg=a.max_pitch_deg, max_yaw_deg=a.max_yaw_deg, max_translation=a.max_translation,
                  ransac_max_iter=a.ransac_max_iter, icp_max_iter=a.icp_iters, icp_max_dist=a.icp_max_dist,
                  icp_estimation=a.icp_estimation, icp_normal_k=a.icp_normal_k, icp_kernel=a.icp_kernel,
                  icp_kernel_scale=a.icp_kernel_scale, icp_normal_radius=a.icp_normal_radius, max_log_scale=a.max_log_scale,
                  icp_with_scaling=a.icp_with_scaling, icp_scale_bounds=(a.icp_scale_min, a.icp_scale_max),
-                 registration=a.registration, fgr_mu_floor=a.fgr_mu_floor, gicp_epsilon=a.gicp_epsilon)
+                 registration=a.registration, fgr_mu_floor=a.fgr_mu_floor, gicp_epsilon=a.gicp_epsilon, features=a.features,
+                 fpfh_radius=a.fpfh_radius, fpfh_max_nn=a.fpfh_max_nn)
     results = evaluate(pipe, clouds, cfg)
     postfix = f"shapenet-seed{a.random_seed}-{a.category}-{len(files)}-{a.n_poses_per_model}"
     os.makedirs(a.out_dir, exist_ok=True)

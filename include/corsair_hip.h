@@ -230,6 +230,7 @@ void cs_topk_catalog_free(cs_topk_catalog* catalog);
  * Output rows are problem-major (all rows of problem 0, then problem 1, ...):
  * d_idx int32 [sum_p nq_p, k] = target row index LOCAL to the target segment, -1 if fewer than k
  * candidates; d_dist f64 same shape, optional (Euclidean distance).
+ * dim is 3, 16, 32 or 33 (cs_fpfh's descriptors; the exhaustive kernel, like 3 and 32); 1 <= k <= 8.
  * Non-finite rows (both paths, labelled or not): a candidate whose canonical f64 squared distance is NaN or
  * +inf is never a neighbour -- the results equal those of the same call with the non-finite target rows removed,
  * indices mapped back; the (-1, +inf) padding applies when fewer than k candidates at finite distance remain, and a
@@ -942,10 +943,84 @@ int cs_fgr_batch(const float* d_src, const float* d_tgt, const int64_t* h_off, i
                  int32_t* d_iters, int32_t* d_ntuple, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * cs_orient_normals: flips normals so that they point away from (away = 1) or towards (away = 0) a view point per
+ * segment -- [O3D-knowledge] Open3D's orient_normals_towards_camera_location with the sense selectable -- or, with
+ * d_view = NULL, the segment's centroid.  cs_estimate_normals' sign rule depends on the pose and FPFH is not invariant to a
+ * flipped normal, so cs_fpfh's callers orient first.  tests/fpfh_ref.py restates this comment bit for bit.
+ *   d_xyz f32 [n,3]; h_off int64 [n_seg + 1] host offsets; d_view f64 [n_seg,3] device or NULL; d_normal f32 [n,3] in/out.
+ *   Per row:  d = (double)x - v (one f64 subtraction per coordinate),  s = fma(n_z, d_z, fma(n_y, d_y, n_x * d_x)) on the
+ *     normal widened to f64; the three components are negated when s < 0 (away = 1) or s > 0 (away = 0).  A zero or NaN s
+ *     keeps the normal (so do NaN normals, rows and view points).
+ *   The centroid (d_view = NULL) is exact and free of the rows' order: over the rows of the segment whose three coordinates
+ *     are finite and below 2^15 in magnitude, S_c = sum of the integers (int64)rint(x_c * 2^16) (round to nearest even; each
+ *     below 2^31 in magnitude, fewer than 2^31 rows: the 64-bit sum cannot overflow), cnt = their number, and
+ *     v_c = ((double)S_c / (double)cnt) * 2^-16 (the conversions round to nearest even).  A segment without such a row keeps
+ *     its normals.  A permuted segment gives the permuted answer, bit for bit.
+ *   n_seg = 0 and empty segments are legal.  Refused (CS_ERR_INVALID): a NULL offset table, a negative count, offsets that
+ *     decrease, an `away` other than 0 / 1, NULL d_xyz or d_normal while a row exists; (CS_ERR_UNSUPPORTED): a segment of
+ *     2^31 rows or more.  No host wait; the only atomics are the integer sums.  Profile family "orient".
+ * ---------------------------------------------------------------------------------------- */
+int cs_orient_normals(const float* d_xyz, const int64_t* h_off, int n_seg, const double* d_view, int away,
+                      float* d_normal, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * cs_fpfh: Fast Point Feature Histograms (Rusu, Blodow, Beetz, ICRA 2009), 33 values per row, after [O3D-knowledge]
+ * Open3D's ComputeFPFHFeature as remembered and not checked against an installation; where the project's habits differ
+ * they hold (DESIGN 21 lists the differences).  This comment is the specification and tests/fpfh_ref.py restates it bit for
+ * bit.  Every operation is ONE IEEE f64 operation in the order the parentheses give, or an explicit fma; nothing is
+ * contracted; only + - * / sqrt floor fma and comparisons appear.
+ *   d_xyz f32 [n,3]; d_normal f32 [n,3] (oriented: cs_orient_normals); h_off int64 [n_seg + 1] host offsets;
+ *   d_fpfh f32 [n,33].  Coordinates and normals are widened to f64 first.
+ *   Neighbours of row i: the rows j != i of the SAME segment with d2 < radius * radius (one f64 product), STRICT;
+ *     (dx, dy, dz) = p_j - p_i, d2 = fma(dz, dz, fma(dy, dy, dx * dx)) -- cs_estimate_normals_hybrid's chain.  Of those the
+ *     min(max_nn - 1, found) smallest by (d2, j) ([O3D-knowledge]: Open3D's hybrid search returns the row itself first and
+ *     max_nn counts it).  A NaN or inf d2 never qualifies.  max_nn in [4, 128]; radius finite and > 0.  m_i = their number.
+ *   Pair (i, j), len = sqrt(d2), dot(a, b) = (a_x * b_x + a_y * b_y) + a_z * b_z,
+ *     cross(a, b) = (a_y * b_z - a_z * b_y, a_z * b_x - a_x * b_z, a_x * b_y - a_y * b_x):
+ *     a1 = dot(n_i, dp) / len, a2 = dot(n_j, dp) / len.  |a1| < |a2|: n1 = n_j, n2 = n_i, dp = -dp, f2 = -a2 (Open3D's
+ *     acos(|a1|) > acos(|a2|) without the acos); otherwise n1 = n_i, n2 = n_j, f2 = a1.
+ *     v = cross(dp, n1), vl = sqrt(dot(v, v)), v = v / vl (three divisions), w = cross(n1, v), f1 = dot(v, n2),
+ *     x = dot(n1, n2), y = dot(w, n2); f0 is the angle of (x, y).
+ *     Degenerate -- len = 0, vl = 0 or not finite, or one of f1, f2, x, y not finite (NaN normals arrive here) -- the
+ *     pair goes to bins 5 / 5 / 5 (Open3D's answer, all features 0).
+ *   Bins, 11 per feature, 33 counters: f0 -> its bin, f1 -> 11 + its bin, f2 -> 22 + its bin.
+ *     f1, f2: floor((11 * (f + 1)) * 0.5) clamped to [0, 10].
+ *     f0: the number of boundaries theta_m = -pi + 2 pi m / 11 (m = 1..10) that are not above the angle, with no
+ *       transcendental function: corsair_amd/csrc/fpfh_bounds.h (tools/gen_fpfh_bounds.py) tabulates (c_m, s_m) =
+ *       (cos theta_m, sin theta_m) as f64 literals and THOSE numbers are the specification; t_m = fma(c_m, y, -(s_m * x)).
+ *       x = y = 0: bin 5.  Otherwise y < 0: the number of m in 1..5 with t_m >= 0; else 5 + the number of m in 6..10 with
+ *       t_m >= 0.  DELIBERATE DIFFERENCE: y = -0 with x < 0 gives bin 10 like y = +0 (atan2 gives -pi there, bin 0).
+ *   SPFH: spfh_b(i) = (double)count_b(i) * (100.0 / (double)m_i), zeros when m_i = 0.  DELIBERATE DIFFERENCE: Open3D adds
+ *     100 / m_i once per pair.
+ *   FPFH: acc_b = 0 (33), sum_g = 0 (3).  For the neighbours j of i in (d2, j) order, skipping d2 == 0, for b = 0..32 in
+ *     order: val = spfh_b(j) / d2;  acc_b = acc_b + val;  sum_(b / 11) = sum_(b / 11) + val.  Then
+ *     out_b = acc_b * (100.0 / sum_(b / 11)) when sum_(b / 11) != 0 (a NaN sum counts as != 0), else acc_b; then
+ *     out_b = out_b + spfh_b(i); one cast to f32.
+ *   Independence: a row's descriptor depends on its segment alone -- not on batch neighbours, the launch shape or the run
+ *     -- and on the ORDER of the rows inside the segment only through exact distance ties.
+ *   n_seg = 0 and empty segments are legal.  Refused (CS_ERR_INVALID): a NULL offset table, a negative count, offsets that
+ *     decrease, NULL arrays while a row exists, a radius that is NaN, infinite or <= 0; (CS_ERR_UNSUPPORTED): max_nn
+ *     outside [4, 128], a segment of 2^31 rows or more.
+ *   Paths, the same bits: the exhaustive scan of the row's segment is the definition, the whole path under CS_FPFH_GRID=0
+ *     (read per call) and the path of every segment of at most 512 rows (cs_estimate_normals_hybrid's convention) and of a
+ *     radius of 1e150 or more.  Otherwise the cell grid of cs_estimate_normals_hybrid (the same code: cells of
+ *     radius (1 + 2^-10), rows sorted by (segment, cell), complete for d2 < radius^2 by the argument in cellgrid.h).  A
+ *     ball larger than the on-chip list is ranked in parts (fpfh.hip) with the same result.
+ *   Everything is enqueued on `stream`; no host wait (CS_FPFH_STATS=1 adds one at the end); the only atomics are integer.
+ *   cs_fpfh_stats: out = {neighbours found (the sum of m_i), rows whose on-chip list was ranked in parts}, counted only
+ *     while CS_FPFH_STATS=1.  CS_FPFH_PASS=1 (read per call) is a timing diagnostic for tools/fpfh_bench.py: the call stops
+ *     after the SPFH pass and d_fpfh is NOT written.
+ * Profile family "fpfh", one scope per call.
+ * ---------------------------------------------------------------------------------------- */
+int cs_fpfh(const float* d_xyz, const float* d_normal, const int64_t* h_off, int n_seg, double radius, int max_nn,
+            float* d_fpfh, void* stream);
+void cs_fpfh_stats(uint64_t out[2], int reset);
+
+/* ------------------------------------------------------------------------------------------
  * Profiling hooks for bench.py: when enabled the library brackets the launches of each named
  * kernel family with hipEvents on the launch stream and accumulates the elapsed time.
  * names: "conv", "ransac_eval", "ransac_pre", "ransac_hyp", "knn", "chamfer", "topk", "symcut",
- * "kmap", "loss", "hardneg", "icp", "normals", "fgr", "chamfer2".
+ * "kmap", "loss", "hardneg", "icp", "normals", "fgr", "chamfer2", "fpfh", "orient".
  * ---------------------------------------------------------------------------------------- */
 void cs_prof_enable(int on);
 void cs_prof_reset(void);
