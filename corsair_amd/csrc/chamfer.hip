@@ -4,10 +4,10 @@
 // The canonical distance of a source p = R s + t to a target is the f64 fma chain over x, y, z; the result of a source is
 // the minimum over the targets.  Every distance that enters a sum or maximum is that of the canonical chain; the fast
 // paths only decide WHICH targets get the canonical evaluation:
-//   * default: k_chamfer_f16 ranks by |t|^2 - 2 p.t on the f16 matrix cores, evaluates the rows of the two best tiles
-//     with the canonical chain and vouches for the result against its error budget; workgroups it cannot vouch for are
-//     recomputed by k_chamfer_mfma (flag array, no host decision).  CS_CHAMFER_STATS=1 counts those workgroups
-//     (cs_chamfer_f16_stats; synchronises).
+//   * default: k_chamfer_f16 ranks by |t|^2 - 2 p.t on the f16 matrix cores (chf_rank.h: the scan it shares with the ICP's
+//     k_icp_f16), evaluates the rows of the two best tiles with the canonical chain and vouches for the result against
+//     the scan's error budget; workgroups it cannot vouch for are recomputed by k_chamfer_mfma (flag array, no host
+//     decision).  CS_CHAMFER_STATS=1 counts those workgroups (cs_chamfer_f16_stats; synchronises).
 //   * CS_CHAMFER_F16=0: k_chamfer_mfma for every tile -- arg-min on the f64 matrix pipe, canonical chain on the four
 //     candidates of a source.
 //   * CS_CHAMFER_MFMA=0: k_chamfer, exhaustive on the VALU -- what the tests hold the other two against.
@@ -21,10 +21,30 @@
 // k_chamfer2, exhaustive on the VALU like k_chamfer, each direction searched with its own rows in registers.
 #include <algorithm>
 
-
-#include "nn_common.h"
+#include "chf_rank.h"
 
 namespace cs {
+
+// the posed source of every kernel here
+__device__ __forceinline__ void chamfer_pose(const float* __restrict__ Tp, const float* __restrict__ s, double* px,
+                                             double* py, double* pz) {
+  const double x = s[0], y = s[1], z = s[2];
+  // row-major 4x4: p = R x + t, evaluated as fma(r0,x, fma(r1,y, fma(r2,z, t)))
+  *px = fma((double)Tp[0], x, fma((double)Tp[1], y, fma((double)Tp[2], z, (double)Tp[3])));
+  *py = fma((double)Tp[4], x, fma((double)Tp[5], y, fma((double)Tp[6], z, (double)Tp[7])));
+  *pz = fma((double)Tp[8], x, fma((double)Tp[9], y, fma((double)Tp[10], z, (double)Tp[11])));
+}
+
+// The tail of every search kernel: red[0, N) holds a value per source (0 for a thread without one); afterwards red[0] is
+// their sum, or their maximum.  Contains barriers: the whole workgroup calls it.
+template <int N>
+__device__ __forceinline__ void chamfer_block_reduce(double (&red)[N], int tid, int reduce_max) {
+  __syncthreads();
+  for (int off = N / 2; off > 0; off >>= 1) {
+    if (tid < off) red[tid] = reduce_max ? fmax(red[tid], red[tid + off]) : red[tid] + red[tid + off];
+    __syncthreads();
+  }
+}
 
 // ------------------------------------------------------------------------------------------
 // one-directional Chamfer
@@ -52,14 +72,7 @@ __global__ __launch_bounds__(256) void k_chamfer(const ChamferWork* __restrict__
   const bool active = tid < wk.sn;
   const float* Tp = T + (int64_t)wk.prob * 16;
   double px = 0, py = 0, pz = 0;
-  if (active) {
-    const float* s = src + (wk.s0 + tid) * 3;
-    double x = s[0], y = s[1], z = s[2];
-    // row-major 4x4: p = R x + t, evaluated as fma(r0,x, fma(r1,y, fma(r2,z, t)))
-    px = fma((double)Tp[0], x, fma((double)Tp[1], y, fma((double)Tp[2], z, (double)Tp[3])));
-    py = fma((double)Tp[4], x, fma((double)Tp[5], y, fma((double)Tp[6], z, (double)Tp[7])));
-    pz = fma((double)Tp[8], x, fma((double)Tp[9], y, fma((double)Tp[10], z, (double)Tp[11])));
-  }
+  if (active) chamfer_pose(Tp, src + (wk.s0 + tid) * 3, &px, &py, &pz);
   double best = INFINITY;
   for (int tbase = 0; tbase < wk.tn; tbase += CH_TT) {
     const int tcount = min(CH_TT, wk.tn - tbase);
@@ -76,11 +89,7 @@ __global__ __launch_bounds__(256) void k_chamfer(const ChamferWork* __restrict__
     }
   }
   red[tid] = active ? sqrt(best) : 0.0;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if (tid < off) red[tid] = reduce_max ? fmax(red[tid], red[tid + off]) : red[tid] + red[tid + off];
-    __syncthreads();
-  }
+  chamfer_block_reduce(red, tid, reduce_max);
   if (tid == 0) partial[wk.slot] = red[0];
 }
 
@@ -128,11 +137,7 @@ __global__ __launch_bounds__(256) void k_chamfer_mfma(const ChamferWork* __restr
 #pragma unroll
   for (int g = 0; g < CHM_NG; ++g) {
     const int sloc = (wave * CHM_NG + g) * 16 + col;
-    const float* sp = src + (wk.s0 + (sloc < wk.sn ? sloc : 0)) * 3;
-    const double x = sp[0], y = sp[1], z = sp[2];
-    px[g] = fma((double)Tp[0], x, fma((double)Tp[1], y, fma((double)Tp[2], z, (double)Tp[3])));
-    py[g] = fma((double)Tp[4], x, fma((double)Tp[5], y, fma((double)Tp[6], z, (double)Tp[7])));
-    pz[g] = fma((double)Tp[8], x, fma((double)Tp[9], y, fma((double)Tp[10], z, (double)Tp[11])));
+    chamfer_pose(Tp, src + (wk.s0 + (sloc < wk.sn ? sloc : 0)) * 3, &px[g], &py[g], &pz[g]);
     bq[g] = kq == 0 ? -2.0 * px[g] : (kq == 1 ? -2.0 * py[g] : (kq == 2 ? -2.0 * pz[g] : 1.0));
     best[g] = INFINITY;
     bidx[g] = -1;
@@ -182,11 +187,7 @@ __global__ __launch_bounds__(256) void k_chamfer_mfma(const ChamferWork* __restr
     const int sloc = (wave * CHM_NG + g) * 16 + col;
     if (kq == 0) red[sloc] = sloc < wk.sn ? sqrt(d) : 0.0;
   }
-  __syncthreads();
-  for (int off = CHM_ST / 2; off > 0; off >>= 1) {
-    if (tid < off) red[tid] = reduce_max ? fmax(red[tid], red[tid + off]) : red[tid] + red[tid + off];
-    __syncthreads();
-  }
+  chamfer_block_reduce(red, tid, reduce_max);
   if (tid == 0) partial[wk.slot] = red[0];
 }
 
@@ -195,18 +196,15 @@ __global__ __launch_bounds__(256) void k_chamfer_mfma(const ChamferWork* __restr
 // ALU (78.6 TF either way): k_chamfer_mfma sits at 0.23 of it with five VALU operations per result on top.  The ranking
 // value |t|^2 - 2 p.t needs nine products when the coordinates are cut into f16 hi + lo (ph.th + ph.tl + pl.th): ONE
 // v_mfma_f32_32x32x16_f16 per 32 targets x 32 sources with |t|^2 in the accumulator input, 16x the rate per pair.  It only
-// RANKS: a lane (one source, 16 of a tile's 32 target rows) keeps the two best TILE minima and the third best value (eight
-// v_min3 per tile, no index per value); at the end the rows of its two tiles are evaluated with the canonical f64 chain,
-// and the result is vouched for when it lies below the third value minus the error budget of the approximation -- then no
-// row outside the evaluated tiles can be nearer.  A workgroup with a source that fails the test is recomputed by
-// k_chamfer_mfma (flag array, no host decision).  Coordinates are scaled by 2^9 before the cut so that the lo parts stay
-// normal f16 numbers; |coordinate| >= 60 does not fit and takes the f64 kernel as well.  Results: the same canonical
+// RANKS (chf_rank.h: image, operands, scan and error budget, shared with the ICP's association kernel): at the end the
+// rows of a lane's two best tiles are evaluated with the canonical f64 chain, and the result is vouched for when it lies
+// below the smallest unevaluated tile minimum minus the error budget -- then no row outside the evaluated tiles can be
+// nearer.  A workgroup with a source that fails the test is recomputed by k_chamfer_mfma (flag array, no host decision).
+// Coordinates outside the f16 range (|coordinate| >= 60) take the f64 kernel as well.  Results: the same canonical
 // distances as the other two kernels (tests/test_gpu_post.py::test_chamfer_matches_oracle, all three paths).
-// (CHF_PITCH, CHF_ROWS, CHF_NG, CHF_SCALE: nn_common.h -- the ICP's association kernel reads the same image)
 static_assert(4 * 32 * CHF_NG == CHM_ST, "the f16 kernel and its f64 fallback share the work items");
 
-// target image: row j = [th(3) | tl(3) | th(3) | 0(7) | pad(8)] of the scaled coordinates, tn32[j] = |S t|^2 (f64 chain,
-// rounded to f32); rows [n, n_pad) are zero with tn32 = +inf (they never win)
+// the target image of chf_rank.h; rows [n, n_pad) are zero with tn32 = +inf (they never win)
 __global__ void k_chamfer_pack16(const float* __restrict__ tgt, int64_t n, int64_t n_pad, _Float16* __restrict__ img,
                                  float* __restrict__ tn32, float4* __restrict__ t4f) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -258,151 +256,38 @@ __global__ __launch_bounds__(256) void k_chamfer_f16(const ChamferWork* __restri
   const int col = lane & 31;
   const float* Tp = T + (int64_t)wk.prob * 16;
   if (tid == 0) wg_bad = 0;
-  double px[CHF_NG], py[CHF_NG], pz[CHF_NG];
-  f16x8 bop[CHF_NG];
-  float b1[CHF_NG], b2[CHF_NG], b3[CHF_NG];
-  int t1[CHF_NG], t2[CHF_NG];
-  bool in_range = true;
+  ChfRank rk;
 #pragma unroll
   for (int g = 0; g < CHF_NG; ++g) {
     const int sloc = wave * 32 * CHF_NG + 32 * g + col;
-    const float* sp = src + (wk.s0 + (sloc < wk.sn ? sloc : 0)) * 3;
-    const double x = sp[0], y = sp[1], z = sp[2];
-    px[g] = fma((double)Tp[0], x, fma((double)Tp[1], y, fma((double)Tp[2], z, (double)Tp[3])));
-    py[g] = fma((double)Tp[4], x, fma((double)Tp[5], y, fma((double)Tp[6], z, (double)Tp[7])));
-    pz[g] = fma((double)Tp[8], x, fma((double)Tp[9], y, fma((double)Tp[10], z, (double)Tp[11])));
-    const float pf[3] = {(float)px[g] * CHF_SCALE, (float)py[g] * CHF_SCALE, (float)pz[g] * CHF_SCALE};
-    _Float16 hi[3], lo[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      knf_split(-2.0f * pf[c], &hi[c], &lo[c]);
-      in_range = in_range && fabsf(pf[c]) < 60.0f * CHF_SCALE;   // (NaN fails too)
-    }
-    // B rows k: 0..2 = -2 ph (x th), 3..5 = -2 ph (x tl), 6..8 = -2 pl (x th), 9..15 = 0; this lane holds k = 8 half .. + 7
-    const _Float16 z0 = (_Float16)0.0f;
-    if (half == 0)
-      bop[g] = f16x8{hi[0], hi[1], hi[2], hi[0], hi[1], hi[2], lo[0], lo[1]};
-    else
-      bop[g] = f16x8{lo[2], z0, z0, z0, z0, z0, z0, z0};
-    b1[g] = b2[g] = b3[g] = INFINITY;
-    t1[g] = t2[g] = -1;
+    chamfer_pose(Tp, src + (wk.s0 + (sloc < wk.sn ? sloc : 0)) * 3, &rk.px[g], &rk.py[g], &rk.pz[g]);
+    chf_operand(rk, g, half);
   }
-  // register-staged double buffer: the next stage's 12 KiB image + |t|^2 are requested before this stage is computed
-  const uint4* gimg = reinterpret_cast<const uint4*>(img + (int64_t)wk.t0 * CHF_PITCH);
-  constexpr int U4_PER_STAGE = CHF_ROWS * CHF_PITCH * 2 / 16;   // 768 = 3 per thread
-  uint4 st0, st1, st2;     // (three named registers: an array captured by the lambdas below went to scratch)
-  float stn;
-  float tmax2 = 0.0f;
-  auto load_stage = [&](int base) {
-    const uint4* g = gimg + (int64_t)base * (CHF_PITCH * 2 / 16) + tid;
-    st0 = g[0];
-    st1 = g[256];
-    st2 = g[512];
-    const int r = base + tid;
-    stn = r < wk.tn ? tn32[wk.t0 + r] : INFINITY;   // rows past the segment (another problem's rows) never win
-    if (r < wk.tn) tmax2 = fmaxf(tmax2, stn);
-  };
-  auto store_stage = [&](int b) {
-    uint4* d = reinterpret_cast<uint4*>(a_s[b]) + tid;
-    d[0] = st0;
-    d[256] = st1;
-    d[512] = st2;
-    tn_s[b][tid] = stn;
-  };
-  static_assert(U4_PER_STAGE == 3 * 256, "three 16-byte pieces per thread");
-  if (wk.tn > 0) {
-    load_stage(0);
-    store_stage(0);
-  }
-  int buf = 0;
-  for (int base = 0; base < wk.tn; base += CHF_ROWS) {
-    __syncthreads();
-    const bool more = base + CHF_ROWS < wk.tn;
-    if (more) load_stage(base + CHF_ROWS);
-#pragma unroll 1
-    for (int t = 0; t < CHF_ROWS / 32; ++t) {
-      if (base + 32 * t >= wk.tn) break;   // whole tile past the range (block-uniform)
-      const f16x8 a = *reinterpret_cast<const f16x8*>(a_s[buf] + (t * 32 + col) * CHF_PITCH + 8 * half);
-      f32x16 c16;
-#pragma unroll
-      for (int q4 = 0; q4 < 4; ++q4) {
-        const float4 v = *reinterpret_cast<const float4*>(&tn_s[buf][t * 32 + 8 * q4 + 4 * half]);
-        c16[4 * q4 + 0] = v.x; c16[4 * q4 + 1] = v.y; c16[4 * q4 + 2] = v.z; c16[4 * q4 + 3] = v.w;
-      }
-      const int tile = base / 32 + t;
-#pragma unroll
-      for (int g = 0; g < CHF_NG; ++g) {
-        const f32x16 d = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, bop[g], c16, 0, 0, 0);
-        float m = fminf(fminf(d[0], d[1]), d[2]);
-        m = fminf(fminf(m, d[3]), d[4]);
-        m = fminf(fminf(m, d[5]), d[6]);
-        m = fminf(fminf(m, d[7]), d[8]);
-        m = fminf(fminf(m, d[9]), d[10]);
-        m = fminf(fminf(m, d[11]), d[12]);
-        m = fminf(fminf(m, d[13]), d[14]);
-        m = fminf(m, d[15]);
-        // sorted insertion of the tile minimum without a branch: new j-th value = median of (old j-1-th, old j-th, m);
-        // the tile ids follow the two comparisons
-        const float o1 = b1[g], o2 = b2[g];
-        const bool lt1 = m < o1, lt2 = m < o2;
-        b1[g] = fminf(o1, m);
-        b2[g] = __builtin_amdgcn_fmed3f(o1, o2, m);
-        b3[g] = __builtin_amdgcn_fmed3f(o2, b3[g], m);
-        t2[g] = lt1 ? t1[g] : (lt2 ? tile : t2[g]);
-        t1[g] = lt1 ? tile : t1[g];
-      }
-    }
-    if (more) store_stage(buf ^ 1);
-    buf ^= 1;
-  }
-  // largest |S t|^2 of the segment (error budget)
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) tmax2 = fmaxf(tmax2, __shfl_xor(tmax2, off));
-  if (lane == 0) wmax[wave] = tmax2;
-  __syncthreads();
-  const double tmax = sqrt((double)fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]))) / (double)CHF_SCALE;
-  bool bad = !in_range || !(tmax < 60.0);
+  const double tmax = chf_scan(rk, img, tn32, wk.t0, wk.tn, a_s, tn_s, wmax, tid);
+  bool bad = !rk.in_range || !(tmax < 60.0);
   const float4* trow = t4f + wk.t0;
-  auto eval_tile = [&](int g, int tile) {   // canonical distances of this lane's 16 rows of a tile: smallest
-    double e = INFINITY;
-    if (tile >= 0) {
-      float4 v[16];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int row = tile * 32 + 4 * half + (i & 3) + 8 * (i >> 2);
-        v[i] = trow[row < wk.tn ? row : 0];
-      }
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int row = tile * 32 + 4 * half + (i & 3) + 8 * (i >> 2);
-        const double dx = px[g] - (double)v[i].x, dy = py[g] - (double)v[i].y, dz = pz[g] - (double)v[i].z;
-        const double d = fma(dz, dz, fma(dy, dy, dx * dx));
-        e = row < wk.tn ? fmin(e, d) : e;
-      }
-    }
+  auto eval_tile = [&](int g, int tile) {   // smallest canonical distance of this lane's 16 rows of a tile
+    double e;
+    int er;
+    chf_eval_tile(trow, wk.tn, tile, half, rk.px[g], rk.py[g], rk.pz[g], e, er);
     return e;
   };
 #pragma unroll
   for (int g = 0; g < CHF_NG; ++g) {
-    // Every unevaluated row has an approximate value >= the smallest tile minimum that was not evaluated (in scaled units
-    // S^2 (|t|^2 - 2 p.t)), hence an exact one >= that - eps with eps covering: <= 16 f32 accumulation steps relative to
-    // sum |terms| <= (|P| + |T|)^2, the dropped lo.lo products and the hi + lo cut residuals (2^-22 relative each), the f32
-    // rounding of |T|^2 -- together < 2^-20 (|P| + |T|max)^2, charged 2^-19 -- and lo parts below the f16 normal range
-    // should the matrix pipe flush them (<= 2^-14 per product side: 2^-10 (|P| + |T|max) covers all nine).
-    const double pn2 = fma(pz[g], pz[g], fma(py[g], py[g], px[g] * px[g]));
-    const double S = (double)CHF_SCALE, PT = S * (sqrt(pn2) + tmax);
-    const double eps = 0x1.0p-19 * PT * PT + 0x1.0p-10 * PT;
-    // best tile of either lane of the source first; the second tiles only where that does not settle it
-    double e = eval_tile(g, t1[g]);
+    const double pn2 = fma(rk.pz[g], rk.pz[g], fma(rk.py[g], rk.py[g], rk.px[g] * rk.px[g]));
+    const double S = (double)CHF_SCALE, eps = chf_eps(pn2, tmax);
+    // best tile of either lane of the source first; the second tiles only where that does not settle it.  Vouching with
+    // <= (k_icp_f16: <): an unevaluated row that ties has the same distance, and only the distance is returned here.
+    double e = eval_tile(g, rk.t1[g]);
     e = fmin(e, __shfl_xor(e, 32));
-    float rest = fminf(b2[g], __shfl_xor(b2[g], 32));     // smallest unevaluated tile minimum of the source
+    float rest = fminf(rk.b2[g], __shfl_xor(rk.b2[g], 32));     // smallest unevaluated tile minimum of the source
     bool ok = rest == INFINITY || (e - pn2) * S * S <= (double)rest - eps;
     if (__any(!ok)) {
-      double e2 = ok ? INFINITY : eval_tile(g, t2[g]);
+      double e2 = ok ? INFINITY : eval_tile(g, rk.t2[g]);
       e2 = fmin(e2, __shfl_xor(e2, 32));
       if (!ok) {
         e = fmin(e, e2);
-        rest = fminf(b3[g], __shfl_xor(b3[g], 32));
+        rest = fminf(rk.b3[g], __shfl_xor(rk.b3[g], 32));
         ok = rest == INFINITY || (e - pn2) * S * S <= (double)rest - eps;
       }
     }
@@ -411,11 +296,7 @@ __global__ __launch_bounds__(256) void k_chamfer_f16(const ChamferWork* __restri
     if (half == 0) red[sloc] = sloc < wk.sn ? sqrt(e) : 0.0;
   }
   if (__any(bad) && lane == 0) atomicOr(&wg_bad, 1);
-  __syncthreads();
-  for (int off = CHM_ST / 2; off > 0; off >>= 1) {
-    if (tid < off) red[tid] = reduce_max ? fmax(red[tid], red[tid + off]) : red[tid] + red[tid + off];
-    __syncthreads();
-  }
+  chamfer_block_reduce(red, tid, reduce_max);
   if (tid == 0) {
     partial[wk.slot] = red[0];
     flag[blockIdx.x] = wg_bad;
@@ -462,15 +343,6 @@ struct Chamfer2Work {
   int32_t dir;  // 0 forward, 1 backward
   int32_t pad;
 };
-
-__device__ __forceinline__ void chamfer_pose(const float* __restrict__ Tp, const float* __restrict__ s, double* px,
-                                             double* py, double* pz) {
-  const double x = s[0], y = s[1], z = s[2];
-  // row-major 4x4: p = R x + t, evaluated as fma(r0,x, fma(r1,y, fma(r2,z, t))) -- k_chamfer's chain
-  *px = fma((double)Tp[0], x, fma((double)Tp[1], y, fma((double)Tp[2], z, (double)Tp[3])));
-  *py = fma((double)Tp[4], x, fma((double)Tp[5], y, fma((double)Tp[6], z, (double)Tp[7])));
-  *pz = fma((double)Tp[8], x, fma((double)Tp[9], y, fma((double)Tp[10], z, (double)Tp[11])));
-}
 
 __global__ __launch_bounds__(256) void k_chamfer2(const Chamfer2Work* __restrict__ work, const float* __restrict__ src,
                                                   const float* __restrict__ tgt, const float* __restrict__ T,
@@ -526,11 +398,7 @@ __global__ __launch_bounds__(256) void k_chamfer2(const Chamfer2Work* __restrict
     }
   }
   red[tid] = active ? sqrt(best) : 0.0;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if (tid < off) red[tid] = red[tid] + red[tid + off];
-    __syncthreads();
-  }
+  chamfer_block_reduce(red, tid, 0);
   if (tid == 0) partial[wk.slot] = red[0];
 }
 
@@ -578,16 +446,11 @@ static int chamfer_rank(const ChamferOptions& opt, const ChamferWork* d_work, un
                        (const int32_t*)nullptr);
     return CS_OK;
   }
-  // image rows padded by one stage: the last stage of the last segment reads past its end
-  const int64_t n_pad = nt_rows + CHF_ROWS;
-  PoolBuf<_Float16> img16((size_t)n_pad * CHF_PITCH);
-  PoolBuf<float> tn16((size_t)n_pad);
-  PoolBuf<float4> t4f((size_t)(nt_rows ? nt_rows : 1));
+  ChfImage im;
   PoolBuf<int32_t> wflag(n_work);
-  CS_REQUIRE(img16.p && tn16.p && wflag.p && t4f.p, CS_ERR_HIP, "cs_chamfer_1dir: scratch allocation failed");
-  chamfer_pack16(d_tgt, nt_rows, n_pad, img16.p, tn16.p, t4f.p, s);
-  hipLaunchKernelGGL(k_chamfer_f16, grid, dim3(256), 0, s, d_work, d_src, t4f.p, img16.p, tn16.p, d_T, reduce_max,
-                     partial, wflag.p);
+  CS_REQUIRE(wflag.p && im.pack(d_tgt, nt_rows, s), CS_ERR_HIP, "cs_chamfer_1dir: scratch allocation failed");
+  hipLaunchKernelGGL(k_chamfer_f16, grid, dim3(256), 0, s, d_work, d_src, im.t4f.p, im.img16.p, im.tn16.p, d_T,
+                     reduce_max, partial, wflag.p);
   hipLaunchKernelGGL(k_chamfer_mfma, grid, dim3(256), 0, s, d_work, d_src, d_tgt, t4g.p, d_T, reduce_max, partial,
                      wflag.p);
   if (opt.stats) {
@@ -597,6 +460,34 @@ static int chamfer_rank(const ChamferOptions& opt, const ChamferWork* d_work, un
     g_chamfer_stats[0] += n_work;
     g_chamfer_stats[1] += h;
   }
+  return CS_OK;
+}
+
+// What both drivers do once their work list stands: upload it with the slot table (slot_begin[o] .. slot_begin[o + 1] = the
+// work items of output o) and the row counts, run `search(d_work, partial)` (it fills partial[w.slot] of every work item)
+// and finish every output from its slots -- the mean or the maximum, NaN for an output without rows.
+template <typename Work, typename Search>
+static int chamfer_search_finish(const char* who, const char* family, double flop, const std::vector<Work>& work,
+                                 const std::vector<int32_t>& slot_begin, const std::vector<int64_t>& count, int reduce_max,
+                                 double* d_out, hipStream_t s, Search search) {
+  const int n_out = (int)count.size();
+  PoolBuf<Work> dwork;
+  PoolBuf<int32_t> dslot;
+  PoolBuf<int64_t> dcount;
+  PoolBuf<double> partial(work.size() + 1);
+  CS_REQUIRE(partial.p, CS_ERR_HIP, "%s: scratch allocation failed", who);
+  int rc = upload(dwork, work, s);
+  if (!rc) rc = upload(dslot, slot_begin, s);
+  if (!rc) rc = upload(dcount, count, s);
+  if (rc) return rc;
+  ProfScope prof(family, s, flop);
+  if (!work.empty()) {
+    rc = search(dwork.p, partial.p);
+    if (rc) return rc;
+  }
+  hipLaunchKernelGGL(k_chamfer_finish, dim3((unsigned)ceil_div(n_out, 64)), dim3(64), 0, s, partial.p, dslot.p, dcount.p,
+                     n_out, reduce_max, d_out);
+  CS_LAUNCH_CHECK();
   return CS_OK;
 }
 
@@ -640,25 +531,12 @@ static int nn_dist_reduce(const float* d_src, const int64_t* h_soff, const float
   }
   slot_begin[n_prob] = (int32_t)work.size();
   CS_REQUIRE(work.empty() || (d_src && d_tgt), CS_ERR_INVALID, "cs_chamfer_1dir: NULL point array");
-  PoolBuf<ChamferWork> dwork;
-  PoolBuf<int32_t> dslot;
-  PoolBuf<int64_t> dcount;
-  PoolBuf<double> partial(work.size() + 1);
-  CS_REQUIRE(partial.p, CS_ERR_HIP, "cs_chamfer_1dir: scratch allocation failed");
-  int rc = upload(dwork, work, s);
-  if (!rc) rc = upload(dslot, slot_begin, s);
-  if (!rc) rc = upload(dcount, src_count, s);
-  if (rc) return rc;
-  ProfScope prof("chamfer", s, ch_flop);
-  if (!work.empty()) {
-    rc = chamfer_rank(opt, dwork.p, (unsigned)work.size(), d_src, d_tgt, nt_rows, d_T, reduce_max, partial.p, s);
-    if (rc) return rc;
-  }
-  // finish: per problem the mean (Chamfer) or the maximum (Hausdorff) of its tiles' partial results
-  hipLaunchKernelGGL(k_chamfer_finish, dim3((unsigned)ceil_div(n_prob, 64)), dim3(64), 0, s,
-                     partial.p, dslot.p, dcount.p, n_prob, reduce_max, d_out);
-  CS_LAUNCH_CHECK();
-  return CS_OK;
+  // per problem the mean (Chamfer) or the maximum (Hausdorff) of its tiles' partial results
+  return chamfer_search_finish("cs_chamfer_1dir", "chamfer", ch_flop, work, slot_begin, src_count, reduce_max, d_out, s,
+                               [&](const ChamferWork* d_work, double* partial) {
+                                 return chamfer_rank(opt, d_work, (unsigned)work.size(), d_src, d_tgt, nt_rows, d_T,
+                                                     reduce_max, partial, s);
+                               });
 }
 
 // cs_chamfer_2dir: the work list holds, per problem, the forward tiles then the backward tiles; direction h = 2 p + dir is
@@ -704,22 +582,12 @@ static int chamfer_2dir(const float* d_src, const int64_t* h_soff, const float* 
   }
   slot_begin[2 * (size_t)n_prob] = (int32_t)work.size();
   CS_REQUIRE(work.empty() || (d_src && d_tgt), CS_ERR_INVALID, "cs_chamfer_2dir: NULL point array");
-  PoolBuf<Chamfer2Work> dwork;
-  PoolBuf<int32_t> dslot;
-  PoolBuf<int64_t> dcount;
-  PoolBuf<double> partial(work.size() + 1);
-  CS_REQUIRE(partial.p, CS_ERR_HIP, "cs_chamfer_2dir: scratch allocation failed");
-  int rc = upload(dwork, work, s);
-  if (!rc) rc = upload(dslot, slot_begin, s);
-  if (!rc) rc = upload(dcount, row_count, s);
-  if (rc) return rc;
-  ProfScope prof("chamfer2", s, ch_flop);
-  if (!work.empty())
-    hipLaunchKernelGGL(k_chamfer2, dim3((unsigned)work.size()), dim3(256), 0, s, dwork.p, d_src, d_tgt, d_T, partial.p);
-  hipLaunchKernelGGL(k_chamfer_finish, dim3((unsigned)ceil_div(2 * (int64_t)n_prob, 64)), dim3(64), 0, s, partial.p,
-                     dslot.p, dcount.p, 2 * n_prob, 0, d_out);
-  CS_LAUNCH_CHECK();
-  return CS_OK;
+  return chamfer_search_finish("cs_chamfer_2dir", "chamfer2", ch_flop, work, slot_begin, row_count, 0, d_out, s,
+                               [&](const Chamfer2Work* d_work, double* partial) {
+                                 hipLaunchKernelGGL(k_chamfer2, dim3((unsigned)work.size()), dim3(256), 0, s, d_work, d_src,
+                                                    d_tgt, d_T, partial);
+                                 return CS_OK;
+                               });
 }
 
 extern "C" {

@@ -116,7 +116,7 @@ struct IcpState {
   unsigned long long* sums;     // n_prob * icp_nsum(est)
   unsigned long long* stats;    // the two counters of CS_ICP_STATS behind the sums, NULL when they are not wanted
   int32_t* done;
-  // the f16 image of the targets (chamfer_pack16) and the workgroup flags: NULL under CS_ICP_F16=0
+  // the f16 image of the targets (ChfImage, chf_rank.h) and the workgroup flags: NULL under CS_ICP_F16=0
   const _Float16* img16;
   const float* tn16;
   const float4* t4f;

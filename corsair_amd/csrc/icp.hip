@@ -12,7 +12,7 @@
 // One call = one target preparation + (max_iter + 1) rounds, all enqueued without a host wait:
 //   k_icp_frame    per problem: the bounding box of its target segment (exact min / max), the origin and the
 //                  power-of-two scales of its fixed-point sums
-//   chamfer_pack16 the f16 hi / lo image, |S t|^2 and the float4 rows of every target, once per call
+//   ChfImage       the f16 hi / lo image, |S t|^2 and the float4 rows of every target (chf_rank.h), once per call
 //   round r:       k_icp_f16 (+ k_icp_exact for the workgroups it flags) or k_icp_exact alone -- association of the posed
 //                  ORIGINAL sources under the current T, 17 (point), 29 (plane), 30 (weighted plane), 18 (point + scale),
 //                  37 (plane + scale) or 30 (GICP) order-free 64-bit integer sums per problem; k_icp_step -- one lane per problem:
@@ -23,8 +23,8 @@
 
 #include <algorithm>
 
+#include "chf_rank.h"
 #include "icp.h"
-#include "nn_common.h"
 
 namespace cs {
 namespace {
@@ -116,23 +116,14 @@ int icp_run(const char* name, int est, const IcpCall& c) {
   icp_launch_setup(est, c, st, s);
   if (est == ICP_GICP && c.mrmse) CS_HIP_CHECK(hipMemsetAsync(c.mrmse, 0, sizeof(double) * (size_t)n_prob, s));
   // the targets do not move: one image for every round
-  PoolBuf<_Float16> img16;
-  PoolBuf<float> tn16;
-  PoolBuf<float4> t4f;
+  ChfImage im;
   PoolBuf<int32_t> wflag;
-  if (use_f16 && st.n_work) {
-    const int64_t n_pad = nt_rows + CHF_ROWS;   // the last stage of the last segment reads past its end
-    img16.alloc((size_t)n_pad * CHF_PITCH);
-    tn16.alloc((size_t)n_pad);
-    t4f.alloc((size_t)(nt_rows ? nt_rows : 1));
-    wflag.alloc(st.n_work);
-    CS_REQUIRE(img16.p && tn16.p && t4f.p && wflag.p, CS_ERR_HIP, "%s: scratch allocation failed", name);
-    chamfer_pack16(c.tgt, nt_rows, n_pad, img16.p, tn16.p, t4f.p, s);
-  }
+  if (use_f16 && st.n_work)
+    CS_REQUIRE(wflag.alloc(st.n_work) && im.pack(c.tgt, nt_rows, s), CS_ERR_HIP, "%s: scratch allocation failed", name);
   CS_LAUNCH_CHECK();
-  st.img16 = img16.p;
-  st.tn16 = tn16.p;
-  st.t4f = t4f.p;
+  st.img16 = im.img16.p;
+  st.tn16 = im.tn16.p;
+  st.t4f = im.t4f.p;
   st.wflag = wflag.p;
   for (int round = 0; round <= c.max_iter; ++round) {
     if (st.n_work) icp_launch_assoc(est, use_f16, c, st, s);

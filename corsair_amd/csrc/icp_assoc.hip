@@ -1,10 +1,11 @@
 // The association of one ICP round: the posed ORIGINAL sources under the current T against the targets of
 // their problem, the nearest target by (distance, row), and the sums of the kept pairs (icp_sums.h) at the end of either
-// kernel.  k_icp_f16 ranks on the matrix cores and vouches for its result or flags its workgroup; k_icp_exact recomputes the
-// flagged workgroups, and is the whole path under CS_ICP_F16=0.  icp_launch_assoc is the way in.
+// kernel.  k_icp_f16 ranks on the matrix cores (chf_rank.h: the scan it shares with k_chamfer_f16) and vouches for its result
+// or flags its workgroup; k_icp_exact recomputes the flagged workgroups, and is the whole path under CS_ICP_F16=0.
+// icp_launch_assoc is the way in.
+#include "chf_rank.h"
 #include "icp.h"
 #include "icp_sums.h"
-#include "nn_common.h"
 
 namespace cs {
 namespace {
@@ -69,11 +70,11 @@ __global__ __launch_bounds__(256) void k_icp_exact(const IcpWork* __restrict__ w
                       EST == ICP_GICP && kept ? snrm + (wk.s0 + tid) * 3 : nullptr, T + (int64_t)wk.prob * 16, ome);
 }
 
-// The association on the f16 matrix cores: k_chamfer_f16's ranking (same image, same operand layout, same error budget;
-// chamfer.hip and DESIGN 3 / 12) keeping (distance, row) of the evaluated rows and vouching STRICTLY: the result stands only
-// when it lies below the smallest unevaluated tile minimum minus the error budget, so a row that was not evaluated can
-// neither beat nor tie it.  A workgroup with a source that fails the test, or with coordinates outside the f16 range,
-// adds nothing and raises its flag; k_icp_exact recomputes it.
+// The association on the f16 matrix cores: the ranking scan of chf_rank.h, which k_chamfer_f16 runs as well (same image,
+// same operands, same error budget), keeping (distance, row) of the evaluated rows and vouching STRICTLY:
+// the result stands only when it lies below the smallest unevaluated tile minimum minus the error budget, so a row that
+// was not evaluated can neither beat nor tie it.  A workgroup with a source that fails the test, or with coordinates
+// outside the f16 range, adds nothing and raises its flag; k_icp_exact recomputes it.
 template <int EST>
 __global__ __launch_bounds__(256) void k_icp_f16(const IcpWork* __restrict__ work, const IcpProb* __restrict__ probs,
                                                  const float* __restrict__ src, const float4* __restrict__ t4f,
@@ -105,126 +106,20 @@ __global__ __launch_bounds__(256) void k_icp_f16(const IcpWork* __restrict__ wor
   const int col = lane & 31;
   const double* Tp = T + (int64_t)wk.prob * 16;
   if (tid == 0) wg_bad = 0;
-  double px[CHF_NG], py[CHF_NG], pz[CHF_NG];
-  f16x8 bop[CHF_NG];
-  float b1[CHF_NG], b2[CHF_NG], b3[CHF_NG];
-  int t1[CHF_NG], t2[CHF_NG];
-  bool in_range = true;
+  ChfRank rk;
 #pragma unroll
   for (int g = 0; g < CHF_NG; ++g) {
     const int sloc = wave * 32 * CHF_NG + 32 * g + col;
-    icp_pose(Tp, src + (wk.s0 + (sloc < wk.sn ? sloc : 0)) * 3, px[g], py[g], pz[g]);
-    const float pf[3] = {(float)px[g] * CHF_SCALE, (float)py[g] * CHF_SCALE, (float)pz[g] * CHF_SCALE};
-    _Float16 hi[3], lo[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      knf_split(-2.0f * pf[c], &hi[c], &lo[c]);
-      in_range = in_range && fabsf(pf[c]) < 60.0f * CHF_SCALE;   // (NaN fails too)
-    }
-    // B rows k: 0..2 = -2 ph (x th), 3..5 = -2 ph (x tl), 6..8 = -2 pl (x th), 9..15 = 0; this lane holds k = 8 half .. + 7
-    const _Float16 z0 = (_Float16)0.0f;
-    if (half == 0)
-      bop[g] = f16x8{hi[0], hi[1], hi[2], hi[0], hi[1], hi[2], lo[0], lo[1]};
-    else
-      bop[g] = f16x8{lo[2], z0, z0, z0, z0, z0, z0, z0};
-    b1[g] = b2[g] = b3[g] = INFINITY;
-    t1[g] = t2[g] = -1;
+    icp_pose(Tp, src + (wk.s0 + (sloc < wk.sn ? sloc : 0)) * 3, rk.px[g], rk.py[g], rk.pz[g]);
+    chf_operand(rk, g, half);
   }
-  // register-staged double buffer of the 12-KiB image stages, as in k_chamfer_f16
-  const uint4* gimg = reinterpret_cast<const uint4*>(img + pr.t0 * CHF_PITCH);
-  constexpr int U4_PER_STAGE = CHF_ROWS * CHF_PITCH * 2 / 16;
-  static_assert(U4_PER_STAGE == 3 * 256, "three 16-byte pieces per thread");
-  uint4 st0, st1, st2;
-  float stn;
-  float tmax2 = 0.0f;
-  auto load_stage = [&](int base) {
-    const uint4* g = gimg + (int64_t)base * (CHF_PITCH * 2 / 16) + tid;
-    st0 = g[0];
-    st1 = g[256];
-    st2 = g[512];
-    const int r = base + tid;
-    stn = r < tn ? tn32[pr.t0 + r] : INFINITY;   // rows past the segment (another problem's rows) never win
-    if (r < tn) tmax2 = fmaxf(tmax2, stn);
-  };
-  auto store_stage = [&](int b) {
-    uint4* d = reinterpret_cast<uint4*>(a_s[b]) + tid;
-    d[0] = st0;
-    d[256] = st1;
-    d[512] = st2;
-    tn_s[b][tid] = stn;
-  };
-  if (tn > 0) {
-    load_stage(0);
-    store_stage(0);
-  }
-  int buf = 0;
-  for (int base = 0; base < tn; base += CHF_ROWS) {
-    __syncthreads();
-    const bool more = base + CHF_ROWS < tn;
-    if (more) load_stage(base + CHF_ROWS);
-#pragma unroll 1
-    for (int t = 0; t < CHF_ROWS / 32; ++t) {
-      if (base + 32 * t >= tn) break;   // whole tile past the range (block-uniform)
-      const f16x8 a = *reinterpret_cast<const f16x8*>(a_s[buf] + (t * 32 + col) * CHF_PITCH + 8 * half);
-      f32x16 c16;
-#pragma unroll
-      for (int q4 = 0; q4 < 4; ++q4) {
-        const float4 v = *reinterpret_cast<const float4*>(&tn_s[buf][t * 32 + 8 * q4 + 4 * half]);
-        c16[4 * q4 + 0] = v.x; c16[4 * q4 + 1] = v.y; c16[4 * q4 + 2] = v.z; c16[4 * q4 + 3] = v.w;
-      }
-      const int tile = base / 32 + t;
-#pragma unroll
-      for (int g = 0; g < CHF_NG; ++g) {
-        const f32x16 d = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, bop[g], c16, 0, 0, 0);
-        float m = fminf(fminf(d[0], d[1]), d[2]);
-        m = fminf(fminf(m, d[3]), d[4]);
-        m = fminf(fminf(m, d[5]), d[6]);
-        m = fminf(fminf(m, d[7]), d[8]);
-        m = fminf(fminf(m, d[9]), d[10]);
-        m = fminf(fminf(m, d[11]), d[12]);
-        m = fminf(fminf(m, d[13]), d[14]);
-        m = fminf(m, d[15]);
-        const float o1 = b1[g], o2 = b2[g];
-        const bool lt1 = m < o1, lt2 = m < o2;
-        b1[g] = fminf(o1, m);
-        b2[g] = __builtin_amdgcn_fmed3f(o1, o2, m);
-        b3[g] = __builtin_amdgcn_fmed3f(o2, b3[g], m);
-        t2[g] = lt1 ? t1[g] : (lt2 ? tile : t2[g]);
-        t1[g] = lt1 ? tile : t1[g];
-      }
-    }
-    if (more) store_stage(buf ^ 1);
-    buf ^= 1;
-  }
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) tmax2 = fmaxf(tmax2, __shfl_xor(tmax2, off));
-  if (lane == 0) wmax[wave] = tmax2;
-  __syncthreads();
-  const double tmax = sqrt((double)fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]))) / (double)CHF_SCALE;
-  bool bad = !in_range || !(tmax < 60.0);
+  // (block-uniform: the early return on done[prob] above is taken by the whole workgroup)
+  const double tmax = chf_scan(rk, img, tn32, pr.t0, tn, a_s, tn_s, wmax, tid);
+  bool bad = !rk.in_range || !(tmax < 60.0);
   const float4* trow = t4f + pr.t0;
-  // canonical distances of this lane's 16 rows of a tile, ascending rows, strict <: the smallest by (distance, row)
+  // this lane's 16 rows of a tile: the smallest by (distance, row)
   auto eval_tile = [&](int g, int tile, double& e, int& er) {
-    e = INFINITY;
-    er = 0x7fffffff;
-    if (tile >= 0) {
-      float4 v[16];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int row = tile * 32 + 4 * half + (i & 3) + 8 * (i >> 2);
-        v[i] = trow[row < tn ? row : 0];
-      }
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int row = tile * 32 + 4 * half + (i & 3) + 8 * (i >> 2);
-        const double dx = px[g] - (double)v[i].x, dy = py[g] - (double)v[i].y, dz = pz[g] - (double)v[i].z;
-        const double d = fma(dz, dz, fma(dy, dy, dx * dx));
-        if (row < tn && d < e) {
-          e = d;
-          er = row;
-        }
-      }
-    }
+    chf_eval_tile(trow, tn, tile, half, rk.px[g], rk.py[g], rk.pz[g], e, er);
   };
   // (distance, row) minimum of the two lanes of a source
   auto pair_min = [&](double& e, int& er) {
@@ -239,27 +134,26 @@ __global__ __launch_bounds__(256) void k_icp_f16(const IcpWork* __restrict__ wor
   int my_row = 0x7fffffff;
 #pragma unroll
   for (int g = 0; g < CHF_NG; ++g) {
-    // error budget: the derivation in k_chamfer_f16 (the ranking value and its operands are the same)
-    const double pn2 = fma(pz[g], pz[g], fma(py[g], py[g], px[g] * px[g]));
-    const double S = (double)CHF_SCALE, PT = S * (sqrt(pn2) + tmax);
-    const double eps = 0x1.0p-19 * PT * PT + 0x1.0p-10 * PT;
+    const double pn2 = fma(rk.pz[g], rk.pz[g], fma(rk.py[g], rk.py[g], rk.px[g] * rk.px[g]));
+    const double S = (double)CHF_SCALE, eps = chf_eps(pn2, tmax);
+    // vouching with a strict < (k_chamfer_f16: <=): the row is returned, and an unevaluated row that ties could be the smaller
     double e;
     int er;
-    eval_tile(g, t1[g], e, er);
+    eval_tile(g, rk.t1[g], e, er);
     pair_min(e, er);
-    float rest = fminf(b2[g], __shfl_xor(b2[g], 32));     // smallest unevaluated tile minimum of the source
+    float rest = fminf(rk.b2[g], __shfl_xor(rk.b2[g], 32));     // smallest unevaluated tile minimum of the source
     bool ok = rest == INFINITY || (e - pn2) * S * S < (double)rest - eps;
     if (__any(!ok)) {
       double e2 = INFINITY;
       int er2 = 0x7fffffff;
-      if (!ok) eval_tile(g, t2[g], e2, er2);
+      if (!ok) eval_tile(g, rk.t2[g], e2, er2);
       pair_min(e2, er2);
       if (!ok) {
         if (e2 < e || (e2 == e && er2 < er)) {
           e = e2;
           er = er2;
         }
-        rest = fminf(b3[g], __shfl_xor(b3[g], 32));
+        rest = fminf(rk.b3[g], __shfl_xor(rk.b3[g], 32));
         ok = rest == INFINITY || (e - pn2) * S * S < (double)rest - eps;
       }
     }
@@ -282,7 +176,7 @@ __global__ __launch_bounds__(256) void k_icp_f16(const IcpWork* __restrict__ wor
     }
   }
   if (wbad) return;   // block-uniform
-  const double mpx = half ? px[1] : px[0], mpy = half ? py[1] : py[0], mpz = half ? pz[1] : pz[0];
+  const double mpx = half ? rk.px[1] : rk.px[0], mpy = half ? rk.py[1] : rk.py[0], mpz = half ? rk.pz[1] : rk.pz[0];
   const bool active = tid < wk.sn;   // sloc of (wave, g = half, col) = tid
   const bool kept = active && my_row != 0x7fffffff && my_e < thr2;
   float4 q = make_float4(0.f, 0.f, 0.f, 0.f);

@@ -1,6 +1,8 @@
 // What the k-NN units (knn.h: knn.hip, knn_exact.hip, knn_f16.hip), topk.hip, chamfer.hip, hardneg.hip and two ICP units
-// (icp_assoc.hip: the kernels' side, icp.hip: the driver's) share: the matrix-core operand types, the f16 hi / lo cut, the host helpers of their drivers, and the two kernels that two
-// of them launch (each defined once, in one unit, and reached from the other through an ordinary host function).
+// (icp_assoc.hip: the kernels' side, icp.hip: the driver's) share: the matrix-core operand types, the f16 hi / lo cut, the
+// KNF_* scan of 16-d features, the host helpers of their drivers, and the two kernels that two of them launch (each defined
+// once, in one unit, and reached from the other through an ordinary host function).  The scan of 3-d points that
+// chamfer.hip and the ICP units share is chf_rank.h, on top of this header.
 #pragma once
 #include <stdlib.h>
 
@@ -177,15 +179,6 @@ inline bool env_first_is(const char* name, char c) {
   const char* e = getenv(name);
   return e && e[0] == c;
 }
-
-// The f16 image of 3-d target rows that k_chamfer_f16 (chamfer.hip) and k_icp_f16 (icp_assoc.hip) rank on: row j =
-// [th(3) | tl(3) | th(3) | 0] of the coordinates scaled by CHF_SCALE, tn32[j] = |S t|^2, t4f[j] = (x, y, z, 0).
-constexpr int CHF_PITCH = 24;     // halfs per image row (48 B: conflict-free ds_read_b128 fragments)
-constexpr int CHF_ROWS = 256;     // target rows per LDS stage (8 MFMA row tiles)
-constexpr int CHF_NG = 2;         // 32-source groups per wave
-constexpr float CHF_SCALE = 512.0f;
-// k_chamfer_pack16 (chamfer.hip) over rows [0, n_pad): rows [n, n_pad) are zero with tn32 = +inf.  Launch only.
-void chamfer_pack16(const float* d_tgt, int64_t n, int64_t n_pad, _Float16* img, float* tn32, float4* t4f, hipStream_t s);
 
 // out[i] = sum_c X[i, c]^2, one f64 fma chain per row (k_row_norms, topk.hip).  Launch only: the caller's
 // CS_LAUNCH_CHECK covers it.

@@ -84,6 +84,30 @@ __device__ __forceinline__ bool key_less(unsigned long long da, int ia, unsigned
   return da < db || (da == db && ia < ib);
 }
 
+// Bitonic sort of the n (a power of two) keys (sd[i], si[i]) in LDS, ascending by key_less, by the 256 threads of the
+// workgroup.  The keys are visible to the workgroup before the call (a barrier) and sorted for all of it after.
+__device__ __forceinline__ void bitonic_sort_keys(unsigned long long* sd, int* si, int n, int tid) {
+  for (int size = 2; size <= n; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int t = tid; t < n / 2; t += 256) {
+        const int lo = (t / stride) * stride * 2 + (t % stride);
+        const int hi = lo + stride;
+        const bool up = ((lo & size) == 0);
+        const unsigned long long dl = sd[lo], dh = sd[hi];
+        const int il = si[lo], ih = si[hi];
+        const bool swap = up ? key_less(dh, ih, dl, il) : key_less(dl, il, dh, ih);
+        if (swap) {
+          sd[lo] = dh;
+          si[lo] = ih;
+          sd[hi] = dl;
+          si[hi] = il;
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
 // One block per query: merge the carried top-k with a slab of squared distances by a bitonic sort
 // of (distance bits, index) in LDS.  carry_* hold k entries per query (distance = +inf when unset).
 __global__ __launch_bounds__(256) void k_row_topk(const double* __restrict__ D2, int64_t x_count,
@@ -116,25 +140,7 @@ __global__ __launch_bounds__(256) void k_row_topk(const double* __restrict__ D2,
       si[i] = iv;
     }
     __syncthreads();
-    for (int size = 2; size <= TK_CAP; size <<= 1) {
-      for (int stride = size >> 1; stride > 0; stride >>= 1) {
-        for (int t = tid; t < TK_CAP / 2; t += 256) {
-          int lo = (t / stride) * stride * 2 + (t % stride);
-          int hi = lo + stride;
-          bool up = ((lo & size) == 0);
-          unsigned long long dl = sd[lo], dh = sd[hi];
-          int il = si[lo], ih = si[hi];
-          bool swap = up ? key_less(dh, ih, dl, il) : key_less(dl, il, dh, ih);
-          if (swap) {
-            sd[lo] = dh;
-            si[lo] = ih;
-            sd[hi] = dl;
-            si[hi] = il;
-          }
-        }
-        __syncthreads();
-      }
-    }
+    bitonic_sort_keys(sd, si, TK_CAP, tid);
     for (int i = tid; i < k; i += 256) {
       carry_d[qi * k + i] = sd[i];
       carry_i[qi * k + i] = si[i];
@@ -259,6 +265,7 @@ __global__ __launch_bounds__(256) void k_topk_mfma(const float* __restrict__ Q, 
         double dist = INFINITY;
         if (row < xe) dist = fma(-2.0, acc[t][r], my_qn + xn[row]);
         if (dist < bd[TKM_KK - 1]) {
+          // (knf_insert's loop in f64, on purpose: with knf_insert generic over the value type this kernel grew from 3256 to 5511 instructions)
           double cd = dist;
           int ci = (int)row;
           bool carry = false;
@@ -357,25 +364,7 @@ __global__ __launch_bounds__(256) void k_topk_rescore(const float* __restrict__ 
     }
   }
   __syncthreads();
-  for (int size = 2; size <= P; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = tid; t < P / 2; t += 256) {
-        const int lo = (t / stride) * stride * 2 + (t % stride);
-        const int hi = lo + stride;
-        const bool up = ((lo & size) == 0);
-        const unsigned long long dl = sd[lo], dh = sd[hi];
-        const int il = si[lo], ih = si[hi];
-        const bool swap = up ? key_less(dh, ih, dl, il) : key_less(dl, il, dh, ih);
-        if (swap) {
-          sd[lo] = dh;
-          si[lo] = ih;
-          sd[hi] = dl;
-          si[hi] = il;
-        }
-      }
-      __syncthreads();
-    }
-  }
+  bitonic_sort_keys(sd, si, P, tid);
   for (int i = tid; i < k; i += 256) {
     carry_d[qi * k + i] = sd[i];
     carry_i[qi * k + i] = si[i];
@@ -438,10 +427,7 @@ __global__ void k_tkf_pack(const float* __restrict__ X, int64_t n, int64_t n_pad
 
 __global__ void k_max_bits(const double* __restrict__ v, int64_t n, unsigned* __restrict__ out) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  float m = i < n ? __double2float_ru(v[i]) : 0.f;
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
-  if ((threadIdx.x & 63) == 0 && m > 0.f) atomicMax(out, __float_as_uint(m));  // non-negative floats order like uints
+  knf_seg_max(i < n ? __double2float_ru(v[i]) : 0.f, out);
 }
 
 // work item = (catalog split, query tile of TKF_QT); 512 threads; dynamic LDS: 2 stages + 2 x TKF_ROWS floats.

@@ -111,6 +111,34 @@ def assert_eight_knn_kernels():
     assert "hipcub" not in "".join(units[n] for n in KNN_UNITS if n != "knn_f16.hip")
 
 
+# ---- the 3-d f16 ranking scan's source text ----------------------------------------------------------------------
+CHAMFER_KERNELS = ["k_chamfer", "k_chamfer2", "k_chamfer_f16", "k_chamfer_finish", "k_chamfer_mfma", "k_chamfer_pack",
+                   "k_chamfer_pack16"]
+
+
+def assert_one_chf_rank_scan():
+    """k_chamfer_f16 and k_icp_f16 share ONE scan: the f16 MFMA over the CHF_PITCH image stands in chf_rank.h and in neither
+    kernel's file, the CHF_* constants are defined in one file, and chamfer.hip defines its seven kernels, each once."""
+    import glob
+    import os
+    import re
+
+    from corsair_amd import _lib
+
+    csrc = os.path.join(os.path.dirname(os.path.abspath(_lib.__file__)), "csrc")
+    text = {os.path.basename(p): open(p).read() for ext in ("*.h", "*.hip") for p in glob.glob(os.path.join(csrc, ext))}
+    mfma = "__builtin_amdgcn_mfma_f32_32x32x16_f16"
+    assert mfma in text["chf_rank.h"] and "CHF_PITCH" in text["chf_rank.h"]
+    assert mfma not in text["chamfer.hip"] and mfma not in text["icp_assoc.hip"]
+    define = r"constexpr[^;\n]*?\b(CHF_\w+)\s*=|#\s*define\s+(CHF_\w+)"
+    defined = {n: sorted(a or b for a, b in re.findall(define, t)) for n, t in text.items()}
+    assert {n: d for n, d in defined.items() if d} == {"chf_rank.h": ["CHF_NG", "CHF_PITCH", "CHF_ROWS", "CHF_SCALE"]}
+    kernels = re.findall(r"^__global__ [^\n]*?void (k_\w+)\(", text["chamfer.hip"], flags=re.M)
+    assert sorted(kernels) == CHAMFER_KERNELS
+    assert text["chamfer.hip"].count("__global__") == len(CHAMFER_KERNELS)
+    assert "__global__" not in text["chf_rank.h"]
+
+
 # ---- operator-level contract tests: column views of wider buffers ------------------------------------------
 # A quiet NaN whose payload no arithmetic produces: a buffer filled with it shows both a stray WRITE (the bits
 # change) and a stray READ (a NaN reaches the result).
