@@ -601,6 +601,64 @@ def normals_stats(reset=False):
     return int(out[0]), int(out[1])
 
 
+def knn_mean_dist(xyz, offsets, k=20):
+    """cs_knn_mean_dist: f64 [n] device, the mean distance of every row of packed clouds (host offset list) to the k
+    nearest rows of its own segment, itself included (Open3D's average); 2 <= k <= 32.  NaN for a row with a non-finite
+    coordinate.  The semantics are the header comment of cs_knn_mean_dist.  No host wait."""
+    xyz = _packed_points(xyz, offsets, "knn_mean_dist")
+    out = torch.empty(xyz.shape[0], dtype=torch.float64, device=xyz.device)
+    check(_lib.load().cs_knn_mean_dist(ptr(xyz), i64_array(offsets), len(offsets) - 1, int(k), ptr(out), stream_ptr()))
+    return out
+
+
+def outlier_statistical(xyz, offsets, k=20, std_ratio=2.0):
+    """Open3D's remove_statistical_outlier(k, std_ratio) per segment: cs_knn_mean_dist, then cs_outlier_statistical.
+    Returns (keep bool [n], stat f64 [n_seg,4] = (n_valid, mu, sigma, tau) per segment), both on the device; a row is
+    kept when 0 < mean < tau = mu + std_ratio * sigma.  The statistic is an exact integer sum: a permuted segment gives
+    the permuted mask and the same `stat` bits.  No host wait."""
+    mean = knn_mean_dist(xyz, offsets, k)
+    n_seg = len(offsets) - 1
+    keep = torch.zeros(mean.shape[0], dtype=torch.uint8, device=mean.device)
+    stat = torch.zeros((n_seg, 4), dtype=torch.float64, device=mean.device)
+    check(_lib.load().cs_outlier_statistical(ptr(mean), i64_array(offsets), n_seg, float(std_ratio), ptr(keep), ptr(stat),
+                                             stream_ptr()))
+    return keep.bool(), stat
+
+
+def outlier_radius(xyz, offsets, radius, nb_points):
+    """Open3D's remove_radius_outlier(nb_points, radius) per segment, cs_outlier_radius: (keep bool [n], count int32 [n])
+    on the device; count = the rows of the segment strictly inside `radius`, the row itself included, and a row is kept
+    when count > nb_points.  No host wait."""
+    xyz = _packed_points(xyz, offsets, "outlier_radius")
+    count = torch.zeros(xyz.shape[0], dtype=torch.int32, device=xyz.device)
+    keep = torch.zeros(xyz.shape[0], dtype=torch.uint8, device=xyz.device)
+    check(_lib.load().cs_outlier_radius(ptr(xyz), i64_array(offsets), len(offsets) - 1, float(radius), int(nb_points),
+                                        ptr(count), ptr(keep), stream_ptr()))
+    return keep.bool(), count
+
+
+def outlier_stats(reset=False):
+    """cs_outlier_stats: (rows answered by a cell-grid path, of those recomputed by the exhaustive scan); counts only
+    under CS_OUTLIER_STATS=1."""
+    out = (ctypes.c_uint64 * 2)()
+    _lib.load().cs_outlier_stats(out, 1 if reset else 0)
+    return int(out[0]), int(out[1])
+
+
+def select_rows(keep, offsets):
+    """The rows a mask keeps, as (idx int64 [m] device, ascending; new host offsets): plain torch, and the only place where
+    the filters wait for the device (the kept rows per segment come to the host, as voxelize's offsets do)."""
+    keep = keep.bool()
+    if keep.dim() != 1 or len(offsets) < 1 or int(offsets[-1]) > keep.shape[0]:
+        raise ValueError("select_rows: keep must be [n] and cover the offset table")
+    csum = torch.cat([torch.zeros(1, dtype=torch.int64, device=keep.device), torch.cumsum(keep.to(torch.int64), 0)])
+    at = torch.as_tensor([int(o) for o in offsets], dtype=torch.int64, device=keep.device)
+    cnt = (csum[at] - csum[at[0]]).cpu().tolist()
+    lo, hi = int(offsets[0]), int(offsets[-1])
+    idx = torch.nonzero(keep[lo:hi], as_tuple=False)[:, 0] + lo
+    return idx, [int(c) for c in cnt]
+
+
 def icp_batch(src, soff, tgt, toff, src_seg, tgt_seg, T0, max_dist, max_iter=30, relative_fitness=1e-6,
               relative_rmse=1e-6, return_corr=False, tgt_normals=None, kernel="l2", kernel_scale=None, with_scaling=False,
               scale_bounds=(0.5, 2.0), *, estimation=None, src_normals=None, gicp_epsilon=1e-3):

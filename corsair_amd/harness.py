@@ -26,6 +26,8 @@ from .utils.eval_pose import eval_pose
 ICP_KERNEL_NAMES = tuple(B.ICP_KERNELS)       # "l2", "huber", "cauchy", "tukey"
 VERIFY_SCORES = ("symmetric", "forward")
 VERIFY_MAX_K = 32
+SCAN_FILTERS = ("none", "statistical", "radius")
+SCAN_FILTER_MIN_ROWS = 10      # ransac_n: a cloud the filter would leave with fewer rows keeps all of them
 
 
 @dataclass
@@ -81,6 +83,32 @@ class Config:
     # NEITHER DEFAULT HAS BEEN TUNED on real scans: no K is recommended, and which score suits partial scans is not measured
     verify_top_k: int = 0
     verify_score: str = "symmetric"
+    # cleaning of RAW QUERY scans before the network sees them (embed_clouds(scan_filter=True)), on the f32 origins
+    # after voxelisation: "none" (the default, the reference's behaviour), "statistical" (cs_knn_mean_dist +
+    # cs_outlier_statistical, Open3D's remove_statistical_outlier) or "radius" (cs_outlier_radius, remove_radius_outlier).
+    # scan_filter_k = 20 and scan_filter_std = 2.0 are the values of Open3D's tutorial, UNTUNED here
+    scan_filter: str = "none"
+    scan_filter_k: int = 20
+    scan_filter_std: float = 2.0
+    # in VOXELS (the radius is scan_filter_radius * voxel_size): 2.5 is the radius inside which DESIGN 15 counted 12 - 24 rows
+    # of a voxelised surface.  UNTUNED, and so is scan_filter_min_nb = 4 (a row is kept with MORE than that many rows inside
+    # the radius, itself included)
+    scan_filter_radius: float = 2.5
+    scan_filter_min_nb: int = 4
+
+    def check_scan_filter(self):
+        if self.scan_filter not in SCAN_FILTERS:
+            raise ValueError("Config.scan_filter must be one of %s, got %r" % (SCAN_FILTERS, self.scan_filter))
+        k = self.scan_filter_k
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 2 <= int(k) <= 32:
+            raise ValueError("Config.scan_filter_k must be an integer in [2, 32], got %r" % (k,))
+        if not 0.0 <= float(self.scan_filter_std) < float("inf"):
+            raise ValueError("Config.scan_filter_std must be finite and >= 0, got %r" % (self.scan_filter_std,))
+        if not 0.0 < float(self.scan_filter_radius) < float("inf"):
+            raise ValueError("Config.scan_filter_radius must be positive and finite, got %r" % (self.scan_filter_radius,))
+        nb = self.scan_filter_min_nb
+        if isinstance(nb, bool) or not isinstance(nb, (int, np.integer)) or int(nb) < 0:
+            raise ValueError("Config.scan_filter_min_nb must be an integer >= 0, got %r" % (nb,))
 
     def verify_k(self):
         """Candidates per query that are registered and re-ranked; 0 when the verification is off."""
@@ -175,19 +203,49 @@ class Pipeline:
         self.cfg = config or Config()
         self.device = torch.device(device)
         self.engine = E.ResUNetEngine(state_dict, embedding_state_dict, device=self.device)
+        self.scan_filter_stat = {"rows_in": 0, "rows_kept": 0, "clouds_skipped": 0}     # filter_scan adds to it
 
     # ---- feature extraction (evaluation.py:213-269) ----------------------------------------------
-    def embed_batch(self, xyz, offsets):
+    def embed_batch(self, xyz, offsets, scan_filter=False):
         """xyz f32 [n,3] device (concatenated raw clouds, already normalised), offsets host list.
         Returns an EmbeddedSet for the batch."""
-        return self.embed_batch_raw(xyz, offsets, self.cfg.voxel_size)
+        return self.embed_batch_raw(xyz, offsets, self.cfg.voxel_size, scan_filter)
 
-    def embed_batch_raw(self, xyz, offsets, voxel_size):
+    def filter_scan(self, origin, offsets, voxel_size):
+        """The configured scan filter (Config.scan_filter) on packed f32 origins: (idx int64 [m] device or None
+        when every row stays, new host offsets).  A cloud that would be left with fewer than SCAN_FILTER_MIN_ROWS rows keeps
+        all of its rows.  Adds to self.scan_filter_stat.  One host wait (backend.select_rows)."""
+        c = self.cfg
+        c.check_scan_filter()
+        if c.scan_filter == "statistical":
+            mask, _ = B.outlier_statistical(origin, offsets, int(c.scan_filter_k), float(c.scan_filter_std))
+        else:
+            mask, _ = B.outlier_radius(origin, offsets, float(c.scan_filter_radius) * float(voxel_size),
+                                       int(c.scan_filter_min_nb))
+        idx, new_off = B.select_rows(mask, offsets)
+        short = [p for p in range(len(offsets) - 1)
+                 if new_off[p + 1] - new_off[p] < SCAN_FILTER_MIN_ROWS and new_off[p + 1] - new_off[p] < offsets[p + 1] - offsets[p]]
+        if short:
+            for p in short:
+                mask[offsets[p]:offsets[p + 1]] = True
+            idx, new_off = B.select_rows(mask, offsets)
+        st = self.scan_filter_stat
+        st["rows_in"] += int(offsets[-1] - offsets[0])
+        st["rows_kept"] += int(new_off[-1])
+        st["clouds_skipped"] += len(short)
+        return (None if new_off[-1] == offsets[-1] - offsets[0] else idx), new_off
+
+    def embed_batch_raw(self, xyz, offsets, voxel_size, scan_filter=False):
         """xyz f32 or f64: quantised in its own type (backend.voxelize); the kept points of an f64 cloud
         become f32 origins AFTER the selection (evaluation-shapenet.py:103-105; the collate of
-        datasets/ChairDataset.py:204-237 does the same to the f64 `rot_coords`)."""
+        datasets/ChairDataset.py:204-237 does the same to the f64 `rot_coords`).  scan_filter: when the configuration
+        names a filter (Config.scan_filter), it runs on those origins and the voxels it drops never reach the network."""
         keep, grid, out_off = B.voxelize(xyz, offsets, voxel_size)
         origin = xyz[keep].to(torch.float32)
+        if scan_filter and self.cfg.scan_filter != "none":
+            sel, out_off = self.filter_scan(origin, out_off, voxel_size)
+            if sel is not None:
+                origin, grid = origin[sel], grid[sel]
         feats = torch.ones((grid.shape[0], 1), dtype=torch.float32, device=xyz.device)
         out, feat8, maps = self.engine.forward(grid, feats, n_batch=len(offsets) - 1)
         return EmbeddedSet(out, origin, out_off, self._descriptors(feat8, maps, len(offsets) - 1))
@@ -220,10 +278,11 @@ class Pipeline:
         out, feat8, maps = self.engine.forward(grid, feats, n_batch=base)
         return EmbeddedSet(out, torch.cat(origins), out_off, self._descriptors(feat8, maps, base))
 
-    def embed_clouds(self, clouds, batch_size=None):
+    def embed_clouds(self, clouds, batch_size=None, scan_filter=False):
         """clouds: list of f32 or f64 [n,3] NumPy arrays (host), one type per call: a cloud is quantised in
         the type it arrives in, so promoting or narrowing here would move points across voxel boundaries.
-        Forwards of batch_size clouds (default cfg.embed_batch_size; the reference's DataLoader: 32 -- same rows either way)."""
+        Forwards of batch_size clouds (default cfg.embed_batch_size; the reference's DataLoader: 32 -- same rows either way).
+        scan_filter: the clouds are raw scans, cleaned by the configured filter (Config.scan_filter; "none" = nothing runs)."""
         bs = batch_size or self.cfg.embed_batch_size
         kinds = {np.asarray(c).dtype for c in clouds}
         if len(kinds) > 1 or not kinds <= {np.dtype(np.float32), np.dtype(np.float64)}:
@@ -233,7 +292,7 @@ class Pipeline:
             chunk = clouds[i:i + bs]
             xyz = torch.from_numpy(np.concatenate(chunk, 0)).to(self.device)
             off = np.concatenate([[0], np.cumsum([len(c) for c in chunk])]).tolist()
-            sets.append(self.embed_batch(xyz, off))
+            sets.append(self.embed_batch(xyz, off, True) if scan_filter else self.embed_batch(xyz, off))
         return concat_sets(sets)
 
     def voxel_counts(self, clouds, chunk=64):
@@ -467,7 +526,14 @@ def run_eval(pipe, catalog, queries, best_match, table, base_T, lib_T, syms, cat
     bs = batch_size or cfg.batch_size
     ebs = cfg.embed_batch_size   # (batch_size is the REGISTRATION batch; the network's forward has its own size)
     cat = catalog if isinstance(catalog, EmbeddedSet) else pipe.embed_clouds(catalog, ebs)
-    qs = queries if isinstance(queries, EmbeddedSet) else pipe.embed_clouds(queries, ebs)
+    # raw queries alone are cleaned by the configured scan filter: never the catalog, never an EmbeddedSet
+    filt = getattr(cfg, "scan_filter", "none") != "none" and not isinstance(queries, EmbeddedSet)
+    if filt:
+        cfg.check_scan_filter()
+        pipe.scan_filter_stat = {"rows_in": 0, "rows_kept": 0, "clouds_skipped": 0}
+        qs = pipe.embed_clouds(queries, ebs, scan_filter=True)
+    else:
+        qs = queries if isinstance(queries, EmbeddedSet) else pipe.embed_clouds(queries, ebs)
     Q = len(qs)
     best_match = np.asarray(best_match).astype(np.int64)
     syms = np.asarray(syms)
@@ -480,6 +546,8 @@ def run_eval(pipe, catalog, queries, best_match, table, base_T, lib_T, syms, cat
     else:
         stat = retrieval_stat(pipe, qs.desc, cat.desc, best_match, table)
 
+    if filt:
+        stat["scan_filter"] = dict(pipe.scan_filter_stat)
     per_query = None if (ignore_cache or cache_dir is None) else \
         C_.load_results(cache_dir, category, register_top1, icp=cfg.icp_max_iter > 0,
                         icp_scale=bool(getattr(cfg, "icp_with_scaling", False)), **({"verify": K} if K else {}))
@@ -813,6 +881,15 @@ def build_parser():
                          "registered pose (cs_chamfer_2dir); 0 and 1 = off, 2..32 (untuned; not with --register-gt)")
     ap.add_argument("--verify-score", default="symmetric", choices=list(VERIFY_SCORES),
                     help="score of --verify-top-k: forward + backward Chamfer, or forward alone (for partial scans; untuned)")
+    ap.add_argument("--scan-filter", default="none", choices=list(SCAN_FILTERS),
+                    help="clean every raw query scan after voxelisation: Open3D's statistical or radius outlier removal "
+                         "(cs_outlier_statistical / cs_outlier_radius); never the catalog.  Untuned; not recorded in the cache")
+    ap.add_argument("--scan-filter-k", type=int, default=20, help="neighbours of --scan-filter statistical, 2..32 (untuned)")
+    ap.add_argument("--scan-filter-std", type=float, default=2.0,
+                    help="a row is dropped when its mean neighbour distance reaches mean + STD * deviation (untuned)")
+    ap.add_argument("--scan-filter-radius", type=float, default=2.5, help="radius of --scan-filter radius, in voxels (untuned)")
+    ap.add_argument("--scan-filter-min-nb", type=int, default=4,
+                    help="--scan-filter radius keeps a row with MORE than this many rows inside the radius, itself included")
     ap.add_argument("--in-flight", type=int, default=3, help="registration batches in flight (host threads x HIP streams)")
     ap.add_argument("--device", default="cuda", choices=["cuda"], help="there is no CPU path")
     return ap
@@ -841,8 +918,11 @@ def main(argv=None):
                  icp_estimation=a.icp_estimation, icp_normal_k=a.icp_normal_k, icp_kernel=a.icp_kernel,
                  icp_kernel_scale=a.icp_kernel_scale, icp_normal_radius=a.icp_normal_radius,
                  icp_with_scaling=a.icp_with_scaling, icp_scale_bounds=(a.icp_scale_min, a.icp_scale_max),
-                 registration=a.registration, fgr_mu_floor=a.fgr_mu_floor, gicp_epsilon=a.gicp_epsilon)
+                 registration=a.registration, fgr_mu_floor=a.fgr_mu_floor, gicp_epsilon=a.gicp_epsilon,
+                 scan_filter=a.scan_filter, scan_filter_k=a.scan_filter_k, scan_filter_std=a.scan_filter_std,
+                 scan_filter_radius=a.scan_filter_radius, scan_filter_min_nb=a.scan_filter_min_nb)
     cfg.check_icp()
+    cfg.check_scan_filter()
     pipe = Pipeline(sd, esd, device=a.device, config=cfg)
     cad_names, catalog = load_cloud_dir(a.catalog_dir, a.n_points, "catalog")
     _, queries = load_cloud_dir(a.query_dir, a.n_points, "queries")

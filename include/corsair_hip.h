@@ -1017,10 +1017,81 @@ int cs_fpfh(const float* d_xyz, const float* d_normal, const int64_t* h_off, int
 void cs_fpfh_stats(uint64_t out[2], int reset);
 
 /* ------------------------------------------------------------------------------------------
+ * Scan cleaning: the two outlier filters of [O3D-knowledge] Open3D, remove_statistical_outlier(nb_neighbors,
+ * std_ratio) and remove_radius_outlier(nb_points, radius), as remembered and not checked against an installation; where the
+ * project's habits differ they hold.  The reference has no such step, so these comments are the specification and
+ * tests/outlier_ref.py restates them bit for bit.  Every operation is ONE IEEE f64 operation in the order the parentheses
+ * give, or an explicit fma; nothing is contracted; only + - * / sqrt fma rint, scalings by powers of two, integer
+ * arithmetic and comparisons appear.  Common to the three calls: d_xyz f32 [n,3]; h_off int64 [n_seg + 1] host offsets;
+ * neighbours are rows of the SAME segment; d2 = fma(dz, dz, fma(dy, dy, dx * dx)), d. = (double)x_j. - (double)x_i.
+ * (cs_estimate_normals' chain); every threshold is STRICT; a NaN or +inf d2 is never a neighbour.  n_seg = 0 and empty
+ * segments are legal.  Refused by all three (CS_ERR_INVALID): a NULL offset table, a negative count, offsets that decrease,
+ * a NULL array while a row exists; (CS_ERR_UNSUPPORTED): a segment of 2^31 rows or more.  Everything is enqueued on
+ * `stream`; no host wait (CS_OUTLIER_STATS=1 adds one at the end of cs_knn_mean_dist); the only atomics are integer.
+ * Profile family "outlier", one scope per call.
+ *
+ * cs_knn_mean_dist: d_mean f64 [n]; k in [2, 32] (else CS_ERR_UNSUPPORTED).
+ *   Row i: among the rows j of its segment with d2 < +inf, itself included (d2 = 0; [O3D-knowledge]: the average Open3D
+ *     forms counts the point itself), the c = min(k, found) smallest d2, d2_(0) <= d2_(1) <= ...;
+ *     mean_i = (((+0 + sqrt(d2_(0))) + sqrt(d2_(1))) + ...) / (double)c.
+ *     Rows that tie in d2 contribute equal terms: the value is a function of the multiset of the row's d2 values and does
+ *     not depend on the order of the rows inside the segment, on batch neighbours, the launch shape or the run.
+ *   A row with a non-finite coordinate finds nothing (c = 0) and gets the quiet NaN 0x7ff8000000000000.
+ *   Paths, the same bits: the exhaustive scan of the row's segment (cs_estimate_normals' kernel with a list of d2 alone) is
+ *     the definition, the whole path under CS_OUTLIER_GRID=0 (read per call) and the path of every segment of at most 1024
+ *     rows.  Otherwise cs_estimate_normals' cell grid (the same code: the cell from the segment's bounding box, the 27
+ *     cells, the voucher): a list is accepted only when its k-th d2 lies strictly below c^2 (1 - 2^-30); every other row is
+ *     compacted into a list and recomputed by the scan, one wave per row; segments the device keeps off the grid (a box
+ *     of zero area or one that is not finite, a cell index at the clamp) are answered by the exhaustive kernel.
+ *
+ * cs_outlier_statistical: d_mean f64 [n] (cs_knn_mean_dist's); std_ratio finite and >= 0 (else CS_ERR_INVALID);
+ *   d_keep u8 [n] (0 / 1); d_stat f64 [n_seg,4] = (n_valid, mu, sigma, tau) per segment, written for empty segments too.
+ *   The VALID rows of a segment are those with 0 <= mean_i < +inf (cs_knn_mean_dist writes no negative mean; a caller's
+ *     own is treated like a NaN one); n_valid = their number.
+ *   M = the maximum of the valid means (exact and free of the order).  M = f 2^e with f in [0.5, 1) (frexp), and
+ *     s = min(31 - e, 1023): the minimum keeps 2^s inside the f64 range for M < 2^-992, where the integers below are
+ *     smaller than 2^31 and the statistic coarser; no distance between f32 rows comes near.  M = 0: s = 31.
+ *   q_i = (uint64)rint(mean_i * 2^s) (round to nearest even; the scaling by a power of two is exact), at most 2^31.
+ *   Three unsigned 64-bit integer sums over the valid rows: S1 = sum q_i, S2lo = sum (q_i^2 mod 2^32),
+ *     S2hi = sum floor(q_i^2 / 2^32); each stays below 2^63 for fewer than 2^31 rows.
+ *   With n = n_valid, in this order:
+ *     mu = ((double)S1 / (double)n) * 2^-s when n >= 1 and M > 0, else 0;
+ *     sigma (the sample deviation): when n >= 2 and M > 0, in unsigned 128-bit integers S2 = S2hi * 2^32 + S2lo,
+ *       D = n * S2 - S1 * S1 (not negative; below 2^124), dhi = floor(D / 2^64), dlo = D mod 2^64,
+ *       dd = (double)dhi * 2^64 + (double)dlo,  den = (double)n * (double)(n - 1),  sigma = sqrt(dd / den) * 2^-s; else 0;
+ *     tau = fma(std_ratio, sigma, mu).
+ *     The conversions of 64-bit integers round to nearest even; the scalings by 2^-s are exact unless the result is
+ *     subnormal, where they round once.
+ *   keep_i = mean_i > 0 && mean_i < tau ([O3D-knowledge]: Open3D also drops a row whose average is 0, e.g. one of k or more
+ *     copies of a point).  A NaN mean is dropped.  M = 0 gives mu = sigma = tau = 0 and keeps nothing.
+ *   The four values are a pure function of the multiset of the segment's means: a permuted segment gives the permuted mask
+ *     and the SAME d_stat, bit for bit, on any launch shape (the integer sums commute; so does the maximum).
+ *
+ * cs_outlier_radius: radius finite and > 0, nb_points >= 0 (else CS_ERR_INVALID); d_count int32 [n]; d_keep u8 [n] or NULL.
+ *   count_i = the number of rows j of the segment, itself included, with d2 < radius * radius (one f64 product);
+ *     keep_i = count_i > nb_points ([O3D-knowledge]: Open3D's rule, whose radius search also returns the point itself; it
+ *     keeps a point AT the radius, which no measured input can tell apart and an integer lattice can).
+ *   A row with a non-finite coordinate gets 0.  A radius whose square overflows to +inf counts the segment's finite rows;
+ *     one whose square underflows to 0 counts nothing.
+ *   Paths, the same bits: the exhaustive scan is the definition, the whole path under CS_OUTLIER_GRID=0, the path of every
+ *     segment of at most 512 rows and of a radius of 1e300 or more; otherwise cs_estimate_normals_hybrid's cell grid (the
+ *     same code: cells of radius (1 + 2^-10), complete for d2 < radius^2 by the argument in cellgrid.h).
+ *
+ * cs_outlier_stats: out = {rows answered by a grid path, of those recomputed by the exhaustive scan}, counted only while
+ *   CS_OUTLIER_STATS=1 (read per call).  The radius grid is complete and recomputes nothing.
+ * ---------------------------------------------------------------------------------------- */
+int cs_knn_mean_dist(const float* d_xyz, const int64_t* h_off, int n_seg, int k, double* d_mean, void* stream);
+int cs_outlier_statistical(const double* d_mean, const int64_t* h_off, int n_seg, double std_ratio, uint8_t* d_keep,
+                           double* d_stat, void* stream);
+int cs_outlier_radius(const float* d_xyz, const int64_t* h_off, int n_seg, double radius, int nb_points, int32_t* d_count,
+                      uint8_t* d_keep, void* stream);
+void cs_outlier_stats(uint64_t out[2], int reset);
+
+/* ------------------------------------------------------------------------------------------
  * Profiling hooks for bench.py: when enabled the library brackets the launches of each named
  * kernel family with hipEvents on the launch stream and accumulates the elapsed time.
  * names: "conv", "ransac_eval", "ransac_pre", "ransac_hyp", "knn", "chamfer", "topk", "symcut",
- * "kmap", "loss", "hardneg", "icp", "normals", "fgr", "chamfer2", "fpfh", "orient".
+ * "kmap", "loss", "hardneg", "icp", "normals", "fgr", "chamfer2", "fpfh", "orient", "outlier".
  * ---------------------------------------------------------------------------------------- */
 void cs_prof_enable(int on);
 void cs_prof_reset(void);
