@@ -645,6 +645,43 @@ def outlier_stats(reset=False):
     return int(out[0]), int(out[1])
 
 
+def dbscan(xyz, offsets, eps, min_points):
+    """Open3D's cluster_dbscan(eps, min_points) per segment, cs_dbscan: (label int32 [n], count int32 [n]) on the device.
+    count = the rows of the segment strictly inside `eps`, the row itself included (outlier_radius' count); a row with
+    count >= min_points is a core row, the clusters are the connected components of the core rows, numbered 0, 1, ... by
+    their smallest row; a non-core row takes the label of its nearest core row inside eps (ties: the smaller row), every
+    other row -1.  The labels are a function of the segment alone.  The semantics are the header comment of cs_dbscan.
+    No host wait."""
+    xyz = _packed_points(xyz, offsets, "dbscan")
+    label = torch.full((xyz.shape[0],), -1, dtype=torch.int32, device=xyz.device)
+    count = torch.zeros(xyz.shape[0], dtype=torch.int32, device=xyz.device)
+    check(_lib.load().cs_dbscan(ptr(xyz), i64_array(offsets), len(offsets) - 1, float(eps), int(min_points), ptr(label),
+                                ptr(count), stream_ptr()))
+    return label, count
+
+
+def cluster_largest(label, offsets):
+    """cs_cluster_largest on the labels of `dbscan`: (keep bool [n], stat int32 [n_seg,3] = (clusters, id of the largest,
+    its size) per segment), both on the device; a row is kept when its label is the largest cluster's (core and border
+    rows count, ties go to the smaller id), and a segment without a cluster gives (0, -1, 0) and keeps nothing.  Integer
+    atomics only: the same values on any launch shape.  No host wait."""
+    label = _dev(label, torch.int32, "label").contiguous()
+    if label.dim() != 1 or len(offsets) < 1 or int(offsets[-1]) > label.shape[0]:
+        raise ValueError("cluster_largest: label must be [n] and cover the offset table")
+    n_seg = len(offsets) - 1
+    keep = torch.zeros(label.shape[0], dtype=torch.uint8, device=label.device)
+    stat = torch.zeros((n_seg, 3), dtype=torch.int32, device=label.device)
+    check(_lib.load().cs_cluster_largest(ptr(label), i64_array(offsets), n_seg, ptr(keep), ptr(stat), stream_ptr()))
+    return keep.bool(), stat
+
+
+def dbscan_stats(reset=False):
+    """cs_dbscan_stats: (rows answered by the cell-grid path, border rows); counts only under CS_DBSCAN_STATS=1."""
+    out = (ctypes.c_uint64 * 2)()
+    _lib.load().cs_dbscan_stats(out, 1 if reset else 0)
+    return int(out[0]), int(out[1])
+
+
 def select_rows(keep, offsets):
     """The rows a mask keeps, as (idx int64 [m] device, ascending; new host offsets): plain torch, and the only place where
     the filters wait for the device (the kept rows per segment come to the host, as voxelize's offsets do)."""

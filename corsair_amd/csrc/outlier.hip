@@ -10,6 +10,8 @@
 // count on the hybrid grid (complete by cellgrid.h's argument), the mean distance on the bounding-box grid with the k-NN
 // voucher (the argument above nrm_seg_of in normals.hip: a list whose k-th d2 lies strictly inside cov2 is the scan's);
 // rows the voucher refuses go to a redo list that k_out_mean_redo answers by the scan, one wave per row.
+// The radius count (k_out_count, k_out_count_grid), the work list and the offset check stand in outlier_count.h, which
+// dbscan.hip includes too: the count is cs_dbscan's first pass.
 #include <math.h>
 
 #include <algorithm>
@@ -18,26 +20,16 @@
 #include "cellgrid.h"
 #include "nn_common.h"
 #include "normals_grid.h"
+#include "outlier_count.h"
 
 namespace cs {
 namespace {
 
-constexpr int OUT_ROWS = 256;   // rows per workgroup
-constexpr int OUT_TT = 512;     // segment rows per LDS stage
 constexpr int OUT_REDO_BLOCKS = 2048;
 
-// A segment of fewer rows than this goes to the exhaustive kernel: NRM_GRID_MIN and NRM_KNN_GRID_MIN of normals.hip (one
-// and two LDS stages of the scan), taken over as they are.  They have not been tuned, there or here.
-constexpr int OUT_GRID_MIN = OUT_TT + 1;
+// A segment of fewer rows than this goes to the exhaustive mean-distance kernel: NRM_KNN_GRID_MIN of normals.hip (two LDS
+// stages of the scan), taken over as it is (OUT_GRID_MIN, the radius count's, is in outlier_count.h).  Not tuned.
 constexpr int OUT_KNN_GRID_MIN = 2 * OUT_TT + 1;
-
-struct OutWork {
-  int64_t seg0;   // first row of the segment (global)
-  int32_t sn;     // rows of the segment
-  int32_t r0;     // first row of this workgroup, local to the segment
-  int32_t seg;    // the segment (of the call, or of the chunk for a gated launch)
-  int32_t pad;
-};
 
 // d enters the ascending list; d < bd[KC - 1] is the caller's test.  Equal values are interchangeable: no tie rule.
 template <int KC>
@@ -65,11 +57,6 @@ __device__ __forceinline__ double out_mean(const double (&bd)[KC], int k) {
     }
   }
   return c ? sum / (double)c : __longlong_as_double(0x7ff8000000000000LL);
-}
-
-__device__ __forceinline__ double out_d2(const float* __restrict__ t, double x, double y, double z) {
-  const double dx = (double)t[0] - x, dy = (double)t[1] - y, dz = (double)t[2] - z;
-  return fma(dz, dz, fma(dy, dy, dx * dx));
 }
 
 // gate (optional): the workgroups of a segment that the grid answers (gate[wk.seg].cell > 0) leave at once.
@@ -105,35 +92,6 @@ __global__ __launch_bounds__(OUT_ROWS) void k_out_mean(const OutWork* __restrict
     }
   }
   if (active) mean[wk.seg0 + row] = out_mean<KC>(bd, k);
-}
-
-__global__ __launch_bounds__(OUT_ROWS) void k_out_count(const OutWork* __restrict__ work, const float* __restrict__ xyz,
-                                                        double r2, int nb_points, int32_t* __restrict__ count,
-                                                        uint8_t* __restrict__ keep) {
-  __shared__ float t_lds[OUT_TT * 3];
-  const OutWork wk = work[blockIdx.x];
-  const int tid = threadIdx.x;
-  const int row = wk.r0 + tid;
-  const bool active = row < wk.sn;
-  const float* seg = xyz + wk.seg0 * 3;
-  double x = 0, y = 0, z = 0;
-  if (active) {
-    x = (double)seg[3 * (int64_t)row + 0];
-    y = (double)seg[3 * (int64_t)row + 1];
-    z = (double)seg[3 * (int64_t)row + 2];
-  }
-  int c = 0;
-  for (int tbase = 0; tbase < wk.sn; tbase += OUT_TT) {
-    const int tcount = min(OUT_TT, wk.sn - tbase);
-    __syncthreads();
-    for (int i = tid; i < tcount * 3; i += OUT_ROWS) t_lds[i] = seg[(int64_t)tbase * 3 + i];
-    __syncthreads();
-    if (!active) continue;
-    for (int j = 0; j < tcount; ++j) c += out_d2(t_lds + 3 * j, x, y, z) < r2 ? 1 : 0;   // false for NaN, and for inf < inf
-  }
-  if (!active) return;
-  count[wk.seg0 + row] = c;
-  if (keep) keep[wk.seg0 + row] = c > nb_points ? 1 : 0;
 }
 
 // ---- the grid paths --------------------------------------------------------------------------------------------------
@@ -237,28 +195,6 @@ __global__ __launch_bounds__(64) void k_out_mean_redo(const int32_t* __restrict_
   }
 }
 
-// the hybrid grid (cells of radius (1 + 2^-10)) is complete for d2 < r2: nothing to vouch for, nothing to redo
-__global__ __launch_bounds__(OUT_ROWS) void k_out_count_grid(CellTable tb, const float* __restrict__ sxyz,
-                                                             const int32_t* __restrict__ sj,
-                                                             const uint64_t* __restrict__ skeys, int64_t m_total,
-                                                             const int64_t* __restrict__ off,
-                                                             const NrmSeg* __restrict__ segs, int nb_points,
-                                                             int32_t* __restrict__ count, uint8_t* __restrict__ keep) {
-  const int64_t m = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (m >= m_total) return;
-  const int p = (int)(skeys[m] >> 48);
-  const NrmSeg sg = segs[p];
-  if (!(sg.cell > 0.0)) return;
-  const double x = (double)sxyz[3 * m], y = (double)sxyz[3 * m + 1], z = (double)sxyz[3 * m + 2];
-  int c = 0;
-  cg_probe<3>(
-      tb, sxyz, p, x, y, z, sg.cell, sg.r2, [&](const float* t) { return out_d2(t, x, y, z); },
-      [&](double, int32_t) { ++c; });
-  const int64_t g = off[p] + sj[m];
-  count[g] = c;
-  if (keep) keep[g] = c > nb_points ? 1 : 0;
-}
-
 // ---- the statistic ---------------------------------------------------------------------------------------------------
 // acc = five u64 per segment, zeroed by the caller: [0] the bit pattern of M (non-negative doubles order like their bits),
 // [1] n_valid, [2] S1, [3] S2lo, [4] S2hi.  Integer atomics only: the same values for any order and launch shape.
@@ -354,24 +290,6 @@ __global__ __launch_bounds__(OUT_ROWS) void k_out_keep(const OutWork* __restrict
 // ---- host ------------------------------------------------------------------------------------------------------------
 std::atomic<unsigned long long> g_outlier_stats[2];
 
-void push_work(std::vector<OutWork>& work, int64_t seg0, int64_t sn, int seg) {
-  for (int64_t r = 0; r < sn; r += OUT_ROWS) work.push_back(OutWork{seg0, (int32_t)sn, (int32_t)r, (int32_t)seg, 0});
-}
-
-// checks the offset table; rows = the rows of the call
-int check_segments(const char* who, const int64_t* h_off, int n_seg, int64_t* rows) {
-  CS_REQUIRE(h_off, CS_ERR_INVALID, "%s: NULL offset table", who);
-  CS_REQUIRE(n_seg >= 0, CS_ERR_INVALID, "%s: negative segment count", who);
-  *rows = 0;
-  for (int sg = 0; sg < n_seg; ++sg) {
-    const int64_t sn = h_off[sg + 1] - h_off[sg];
-    CS_REQUIRE(h_off[sg] >= 0 && sn >= 0, CS_ERR_INVALID, "%s: bad segment %d", who, sg);
-    CS_REQUIRE(sn < (1LL << 31), CS_ERR_UNSUPPORTED, "%s: segment %d has 2^31 rows or more", who, sg);
-    *rows += sn;
-  }
-  return CS_OK;
-}
-
 void launch_mean(const OutWork* d_work, size_t n_work, const float* d_xyz, int k, double* d_mean, const NrmSeg* gate,
                  hipStream_t s) {
   const dim3 grid((unsigned)n_work), block(OUT_ROWS);
@@ -441,12 +359,8 @@ int grid_chunks(bool knn, const float* d_xyz, const int64_t* h_off, int n_seg, i
                 double* d_mean, int nb_points, int32_t* d_count, uint8_t* d_keep, unsigned long long* d_stats,
                 hipStream_t s) {
   for (int sg0 = 0; sg0 < n_seg;) {
-    int sg1 = sg0;
     bool any = false;
-    while (sg1 < n_seg && sg1 - sg0 < NRM_CHUNK_SEGS && (sg1 == sg0 || h_off[sg1 + 1] - h_off[sg0] <= NRM_CHUNK_ROWS)) {
-      any = any || h_off[sg1 + 1] - h_off[sg1] >= grid_min;
-      ++sg1;
-    }
+    const int sg1 = next_chunk(h_off, n_seg, sg0, grid_min, &any);
     if (any) {
       const int rc = grid_chunk(knn, d_xyz, h_off + sg0, sg1 - sg0, grid_min, cell, r2, k, d_mean, nb_points, d_count,
                                 d_keep, d_stats, s);

@@ -26,7 +26,7 @@ from .utils.eval_pose import eval_pose
 ICP_KERNEL_NAMES = tuple(B.ICP_KERNELS)       # "l2", "huber", "cauchy", "tukey"
 VERIFY_SCORES = ("symmetric", "forward")
 VERIFY_MAX_K = 32
-SCAN_FILTERS = ("none", "statistical", "radius")
+SCAN_FILTERS = ("none", "statistical", "radius", "cluster")
 SCAN_FILTER_MIN_ROWS = 10      # ransac_n: a cloud the filter would leave with fewer rows keeps all of them
 
 
@@ -95,6 +95,13 @@ class Config:
     # the radius, itself included)
     scan_filter_radius: float = 2.5
     scan_filter_min_nb: int = 4
+    # "cluster" (cs_dbscan + cs_cluster_largest, Open3D's cluster_dbscan): only the rows of the scan's LARGEST
+    # cluster stay, which also drops a dense patch of a neighbouring object that neither outlier filter can remove.
+    # scan_filter_eps is in VOXELS (eps = scan_filter_eps * voxel_size) and a row is a core row with scan_filter_min_points
+    # rows inside eps, itself included: 2.5 and 5 are the radius filter's defaults (its keep rule, count > 4).  Both are
+    # UNTUNED, NO REAL SCAN MEASURED
+    scan_filter_eps: float = 2.5
+    scan_filter_min_points: int = 5
 
     def check_scan_filter(self):
         if self.scan_filter not in SCAN_FILTERS:
@@ -109,6 +116,11 @@ class Config:
         nb = self.scan_filter_min_nb
         if isinstance(nb, bool) or not isinstance(nb, (int, np.integer)) or int(nb) < 0:
             raise ValueError("Config.scan_filter_min_nb must be an integer >= 0, got %r" % (nb,))
+        if not 0.0 < float(self.scan_filter_eps) < float("inf"):
+            raise ValueError("Config.scan_filter_eps must be positive and finite, got %r" % (self.scan_filter_eps,))
+        mp = self.scan_filter_min_points
+        if isinstance(mp, bool) or not isinstance(mp, (int, np.integer)) or int(mp) < 1:
+            raise ValueError("Config.scan_filter_min_points must be an integer >= 1, got %r" % (mp,))
 
     def verify_k(self):
         """Candidates per query that are registered and re-ranked; 0 when the verification is off."""
@@ -212,13 +224,16 @@ class Pipeline:
         return self.embed_batch_raw(xyz, offsets, self.cfg.voxel_size, scan_filter)
 
     def filter_scan(self, origin, offsets, voxel_size):
-        """The configured scan filter (Config.scan_filter, DESIGN 22) on packed f32 origins: (idx int64 [m] device or None
+        """The configured scan filter (Config.scan_filter, DESIGN 22 and 23) on packed f32 origins: (idx int64 [m] device or None
         when every row stays, new host offsets).  A cloud that would be left with fewer than SCAN_FILTER_MIN_ROWS rows keeps
         all of its rows.  Adds to self.scan_filter_stat.  One host wait (backend.select_rows)."""
         c = self.cfg
         c.check_scan_filter()
         if c.scan_filter == "statistical":
             mask, _ = B.outlier_statistical(origin, offsets, int(c.scan_filter_k), float(c.scan_filter_std))
+        elif c.scan_filter == "cluster":
+            label, _ = B.dbscan(origin, offsets, float(c.scan_filter_eps) * float(voxel_size), int(c.scan_filter_min_points))
+            mask, _ = B.cluster_largest(label, offsets)
         else:
             mask, _ = B.outlier_radius(origin, offsets, float(c.scan_filter_radius) * float(voxel_size),
                                        int(c.scan_filter_min_nb))
@@ -883,13 +898,19 @@ def build_parser():
                     help="score of --verify-top-k: forward + backward Chamfer, or forward alone (for partial scans; untuned)")
     ap.add_argument("--scan-filter", default="none", choices=list(SCAN_FILTERS),
                     help="clean every raw query scan after voxelisation: Open3D's statistical or radius outlier removal "
-                         "(cs_outlier_statistical / cs_outlier_radius); never the catalog.  Untuned; not recorded in the cache")
+                         "(cs_outlier_statistical / cs_outlier_radius), or the largest DBSCAN cluster alone (cs_dbscan / "
+                         "cs_cluster_largest); never the catalog.  Untuned; not recorded in the cache")
     ap.add_argument("--scan-filter-k", type=int, default=20, help="neighbours of --scan-filter statistical, 2..32 (untuned)")
     ap.add_argument("--scan-filter-std", type=float, default=2.0,
                     help="a row is dropped when its mean neighbour distance reaches mean + STD * deviation (untuned)")
     ap.add_argument("--scan-filter-radius", type=float, default=2.5, help="radius of --scan-filter radius, in voxels (untuned)")
     ap.add_argument("--scan-filter-min-nb", type=int, default=4,
                     help="--scan-filter radius keeps a row with MORE than this many rows inside the radius, itself included")
+    ap.add_argument("--scan-filter-eps", type=float, default=2.5,
+                    help="eps of --scan-filter cluster, in voxels (untuned, no real scan measured)")
+    ap.add_argument("--scan-filter-min-points", type=int, default=5,
+                    help="--scan-filter cluster: a row is a core row with this many rows inside eps, itself included "
+                         "(untuned, no real scan measured)")
     ap.add_argument("--in-flight", type=int, default=3, help="registration batches in flight (host threads x HIP streams)")
     ap.add_argument("--device", default="cuda", choices=["cuda"], help="there is no CPU path")
     return ap
@@ -920,7 +941,8 @@ def main(argv=None):
                  icp_with_scaling=a.icp_with_scaling, icp_scale_bounds=(a.icp_scale_min, a.icp_scale_max),
                  registration=a.registration, fgr_mu_floor=a.fgr_mu_floor, gicp_epsilon=a.gicp_epsilon,
                  scan_filter=a.scan_filter, scan_filter_k=a.scan_filter_k, scan_filter_std=a.scan_filter_std,
-                 scan_filter_radius=a.scan_filter_radius, scan_filter_min_nb=a.scan_filter_min_nb)
+                 scan_filter_radius=a.scan_filter_radius, scan_filter_min_nb=a.scan_filter_min_nb,
+                 scan_filter_eps=a.scan_filter_eps, scan_filter_min_points=a.scan_filter_min_points)
     cfg.check_icp()
     cfg.check_scan_filter()
     pipe = Pipeline(sd, esd, device=a.device, config=cfg)

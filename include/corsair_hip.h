@@ -1088,10 +1088,62 @@ int cs_outlier_radius(const float* d_xyz, const int64_t* h_off, int n_seg, doubl
 void cs_outlier_stats(uint64_t out[2], int reset);
 
 /* ------------------------------------------------------------------------------------------
+ * Scan clustering: DBSCAN per segment, [O3D-knowledge] Open3D's cluster_dbscan(eps, min_points) as remembered
+ * and not checked against an installation, and the mask of the largest cluster.  The reference has no such step, so these
+ * comments are the specification and tests/dbscan_ref.py restates them.  As in the block above: every operation is ONE IEEE
+ * f64 operation in the order given, or an explicit fma; nothing is contracted; every threshold is STRICT.  d_xyz f32 [n,3];
+ * h_off int64 [n_seg + 1] host offsets; neighbours are rows of the SAME segment; d2 is cs_outlier_radius' chain,
+ * d2 = fma(dz, dz, fma(dy, dy, dx * dx)) with d. = (double)x_j. - (double)x_i.; a NaN or +inf d2 is never a neighbour.
+ * n_seg = 0 and empty segments are legal.  Everything is enqueued on `stream`; no host wait (CS_DBSCAN_STATS=1 adds one at
+ * the end of cs_dbscan); the only atomics are integer.  Profile family "cluster", one scope per call.
+ *
+ * cs_dbscan: eps finite and > 0, min_points >= 1 (else CS_ERR_INVALID); d_label int32 [n]; d_count int32 [n] or NULL.
+ *   Also refused (CS_ERR_INVALID): a NULL offset table, a negative count, offsets that decrease, a NULL d_xyz or d_label
+ *   while a row exists; (CS_ERR_UNSUPPORTED): a segment of 2^31 rows or more.
+ *   r2 = eps * eps (one f64 product).
+ *   count_i = the number of rows j of the segment, itself included, with d2 < r2: exactly cs_outlier_radius' count (the
+ *     same kernels).  d_count, when given, receives it.
+ *   Row i is a CORE row when count_i >= min_points ([O3D-knowledge]: Open3D's and scikit-learn's rule, the point itself
+ *     counted; with min_points = nb_points + 1 it is cs_outlier_radius' keep rule).
+ *   Two core rows are LINKED when d2 < r2; a CLUSTER is a connected component of the core rows under that relation.
+ *   The clusters of a segment are numbered 0, 1, ... in ascending order of their smallest core row (local to the segment).
+ *   A non-core row with at least one core row inside d2 < r2 is a BORDER row: it takes the label of the core neighbour with
+ *     the smallest (d2, local row index), compared as a pair.  THIS IS A DELIBERATE DIFFERENCE: [O3D-knowledge] Open3D and
+ *     scikit-learn give a border row to whichever cluster reaches it first in their visit order, which depends on the
+ *     order of the rows; the rule here depends on no order except through exact ties of d2.
+ *   Every other row gets -1: noise, and every row with a non-finite coordinate (its count is 0).
+ *   A permuted segment gives the same core set and the same partition of the core rows; a border row's cluster can differ
+ *     only at an exact tie of d2 between core rows of two clusters; the cluster NUMBERS follow the smallest rows.  The
+ *     result is a function of the segment alone: batch neighbours, the stream, the launch shape and the run do not reach it.
+ *   An eps whose square overflows to +inf links every finite row of the segment to every other; one whose square underflows
+ *     to 0 finds nothing, not even the row itself: count = 0, nothing is core, every label is -1.
+ *   Paths, the same values: the exhaustive scan of the row's segment (cs_outlier_radius' kernel shape) is the definition,
+ *     the whole path under CS_DBSCAN_GRID=0 (read per call), the path of every segment of at most 512 rows and of an eps of
+ *     1e150 or more; otherwise cs_estimate_normals_hybrid's cell grid (the same code: cells of eps (1 + 2^-10), complete for
+ *     d2 < r2 by the argument in cellgrid.h).  The components come from a lock-free union-find (dbscan.hip): whatever the
+ *     order in which the threads run, its trees are the components and each root is the component's smallest row.
+ *
+ * cs_cluster_largest: d_label int32 [n] (cs_dbscan's); d_keep u8 [n] (0 / 1); d_stat int32 [n_seg,3] per segment, written
+ *   for empty segments too.  Refused as above; a NULL d_stat with n_seg > 0, a NULL d_label or d_keep while a row exists.
+ *   A label outside [0, rows of the segment) is treated as -1 (no cluster).
+ *   size(c) = the number of rows of the segment with label c, core and border rows alike.
+ *   d_stat = (the number of c with size(c) > 0, the c of the largest size -- of equal sizes the smallest c --, that size);
+ *     (0, -1, 0) for a segment without a cluster.  keep_i = label_i is that c.
+ *   Integer atomics only (counts, a maximum, a sum): the same values on any launch shape.
+ *
+ * cs_dbscan_stats: out = {rows answered by the grid path, border rows}, counted only while CS_DBSCAN_STATS=1 (read per call).
+ * ---------------------------------------------------------------------------------------- */
+int cs_dbscan(const float* d_xyz, const int64_t* h_off, int n_seg, double eps, int min_points, int32_t* d_label,
+              int32_t* d_count, void* stream);
+int cs_cluster_largest(const int32_t* d_label, const int64_t* h_off, int n_seg, uint8_t* d_keep, int32_t* d_stat,
+                       void* stream);
+void cs_dbscan_stats(uint64_t out[2], int reset);
+
+/* ------------------------------------------------------------------------------------------
  * Profiling hooks for bench.py: when enabled the library brackets the launches of each named
  * kernel family with hipEvents on the launch stream and accumulates the elapsed time.
  * names: "conv", "ransac_eval", "ransac_pre", "ransac_hyp", "knn", "chamfer", "topk", "symcut",
- * "kmap", "loss", "hardneg", "icp", "normals", "fgr", "chamfer2", "fpfh", "orient", "outlier".
+ * "kmap", "loss", "hardneg", "icp", "normals", "fgr", "chamfer2", "fpfh", "orient", "outlier", "cluster".
  * ---------------------------------------------------------------------------------------- */
 void cs_prof_enable(int on);
 void cs_prof_reset(void);
