@@ -125,6 +125,7 @@ def _declare(lib):
         "cs_dbscan": (c_int, [vp, POINTER(c_int64), c_int, c_double, c_int, vp, vp, vp]),
         "cs_cluster_largest": (c_int, [vp, POINTER(c_int64), c_int, vp, vp, vp]),
         "cs_dbscan_stats": (None, [POINTER(c_uint64), c_int]),
+        "cs_segment_plane": (c_int, [vp, POINTER(c_int64), c_int, c_double, c_int, c_uint64, vp, vp, vp, vp]),
         "cs_fgr_batch": (c_int, [vp, vp, POINTER(c_int64), c_int, c_double, c_double, c_double, c_int, c_int, c_double,
                                  c_int, c_uint64, vp, vp, vp, vp, vp, vp, vp]),
         "cs_prof_enable": (None, [c_int]),

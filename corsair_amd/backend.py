@@ -682,6 +682,24 @@ def dbscan_stats(reset=False):
     return int(out[0]), int(out[1])
 
 
+def segment_plane(xyz, offsets, dist, iters=1024, seed=0):
+    """Open3D's segment_plane(dist, 3, iters) per segment, cs_segment_plane: (inlier bool [n], plane f64 [n_seg,4] =
+    (n_x, n_y, n_z, d) with n . p + d = 0, stat int32 [n_seg,8] = (found, best t, stage-1 count, refit, final count, n_pos,
+    n_neg, rows_finite) per segment), all on the device.  `iters` three-row hypotheses are counted, the best is refitted
+    over its inliers by an order-free integer covariance, and the mask is that of the refitted plane; the normal points to
+    the side most of the other rows are on and n_neg counts the rows beyond it.  A segment without a plane gives a zero
+    plane, stat (0, -1, 0, 0, 0, 0, 0, rows_finite) and no inlier.  The semantics are the header comment of
+    cs_segment_plane.  No host wait."""
+    xyz = _packed_points(xyz, offsets, "segment_plane")
+    n_seg = len(offsets) - 1
+    inlier = torch.zeros(xyz.shape[0], dtype=torch.uint8, device=xyz.device)
+    plane = torch.zeros((n_seg, 4), dtype=torch.float64, device=xyz.device)
+    stat = torch.zeros((n_seg, 8), dtype=torch.int32, device=xyz.device)
+    check(_lib.load().cs_segment_plane(ptr(xyz), i64_array(offsets), n_seg, float(dist), int(iters), int(seed), ptr(plane),
+                                       ptr(stat), ptr(inlier), stream_ptr()))
+    return inlier.bool(), plane, stat
+
+
 def select_rows(keep, offsets):
     """The rows a mask keeps, as (idx int64 [m] device, ascending; new host offsets): plain torch, and the only place where
     the filters wait for the device (the kept rows per segment come to the host, as voxelize's offsets do)."""

@@ -11,9 +11,11 @@ Differences in structure (not in results) from the reference loops:
 """
 from __future__ import annotations
 
+import math
 import os
 
 from dataclasses import dataclass, field
+from typing import Optional, Tuple
 
 import numpy as np
 import torch
@@ -27,6 +29,7 @@ ICP_KERNEL_NAMES = tuple(B.ICP_KERNELS)       # "l2", "huber", "cauchy", "tukey"
 VERIFY_SCORES = ("symmetric", "forward")
 VERIFY_MAX_K = 32
 SCAN_FILTERS = ("none", "statistical", "radius", "cluster")
+SCAN_PLANES = ("none", "remove")
 SCAN_FILTER_MIN_ROWS = 10      # ransac_n: a cloud the filter would leave with fewer rows keeps all of them
 
 
@@ -102,6 +105,43 @@ class Config:
     # UNTUNED, NO REAL SCAN MEASURED
     scan_filter_eps: float = 2.5
     scan_filter_min_points: int = 5
+    # removal of the SUPPORT PLANE (the floor a scanned object stands on, or the wall behind it) from raw query scans, a step
+    # of its own BEFORE scan_filter (cs_segment_plane, Open3D's segment_plane): "none" (the default) or "remove".
+    # scan_plane_dist is in VOXELS, scan_plane_iters the number of hypotheses.  The dominant plane is removed only when it
+    # is a support plane (is_support_plane): it holds scan_plane_min_share of the finite rows, at most scan_plane_max_below
+    # of the other rows lie beyond it, and -- when scan_plane_up is given -- its normal lies within scan_plane_max_tilt
+    # degrees of that direction.  Without scan_plane_up a bare table top seen from above passes the first two rules and is
+    # removed: that is why the step is off by default.  ALL OF THEM UNTUNED, NO REAL SCAN MEASURED
+    scan_plane: str = "none"
+    scan_plane_dist: float = 1.0
+    scan_plane_iters: int = 1024
+    scan_plane_min_share: float = 0.2
+    scan_plane_max_below: float = 0.02
+    scan_plane_up: Optional[Tuple[float, float, float]] = None
+    scan_plane_max_tilt: float = 30.0
+
+    def check_scan_plane(self):
+        if self.scan_plane not in SCAN_PLANES:
+            raise ValueError("Config.scan_plane must be one of %s, got %r" % (SCAN_PLANES, self.scan_plane))
+        if not 0.0 < float(self.scan_plane_dist) < float("inf"):
+            raise ValueError("Config.scan_plane_dist must be positive and finite, got %r" % (self.scan_plane_dist,))
+        it = self.scan_plane_iters
+        if isinstance(it, bool) or not isinstance(it, (int, np.integer)) or not 1 <= int(it) <= 65536:
+            raise ValueError("Config.scan_plane_iters must be an integer in [1, 65536], got %r" % (it,))
+        if not 0.0 <= float(self.scan_plane_min_share) <= 1.0:
+            raise ValueError("Config.scan_plane_min_share must lie in [0, 1], got %r" % (self.scan_plane_min_share,))
+        if not 0.0 <= float(self.scan_plane_max_below) <= 1.0:
+            raise ValueError("Config.scan_plane_max_below must lie in [0, 1], got %r" % (self.scan_plane_max_below,))
+        up = self.scan_plane_up
+        if up is not None:
+            try:
+                v = [float(x) for x in up]
+            except (TypeError, ValueError):
+                v = []
+            if len(v) != 3 or not all(math.isfinite(x) for x in v) or not any(x != 0.0 for x in v):
+                raise ValueError("Config.scan_plane_up must be None or three finite numbers, not all zero, got %r" % (up,))
+        if not 0.0 < float(self.scan_plane_max_tilt) <= 90.0:
+            raise ValueError("Config.scan_plane_max_tilt must lie in (0, 90] degrees, got %r" % (self.scan_plane_max_tilt,))
 
     def check_scan_filter(self):
         if self.scan_filter not in SCAN_FILTERS:
@@ -210,12 +250,34 @@ class EmbeddedSet:
                            None if self.normal is None else self.normal[rows])
 
 
+def is_support_plane(stat_row, plane_row, cfg):
+    """Whether the plane cs_segment_plane found (one row of its stat and of its plane) is a SUPPORT plane under cfg, pure
+    Python: (a) its final inliers are at least scan_plane_min_share of the finite rows, (b) at most scan_plane_max_below of
+    the other finite rows lie beyond it (n_neg; the normal points to the side most rows are on), (c) when scan_plane_up is
+    given, the normal lies within scan_plane_max_tilt degrees of it.  Rules (a) and (b) alone cannot tell a floor from a
+    bare table top seen from above: both are one-sided."""
+    found, _, _, _, final, n_pos, n_neg, finite = (int(v) for v in stat_row)
+    if not found:
+        return False
+    if final < float(cfg.scan_plane_min_share) * finite:
+        return False
+    if n_neg > float(cfg.scan_plane_max_below) * (n_pos + n_neg):
+        return False
+    if cfg.scan_plane_up is not None:
+        up = [float(v) for v in cfg.scan_plane_up]
+        dot = sum(float(plane_row[a]) * up[a] for a in range(3)) / math.sqrt(sum(v * v for v in up))
+        if dot < math.cos(math.radians(float(cfg.scan_plane_max_tilt))):
+            return False
+    return True
+
+
 class Pipeline:
     def __init__(self, state_dict, embedding_state_dict, device="cuda", config=None):
         self.cfg = config or Config()
         self.device = torch.device(device)
         self.engine = E.ResUNetEngine(state_dict, embedding_state_dict, device=self.device)
         self.scan_filter_stat = {"rows_in": 0, "rows_kept": 0, "clouds_skipped": 0}     # filter_scan adds to it
+        self.scan_plane_stat = {"clouds": 0, "planes_removed": 0, "rows_removed": 0}    # remove_plane adds to it
 
     # ---- feature extraction (evaluation.py:213-269) ----------------------------------------------
     def embed_batch(self, xyz, offsets, scan_filter=False):
@@ -250,13 +312,42 @@ class Pipeline:
         st["clouds_skipped"] += len(short)
         return (None if new_off[-1] == offsets[-1] - offsets[0] else idx), new_off
 
+    def remove_plane(self, origin, offsets, voxel_size):
+        """The support-plane step (Config.scan_plane) on packed f32 origins: (idx int64 [m] device or None when every
+        row stays, new host offsets).  The final inliers of cs_segment_plane leave every cloud whose plane is_support_plane
+        accepts, unless the cloud would be left with fewer than SCAN_FILTER_MIN_ROWS rows.  Adds to self.scan_plane_stat.
+        Two host waits: stat and plane come to the host for the rule, then backend.select_rows."""
+        c = self.cfg
+        c.check_scan_plane()
+        inlier, plane, stat = B.segment_plane(origin, offsets, float(c.scan_plane_dist) * float(voxel_size),
+                                              int(c.scan_plane_iters))
+        stat_h, plane_h = stat.cpu().tolist(), plane.cpu().tolist()
+        n_seg = len(offsets) - 1
+        drop = [p for p in range(n_seg)
+                if is_support_plane(stat_h[p], plane_h[p], c) and (offsets[p + 1] - offsets[p]) - stat_h[p][4] >= SCAN_FILTER_MIN_ROWS]
+        st = self.scan_plane_stat
+        st["clouds"] += n_seg
+        st["planes_removed"] += len(drop)
+        st["rows_removed"] += sum(stat_h[p][4] for p in drop)
+        if not drop:
+            return None, [int(o) - int(offsets[0]) for o in offsets]
+        keep = torch.ones(inlier.shape[0], dtype=torch.bool, device=inlier.device)
+        for p in drop:
+            keep[offsets[p]:offsets[p + 1]] = ~inlier[offsets[p]:offsets[p + 1]]
+        return B.select_rows(keep, offsets)
+
     def embed_batch_raw(self, xyz, offsets, voxel_size, scan_filter=False):
         """xyz f32 or f64: quantised in its own type (backend.voxelize); the kept points of an f64 cloud
         become f32 origins AFTER the selection (evaluation-shapenet.py:103-105; the collate of
         datasets/ChairDataset.py:204-237 does the same to the f64 `rot_coords`).  scan_filter: when the configuration
-        names a filter (Config.scan_filter), it runs on those origins and the voxels it drops never reach the network."""
+        names a filter (Config.scan_filter), it runs on those origins and the voxels it drops never reach the network;
+        the support-plane step (Config.scan_plane) runs before it under the same gate."""
         keep, grid, out_off = B.voxelize(xyz, offsets, voxel_size)
         origin = xyz[keep].to(torch.float32)
+        if scan_filter and self.cfg.scan_plane != "none":
+            sel, out_off = self.remove_plane(origin, out_off, voxel_size)
+            if sel is not None:
+                origin, grid = origin[sel], grid[sel]
         if scan_filter and self.cfg.scan_filter != "none":
             sel, out_off = self.filter_scan(origin, out_off, voxel_size)
             if sel is not None:
@@ -543,9 +634,12 @@ def run_eval(pipe, catalog, queries, best_match, table, base_T, lib_T, syms, cat
     cat = catalog if isinstance(catalog, EmbeddedSet) else pipe.embed_clouds(catalog, ebs)
     # raw queries alone are cleaned by the configured scan filter: never the catalog, never an EmbeddedSet
     filt = getattr(cfg, "scan_filter", "none") != "none" and not isinstance(queries, EmbeddedSet)
-    if filt:
+    plane = getattr(cfg, "scan_plane", "none") != "none" and not isinstance(queries, EmbeddedSet)   # the step before it
+    if filt or plane:
         cfg.check_scan_filter()
+        cfg.check_scan_plane()
         pipe.scan_filter_stat = {"rows_in": 0, "rows_kept": 0, "clouds_skipped": 0}
+        pipe.scan_plane_stat = {"clouds": 0, "planes_removed": 0, "rows_removed": 0}
         qs = pipe.embed_clouds(queries, ebs, scan_filter=True)
     else:
         qs = queries if isinstance(queries, EmbeddedSet) else pipe.embed_clouds(queries, ebs)
@@ -563,6 +657,8 @@ def run_eval(pipe, catalog, queries, best_match, table, base_T, lib_T, syms, cat
 
     if filt:
         stat["scan_filter"] = dict(pipe.scan_filter_stat)
+    if plane:
+        stat["scan_plane"] = dict(pipe.scan_plane_stat)
     per_query = None if (ignore_cache or cache_dir is None) else \
         C_.load_results(cache_dir, category, register_top1, icp=cfg.icp_max_iter > 0,
                         icp_scale=bool(getattr(cfg, "icp_with_scaling", False)), **({"verify": K} if K else {}))
@@ -911,6 +1007,26 @@ def build_parser():
     ap.add_argument("--scan-filter-min-points", type=int, default=5,
                     help="--scan-filter cluster: a row is a core row with this many rows inside eps, itself included "
                          "(untuned, no real scan measured)")
+    ap.add_argument("--scan-plane", default="none", choices=list(SCAN_PLANES),
+                    help="remove the support plane (floor or wall; cs_segment_plane, Open3D's segment_plane) from every raw "
+                         "query scan before --scan-filter; never the catalog.  Without --scan-plane-up a bare table top seen "
+                         "from above is removed too (untuned, no real scan measured); not recorded in the cache")
+    ap.add_argument("--scan-plane-dist", type=float, default=1.0,
+                    help="distance threshold of --scan-plane, in voxels (untuned, no real scan measured)")
+    ap.add_argument("--scan-plane-iters", type=int, default=1024,
+                    help="plane hypotheses of --scan-plane, 1..65536 (untuned, no real scan measured)")
+    ap.add_argument("--scan-plane-min-share", type=float, default=0.2,
+                    help="--scan-plane removes a plane that holds at least this share of the scan's rows "
+                         "(untuned, no real scan measured)")
+    ap.add_argument("--scan-plane-max-below", type=float, default=0.02,
+                    help="--scan-plane removes a plane with at most this share of the other rows beyond it "
+                         "(untuned, no real scan measured)")
+    ap.add_argument("--scan-plane-up", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"),
+                    help="the up direction of the scans: --scan-plane then removes only a plane whose normal lies within "
+                         "--scan-plane-max-tilt of it (untuned, no real scan measured)")
+    ap.add_argument("--scan-plane-max-tilt", type=float, default=30.0,
+                    help="largest angle between the plane's normal and --scan-plane-up, in degrees, (0, 90] "
+                         "(untuned, no real scan measured)")
     ap.add_argument("--in-flight", type=int, default=3, help="registration batches in flight (host threads x HIP streams)")
     ap.add_argument("--device", default="cuda", choices=["cuda"], help="there is no CPU path")
     return ap
@@ -942,9 +1058,14 @@ def main(argv=None):
                  registration=a.registration, fgr_mu_floor=a.fgr_mu_floor, gicp_epsilon=a.gicp_epsilon,
                  scan_filter=a.scan_filter, scan_filter_k=a.scan_filter_k, scan_filter_std=a.scan_filter_std,
                  scan_filter_radius=a.scan_filter_radius, scan_filter_min_nb=a.scan_filter_min_nb,
-                 scan_filter_eps=a.scan_filter_eps, scan_filter_min_points=a.scan_filter_min_points)
+                 scan_filter_eps=a.scan_filter_eps, scan_filter_min_points=a.scan_filter_min_points,
+                 scan_plane=a.scan_plane, scan_plane_dist=a.scan_plane_dist, scan_plane_iters=a.scan_plane_iters,
+                 scan_plane_min_share=a.scan_plane_min_share, scan_plane_max_below=a.scan_plane_max_below,
+                 scan_plane_up=None if a.scan_plane_up is None else tuple(a.scan_plane_up),
+                 scan_plane_max_tilt=a.scan_plane_max_tilt)
     cfg.check_icp()
     cfg.check_scan_filter()
+    cfg.check_scan_plane()
     pipe = Pipeline(sd, esd, device=a.device, config=cfg)
     cad_names, catalog = load_cloud_dir(a.catalog_dir, a.n_points, "catalog")
     _, queries = load_cloud_dir(a.query_dir, a.n_points, "queries")

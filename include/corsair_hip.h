@@ -1140,10 +1140,69 @@ int cs_cluster_largest(const int32_t* d_label, const int64_t* h_off, int n_seg, 
 void cs_dbscan_stats(uint64_t out[2], int reset);
 
 /* ------------------------------------------------------------------------------------------
+ * Support-plane segmentation: the dominant plane of every segment by RANSAC, [O3D-knowledge] Open3D's
+ * segment_plane(distance_threshold, ransac_n, num_iterations) as remembered and not checked against an installation; where
+ * the project's habits differ they hold (the list is at the end).  The reference has no such step, so this comment is the
+ * specification and tests/plane_ref.py restates it bit for bit.  As in the blocks above: every operation is ONE IEEE f64
+ * operation in the order given, or an explicit fma; nothing is contracted; only + - * / sqrt fma rint, scalings by powers of
+ * two, integer arithmetic and comparisons appear; every threshold is STRICT.  d_xyz f32 [n,3]; h_off int64 [n_seg + 1] host
+ * offsets; p_i = row i as f64; a segment has m rows with local indices 0 .. m - 1.
+ *
+ * cs_segment_plane: dist finite and > 0, iters in [1, 65536] (else CS_ERR_INVALID); d_plane f64 [n_seg,4]; d_stat int32
+ *   [n_seg,8]; d_inlier u8 [n] (0 / 1).  Also refused (CS_ERR_INVALID): a NULL offset table, a negative count, offsets that
+ *   decrease, a NULL d_plane or d_stat with n_seg > 0, a NULL d_xyz or d_inlier while a row exists; (CS_ERR_UNSUPPORTED): a
+ *   segment of 2^31 rows or more.  n_seg = 0 and empty segments are legal; an empty segment writes the NO-PLANE row.
+ *   Stage 1, the hypotheses.  thr2 = dist * dist.  For t = 0 .. iters - 1:
+ *     i_j = rng_index(seed, t, j, m), j = 0, 1, 2 (corsair_amd/csrc/common.h: the generator of cs_ransac_batch's samples;
+ *       the draws depend on (seed, t, j, m) alone, not on the segment's place in the batch);
+ *     e1 = p_i1 - p_i0, e2 = p_i2 - p_i0;
+ *     n_x = fma(e1_y, e2_z, -(e1_z * e2_y)), n_y = fma(e1_z, e2_x, -(e1_x * e2_z)), n_z = fma(e1_x, e2_y, -(e1_y * e2_x));
+ *     nn = fma(n_z, n_z, fma(n_y, n_y, n_x * n_x)), bound = thr2 * nn.
+ *     The hypothesis is VALID when 0 < nn < +inf and 0 < bound < +inf: repeated rows, collinear rows, a non-finite sample and
+ *       a threshold that under- or overflows are invalid and count 0.
+ *     Row q is an inlier of t when, with u = p_q - p_i0 and s = fma(u_z, n_z, fma(u_y, n_y, u_x * n_x)), s * s < bound (no
+ *       square root, no division; a NaN is false, so a row with a non-finite coordinate is never an inlier).
+ *     count_t = the inliers of t.  The best hypothesis has the largest count, ties to the SMALLEST t.
+ *     A segment without a valid hypothesis, or with a best count below 3, has NO PLANE: its d_plane row is zero, its d_stat row
+ *       (0, -1, 0, 0, 0, 0, 0, rows_finite), its d_inlier rows 0.  rows_finite = the rows whose three coordinates are finite.
+ *   Stage 2, the refit, free of the order of the rows.  A = the stage-1 inliers of the best t, o = p_i0 of that t, u = p - o.
+ *     M = the largest |u_a| over A and the three axes (exact and order-free).  M = 0: the refit is skipped.
+ *     M = f 2^e with f in [0.5, 1) (frexp), sh = min(15 - e, 1023); q_a = (int64)rint(u_a * 2^sh), |q_a| <= 2^15.
+ *     Nine signed 64-bit sums over A: S_a, and S_ab (a <= b) of q_a q_b; each stays below 2^62 for fewer than 2^31 rows.
+ *     With n = |A|, in signed 128-bit integers C_ab = n S_ab - S_a S_b (magnitude below 2^93), converted by
+ *       cs_outlier_statistical's rule for its D: the magnitude as (double)hi * 2^64 + (double)lo (hi, lo its upper and lower
+ *       64 bits), the sign applied afterwards; mirrored.
+ *     jacobi3 (corsair_amd/csrc/horn.h) on C; e = the column of the smallest diagonal entry, ties to the smaller column,
+ *       as cs_estimate_normals selects it; len2 = fma(e_z, e_z, fma(e_y, e_y, e_x * e_x)).
+ *     When the refit is skipped, or len2 is zero or not finite (which a non-finite component makes it): the final plane is
+ *       the sampled one, n_a = n_a / sqrt(nn) and c = o, refit = 0.
+ *     Otherwise n_a = e_a / sqrt(len2), c_a = o_a + ((double)S_a / (double)n) * 2^-sh, refit = 1.
+ *   Stage 3, final inliers, sides, orientation.  For every finite row: u = p - c, s = fma(u_z, n_z, fma(u_y, n_y, u_x * n_x)),
+ *     inlier = s * s < thr2; n_pos, n_neg = the finite rows that are no inliers with s > 0, with s < 0.
+ *     n_neg > n_pos: n is negated and the two counts swap.  n_neg = n_pos: cs_estimate_normals' sign rule, the component of
+ *       largest magnitude (the first such on ties) is made positive (the counts are equal, a swap changes nothing).
+ *     d = -fma(c_z, n_z, fma(c_y, n_y, c_x * n_x)).  d_plane = (n_x, n_y, n_z, d): the normal points to the side most rows
+ *       are on, and n_neg counts what lies beyond the plane.
+ *     d_stat = (1, best t, count of stage 1, refit, final count, n_pos, n_neg, rows_finite); d_inlier = the final mask.
+ *   Independence: the result is a function of (the segment's rows in their order, dist, iters, seed).  The order of the rows
+ *     enters through the draws only; batch neighbours, the stream, the launch shape and the run do not reach the result, and
+ *     stages 2 and 3 depend on the SET A alone (integer sums and an exact maximum).
+ *   Differences from [O3D-knowledge] Open3D: the number of hypotheses is fixed (no probabilistic early exit); thresholds are
+ *     strict; the refit is a fixed-point covariance about a sampled row with a resolution of 2^-15 of the inliers' extent
+ *     (tests/test_plane_cpu.py bounds its angle to the float fit); the returned inliers are those of the REFITTED plane;
+ *     ransac_n is 3.
+ *   Kernels (plane.hip): the count of 256 hypotheses x one slice of CS_PLANE_SLICE rows (read per call, default 1024) per
+ *     workgroup with one integer atomicAdd per thread, then per-row passes and one thread per segment.  Everything is enqueued
+ *     on `stream`; no host wait; the only atomics are integer.  Profile family "plane", one scope per call.
+ * ---------------------------------------------------------------------------------------- */
+int cs_segment_plane(const float* d_xyz, const int64_t* h_off, int n_seg, double dist, int iters, uint64_t seed,
+                     double* d_plane, int32_t* d_stat, uint8_t* d_inlier, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Profiling hooks for bench.py: when enabled the library brackets the launches of each named
  * kernel family with hipEvents on the launch stream and accumulates the elapsed time.
  * names: "conv", "ransac_eval", "ransac_pre", "ransac_hyp", "knn", "chamfer", "topk", "symcut",
- * "kmap", "loss", "hardneg", "icp", "normals", "fgr", "chamfer2", "fpfh", "orient", "outlier", "cluster".
+ * "kmap", "loss", "hardneg", "icp", "normals", "fgr", "chamfer2", "fpfh", "orient", "outlier", "cluster", "plane".
  * ---------------------------------------------------------------------------------------- */
 void cs_prof_enable(int on);
 void cs_prof_reset(void);
