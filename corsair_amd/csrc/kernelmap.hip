@@ -887,8 +887,8 @@ static int order_and_count(BatchPlan& b, hipStream_t s) {
 extern "C" {
 
 // The kernel maps of a batch.  Maps are grouped by the coordinate level they PROBE (their `in` map): one k_level_maps launch
-// per level serves every map of the group from one LDS table per sample, and the levels run on up to four streams (the
-// caller's and the thread's side streams: every side stream starts behind the caller's stream and the caller's stream
+// per level serves every map of the group from one LDS table per sample, and the levels run on up to five streams (four by
+// default: the caller's and the thread's side streams; every side stream starts behind the caller's stream and the caller's stream
 // continues behind all of them; scratch freed meanwhile is handed back to the pool only after that join).  Then ONE radix
 // sort gives every map its tiling order.  CS_KMAP_STREAMS=1: everything on the caller's stream; CS_KMAP_GLOBAL=1: the
 // global-table kernel for everything.
@@ -921,7 +921,8 @@ int cs_kernelmap_build_many(int n, const cs_coordmap* const* in, const cs_coordm
     const int rc_seg = ensure_segments_many(need.data(), (int)need.size(), s);
     if (rc_seg != CS_OK) return rc_seg;
   }
-  static const int n_streams = [] {
+  // read per call, like every other knob (tests flip it between calls of one process)
+  const int n_streams = [] {
     const char* e = getenv("CS_KMAP_STREAMS");
     int v = e ? atoi(e) : 4;   // 2 / 3 / 4 / 5 streams: stress 6016 / 6201 / 6235 / 5608 clouds/s (the runtime maps streams to 4 queues)
     return v < 1 ? 1 : (v > 5 ? 5 : v);
