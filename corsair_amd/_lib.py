@@ -134,6 +134,10 @@ def _declare(lib):
         "cs_prof_get_units": (c_int, [c_char_p, POINTER(c_double)]),
         "cs_pool_trim": (None, []),
         "cs_pool_stats": (None, [POINTER(c_uint64)]),
+        # test hooks (tests/test_gpu_stale_memory.py)
+        "cs_pool_poison": (None, [c_int]),
+        "cs_pool_poison_stats": (None, [POINTER(c_uint64), c_int]),
+        "cs_pool_peek": (c_int, [ctypes.c_size_t, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)

@@ -82,6 +82,27 @@ static void trim_thread_cache() {
   }
 }
 
+// ---- test hook: poison (cs_pool_poison) ----------------------------------------------------
+// -1 = off, else the byte every block is filled with before pool_alloc hands it out.
+static std::atomic<int> g_poison{-1};
+static std::atomic<unsigned long long> g_poison_blocks{0}, g_poison_bytes{0};
+
+// The fill cannot be ordered by a stream: a cached block may still be read by work queued in stream order on the caller's
+// stream, and the internal side streams are non-blocking, so the null stream does not wait for them either.  Hence: wait
+// for the whole device, fill, wait again (the block's first user may run on any stream).
+static bool poison_block(void* p, size_t c, int pattern) {
+  hipError_t e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemset(p, pattern, c);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    set_error("pool poison: fill of a %zu-byte block failed: %s", c, hipGetErrorString(e));
+    return false;
+  }
+  g_poison_blocks.fetch_add(1, std::memory_order_relaxed);
+  g_poison_bytes.fetch_add((unsigned long long)c, std::memory_order_relaxed);
+  return true;
+}
+
 void* pool_alloc(size_t bytes) {
   size_t c = size_class(bytes);
   void* p = nullptr;
@@ -100,6 +121,11 @@ void* pool_alloc(size_t bytes) {
         return nullptr;
       }
     }
+  }
+  const int pattern = g_poison.load(std::memory_order_relaxed);
+  if (pattern >= 0 && !poison_block(p, c, pattern)) {
+    (void)hipFree(p);
+    return nullptr;
   }
   std::lock_guard<std::mutex> lk(g_pool_mu);
   g_live[p] = LiveBlock{c, t_cache.id};
@@ -348,6 +374,29 @@ void cs_pool_stats(uint64_t out[3]) {
   unsigned long long v[3];
   cs::pool_stats(v);
   for (int i = 0; i < 3; ++i) out[i] = v[i];
+}
+
+void cs_pool_poison(int pattern) { cs::g_poison.store(pattern >= 0 && pattern <= 255 ? pattern : -1); }
+
+void cs_pool_poison_stats(uint64_t out[2], int reset) {
+  out[0] = cs::g_poison_blocks.load();
+  out[1] = cs::g_poison_bytes.load();
+  if (reset) {
+    cs::g_poison_blocks.store(0);
+    cs::g_poison_bytes.store(0);
+  }
+}
+
+int cs_pool_peek(size_t bytes, uint8_t* d_out, void* stream) {
+  CS_REQUIRE(bytes > 0 && d_out, CS_ERR_INVALID, "cs_pool_peek: bytes must be positive and d_out non-NULL");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  cs::pool_use_stream(s);
+  void* p = cs::pool_alloc(bytes);
+  if (!p) return CS_ERR_HIP;
+  const hipError_t e = hipMemcpyAsync(d_out, p, bytes, hipMemcpyDeviceToDevice, s);
+  cs::pool_free(p);   // handed out again in stream order, behind the copy
+  CS_HIP_CHECK(e);
+  return CS_OK;
 }
 
 void cs_prof_enable(int on) {

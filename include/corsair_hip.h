@@ -28,6 +28,7 @@
 #ifndef CORSAIR_HIP_H
 #define CORSAIR_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -320,7 +321,8 @@ int cs_chamfer_2dir(const float* d_src, const int64_t* h_soff, const float* d_tg
  * d_inliers int32 [n_prob]; d_rmse f64 [n_prob]; d_iters int32 [n_prob] = iterations consumed.
  * Non-finite pairs: a pair with a NaN or infinite coordinate is never an inlier (its squared distance is not
  * below max_corr^2); it still counts in M and can be sampled.  A hypothesis whose fit is not finite has no inliers
- * and is never the best.  A problem with no finite pair returns the identity, 0 inliers and rmse 0.  With the
+ * and is never the best.  A problem with no finite pair returns the identity, 0 inliers and rmse 0; an EMPTY problem
+ * (no pair at all, anywhere in the batch) returns these and 0 iterations, written by the kernels.  With the
  * prefilter on or off the results are the same, and a problem without a non-finite value has the result it has
  * in a batch without the others, bit for bit.
  * ---------------------------------------------------------------------------------------- */
@@ -1218,6 +1220,24 @@ void cs_pool_trim(void);
  * any thread: a foreign block is released with hipFree (device-synchronising), never recycled into the
  * freeing thread's stream-ordered cache. */
 void cs_pool_stats(uint64_t out[3]);
+
+/* ------------------------------------------------------------------------------------------
+ * TEST HOOKS of the scratch pool (tests/test_gpu_stale_memory.py).  No product path calls them.
+ *
+ * cs_pool_poison: pattern in 0..255 -- from then on every block the pool hands out, fresh from the driver or cached, on any
+ *   host thread, is first filled with that byte over its whole size class; any other value (-1 by convention) turns the
+ *   hook off, which is the default.  While the hook is on every allocation waits for the DEVICE, fills the block and waits
+ *   for the device again: a cached block may still be read by work queued in stream order, and the library's side streams
+ *   are non-blocking, so no stream could order the fill.  Stream overlap is therefore gone in this mode; results are not.
+ *   With the hook off the cost is one relaxed atomic load per allocation.  A result that changes with the pattern shows a
+ *   kernel that reads scratch (or handle storage) it has not written.
+ * cs_pool_poison_stats: out = {blocks, bytes} poisoned since the process started or since the last call with reset != 0.
+ * cs_pool_peek: takes a pool block of `bytes` (> 0) as an entry point would, copies its first `bytes` bytes device-to-device
+ *   to d_out on `stream` and frees the block again: what a kernel would find in scratch of that size.
+ * ---------------------------------------------------------------------------------------- */
+void cs_pool_poison(int pattern);
+void cs_pool_poison_stats(uint64_t out[2], int reset);
+int cs_pool_peek(size_t bytes, uint8_t* d_out, void* stream);
 
 #ifdef __cplusplus
 }
