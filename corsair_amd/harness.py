@@ -181,6 +181,9 @@ class Config:
         return self.icp_kernel_scale if self.icp_kernel_scale > 0 else 1.0 * self.voxel_size
 
     def check_icp(self):
+        if self.registration == "ransac_fm":
+            raise ValueError("Config.registration 'ransac_fm' (feature-matching RANSAC, DESIGN 25) is not wired into the harness, "
+                             "the sharded evaluation or the cache format: use registration.sym_pose_batch or shapenet_eval")
         if self.registration not in ("ransac", "fgr"):
             raise ValueError("Config.registration must be 'ransac' or 'fgr', got %r" % (self.registration,))
         if not (0.0 < float(self.fgr_mu_floor) < float("inf")):

@@ -11,6 +11,8 @@ here every stage is one batched HIP launch over all pairs / hypotheses:
      part assignment (K or K+4 hypotheses per pair)             cs_knn_feat (labelled)
   4. one RANSAC per hypothesis, all in one call                 cs_ransac_batch
      (registration="fgr": Fast Global Registration instead)     cs_fgr_batch
+     (registration="ransac_fm": 1-NN both ways + mutual filter in
+      stage 1, RANSAC with the edge and distance checkers here)  cs_corr_mutual, cs_ransac_fm_batch
   5. one-directional Chamfer of every estimate                  cs_chamfer_1dir
   6. keep the estimate with the smallest Chamfer (first wins)   argmin
 
@@ -27,6 +29,7 @@ import torch
 
 from . import _helper
 from . import backend as B
+from . import featmatch as FM
 from ._lib import to_host
 
 ANCHOR_KEY = 0x5A11C0DE
@@ -168,8 +171,12 @@ def _sym_pose_batch(estimator, baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_
                     icp_estimation="point", icp_normal_k=16, normals1=None, icp_normal_radius=None, icp_with_scaling=False,
                     icp_scale_bounds=None, icp_kernel="l2", icp_kernel_scale=None):
     """The body of sym_pose_batch (below, with the documentation).  estimator = (registration, fgr_mu_floor,
-    fgr_iterations, fgr_tuple_test, normals0, gicp_epsilon), the keyword-only options; the first four already checked."""
-    registration, fgr_mu_floor, fgr_iterations, fgr_tuple_test, normals0, gicp_epsilon = estimator
+    fgr_iterations, fgr_tuple_test, normals0, gicp_epsilon, fm), the keyword-only options; the first four and fm =
+    (fm_ransac_n, fm_edge_similarity, fm_mutual, fm_iterations) already checked."""
+    registration, fgr_mu_floor, fgr_iterations, fgr_tuple_test, normals0, gicp_epsilon, fm = estimator
+    if registration == "ransac_fm" and use_symmetry:
+        raise ValueError("sym_pose_batch: registration 'ransac_fm' needs use_symmetry=False (the part configurations are out "
+                         "of scope)")
     if icp_estimation == "gicp" and (icp_with_scaling or icp_kernel != "l2"):
         raise ValueError("sym_pose_batch: icp_estimation 'gicp' with icp_with_scaling or a robust icp_kernel is out of scope")
     if icp_estimation != "gicp" and normals0 is not None:
@@ -198,7 +205,7 @@ def _sym_pose_batch(estimator, baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_
     off1 = [int(v) for v in off1]
     n0 = [off0[p + 1] - off0[p] for p in range(P)]
     n1 = [off1[p + 1] - off1[p] for p in range(P)]
-    k = k_nn
+    k = 1 if registration == "ransac_fm" else k_nn      # the feature-matching recipe takes 1-NN matches; k_nn is not used
 
     # ---- 1. vanilla correspondences (find_kcorr, utils/eval_pose.py:48-79) -----------------
     # A CAD cloud with fewer than k voxels has no k-th neighbour: SciPy's KD-tree returns the out-of-range index n
@@ -224,8 +231,15 @@ def _sym_pose_batch(estimator, baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_
         nonfinite = (B.cfg_bad(nn, pair_rows[:P + 1], P), B.rows_nonfinite(posF, pair_rows[P + 1:], P))
     # correspondence lists straight from the neighbour lists (one launch; rounds 1-2 built index tensors with
     # repeat_interleave / arange / gathers): pair p = query rows off0[p]:off0[p+1] against the CAD cloud at off1[p]
-    desc_v = np.asarray([[off0[p], off0[p], off1[p], n0[p], off0[p]] for p in range(P)], dtype=np.int64).reshape(P, 5)
-    v_src, v_tgt = B.corr_assemble(xyz0, xyz1, None, nn, desc_v, off0[-1], max(n0) if P else 0)
+    fm_m = None
+    if registration == "ransac_fm":
+        # the backward 1-NN (the segments swap their roles), then the mutual filter with Open3D's fallback on the device:
+        # pair p's correspondences fill the slots off0[p]... and their number stays on the device (fm_m)
+        nn_bwd = B.knn_feat(posF, off1, baseF, off0, 1) if fm[2] else None
+        v_src, v_tgt, fm_m, _ = FM.mutual_correspondences(nn, nn_bwd, xyz0, off0, xyz1, off1, fm[0], fm[2])
+    else:
+        desc_v = np.asarray([[off0[p], off0[p], off1[p], n0[p], off0[p]] for p in range(P)], dtype=np.int64).reshape(P, 5)
+        v_src, v_tgt = B.corr_assemble(xyz0, xyz1, None, nn, desc_v, off0[-1], max(n0) if P else 0)
     corr_src = [v_src]
     corr_tgt = [v_tgt]
     prob_len = [n0[p] * k for p in range(P)]
@@ -339,6 +353,10 @@ def _sym_pose_batch(estimator, baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_
             r = B.fgr_batch(src, tgt, offs, max_corr, mu_floor=fgr_mu_floor, iteration_number=fgr_iterations,
                             tuple_test=fgr_tuple_test, seed=seed)
             T, inl, rmse, iters = r.T, r.inliers, r.rmse, r.iters
+        elif registration == "ransac_fm":
+            r = FM.ransac_fm_batch(src, tgt, offs, max_corr, m=fm_m, ransac_n=fm[0], edge_similarity=fm[1],
+                                   check_distance=True, iterations=fm[3], seed=seed)
+            T, inl, rmse, iters = r.T.to(torch.float32), r.inliers.contiguous(), r.rmse, r.n_valid.contiguous()
         else:
             T, inl, rmse, iters = B.ransac_batch(src, tgt, offs, max_corr, 10, max_iter, confidence, seed)
     else:
@@ -396,6 +414,20 @@ def _sym_pose_batch(estimator, baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_
     return res
 
 
+def check_fm_options(ransac_n, edge_similarity, mutual, iterations, who="sym_pose_batch"):
+    """The fm_* options of registration = "ransac_fm" as (ransac_n, edge_similarity, mutual, iterations), or ValueError."""
+    if isinstance(ransac_n, bool) or ransac_n not in (3, 4):
+        raise ValueError("%s: fm_ransac_n must be 3 or 4, got %r" % (who, ransac_n))
+    if isinstance(edge_similarity, bool) or not isinstance(edge_similarity, (int, float)) or \
+            not 0.0 <= edge_similarity <= 1.0:
+        raise ValueError("%s: fm_edge_similarity must lie in [0, 1] (0 = no edge checker), got %r" % (who, edge_similarity))
+    if not isinstance(mutual, (bool, np.bool_)):
+        raise ValueError("%s: fm_mutual must be a bool, got %r" % (who, mutual))
+    if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or not 1 <= iterations < 2 ** 31:
+        raise ValueError("%s: fm_iterations must be an integer in [1, 2^31), got %r" % (who, iterations))
+    return int(ransac_n), float(edge_similarity), bool(mutual), int(iterations)
+
+
 def sym_pose_batch(*args, registration="ransac", fgr_mu_floor=0.025, fgr_iterations=64, fgr_tuple_test=True, **kwargs):
     """baseF f32 [N0,16], xyz0 f32 [N0,3] (query voxels of all pairs, segment p = off0[p]:off0[p+1]);
     posF/xyz1/off1 likewise for the CAD side; pos_syms: symmetry label per pair.
@@ -436,11 +468,22 @@ def sym_pose_batch(*args, registration="ransac", fgr_mu_floor=0.025, fgr_iterati
     as is icp_normal_k for this estimation).  normals0 (default None) and gicp_epsilon (default 1e-3) are accepted by keyword
     only, like the fgr_* options, and are taken out of **kwargs here.  icp_mrmse is filled too.  A robust icp_kernel or icp_with_scaling with "gicp" is out of scope and refused.
     Descriptors of another width (fpfh_features: 33 columns) register with use_symmetry=False; with use_symmetry the part
-    cut takes 16 or 32 columns and anything else is refused with ValueError before any launch."""
-    if registration not in ("ransac", "fgr"):
-        raise ValueError("sym_pose_batch: registration must be 'ransac' or 'fgr', got %r" % (registration,))
+    cut takes 16 or 32 columns and anything else is refused with ValueError before any launch.
+    registration = "ransac_fm": Open3D's registration_ransac_based_on_feature_matching recipe, for hand-crafted
+    descriptors.  Stage 1 runs cs_knn_feat at k = 1 in BOTH directions (k_nn is not used) and cs_corr_mutual keeps the mutual
+    matches (a pair with fewer than 3 fm_ransac_n of them keeps all of its 1-NN matches); stage 4 is ONE cs_ransac_fm_batch
+    call -- fm_iterations hypotheses of fm_ransac_n (3 or 4) pairs, the edge-length checker at fm_edge_similarity before the
+    fit and the distance checker at max_corr after it; T_all, inliers and iters (= the hypotheses that passed the checkers)
+    are filled from it and stages 5 - 7 are what they are for the RANSAC.  fm_ransac_n = 3, fm_edge_similarity = 0.9,
+    fm_mutual = True, fm_iterations = 100000 are Open3D's defaults, untuned, no real scan measured; like normals0 they are
+    accepted by keyword only and taken out of **kwargs here.  It needs use_symmetry=False (ValueError otherwise); max_iter
+    and confidence are unused.  With "ransac" and "fgr" nothing of it is launched."""
+    if registration not in ("ransac", "fgr", "ransac_fm"):
+        raise ValueError("sym_pose_batch: registration must be 'ransac', 'fgr' or 'ransac_fm', got %r" % (registration,))
     normals0, gicp_epsilon = kwargs.pop("normals0", None), kwargs.pop("gicp_epsilon", 1e-3)
-    return _sym_pose_batch((registration, fgr_mu_floor, fgr_iterations, fgr_tuple_test, normals0, gicp_epsilon), *args,
+    fm = check_fm_options(kwargs.pop("fm_ransac_n", 3), kwargs.pop("fm_edge_similarity", 0.9), kwargs.pop("fm_mutual", True),
+                          kwargs.pop("fm_iterations", 100000))
+    return _sym_pose_batch((registration, fgr_mu_floor, fgr_iterations, fgr_tuple_test, normals0, gicp_epsilon, fm), *args,
                            **kwargs)
 
 

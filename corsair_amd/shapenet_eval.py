@@ -57,12 +57,24 @@ class Config:
     # the correspondence estimator: "ransac" or "fgr" (cs_fgr_batch); fgr_mu_floor is UNTUNED, as in harness.Config
     registration: str = "ransac"
     fgr_mu_floor: float = 0.025
+    # "ransac_fm" (DESIGN 25): 1-NN matches both ways with the mutual filter, then cs_ransac_fm_batch -- fm_iterations
+    # hypotheses of fm_ransac_n pairs with the edge-length checker (fm_edge_similarity, 0 = off) and the distance checker at
+    # max_corr.  Open3D's defaults, UNTUNED, no real scan measured.  The symmetry hypotheses are off under it.
+    fm_ransac_n: int = 3
+    fm_edge_similarity: float = 0.9
+    fm_mutual: bool = True
+    fm_iterations: int = 100000
     # the descriptors: "network" (the ResUNet forward, needs a checkpoint) or "fpfh" (registration.fpfh_features: no weights;
     # sym_pose_batch then runs with use_symmetry=False, the part cut takes the network's widths only).  fpfh_radius is in
     # VOXELS, 5 is Open3D's example value, UNTUNED; fpfh_max_nn is cs_fpfh's max_nn
     features: str = "network"
     fpfh_radius: float = 5.0
     fpfh_max_nn: int = 100
+
+    def check_registration(self):
+        if self.registration not in ("ransac", "fgr", "ransac_fm"):
+            raise ValueError("Config.registration must be 'ransac', 'fgr' or 'ransac_fm', got %r" % (self.registration,))
+        R.check_fm_options(self.fm_ransac_n, self.fm_edge_similarity, self.fm_mutual, self.fm_iterations, "Config")
 
     def icp_distance(self):
         return self.icp_max_dist if self.icp_max_dist > 0 else 2.0 * self.voxel_size
@@ -186,6 +198,10 @@ def evaluate(pipe, clouds, cfg=None, pairs_per_batch=16, seed=None, force_gate=F
     cfg = cfg or Config()
     if cfg.features not in ("network", "fpfh"):
         raise ValueError("Config.features must be 'network' or 'fpfh', got %r" % (cfg.features,))
+    cfg.check_registration()
+    fm_on = cfg.registration == "ransac_fm"     # no symmetry hypotheses under it (the part configurations are out of scope)
+    fm_kw = dict(fm_ransac_n=cfg.fm_ransac_n, fm_edge_similarity=cfg.fm_edge_similarity, fm_mutual=cfg.fm_mutual,
+                 fm_iterations=cfg.fm_iterations) if fm_on else {}
     fpfh_on = cfg.features == "fpfh"
     if fpfh_on:
         pipe = FpfhPipe("cuda" if pipe is None else pipe.device, cfg.fpfh_radius, cfg.fpfh_max_nn)
@@ -228,14 +244,14 @@ def evaluate(pipe, clouds, cfg=None, pairs_per_batch=16, seed=None, force_gate=F
         res = R.sym_pose_batch(base.F, base.origin, base.offsets, posed.F, posed.origin, posed.offsets,
                                labels, cfg.k_nn, cfg.max_corr, 0,
                                [(2 * (s + i), 2 * (s + i) + 1) for i in range(P)], 100,
-                               cfg.ransac_max_iter, cfg.ransac_confidence, not fpfh_on, force_gate, None,
+                               cfg.ransac_max_iter, cfg.ransac_confidence, not fpfh_on and not fm_on, force_gate, None,
                                cfg.icp_max_iter, cfg.icp_distance() if icp_on else None, cfg.icp_estimation,
                                cfg.icp_normal_k, None, cfg.normal_radius(), icp_with_scaling=scale_on,
                                icp_scale_bounds=tuple(cfg.icp_scale_bounds) if scale_on else None,
                                icp_kernel=cfg.icp_kernel,
                                icp_kernel_scale=cfg.icp_scale() if cfg.icp_kernel != "l2" else None,
                                registration=cfg.registration, fgr_mu_floor=cfg.fgr_mu_floor,
-                               gicp_epsilon=cfg.gicp_epsilon)
+                               gicp_epsilon=cfg.gicp_epsilon, **fm_kw)
         Tb, Tr = res.T_best.cpu().numpy(), res.T_ransac.cpu().numpy()
         cdb, cdr = res.cd_best.cpu().numpy(), res.cd_ransac.cpu().numpy()
         for i, (mi, pi, _, _, pose, label, s_gt) in enumerate(chunk):
@@ -380,10 +396,21 @@ def build_parser():
                     help="the ICP refinement also fits an isotropic scale (needs --icp-iters > 0, no robust kernel)")
     ap.add_argument("--icp-scale-min", type=float, default=0.5, help="lower bound of the fitted scale, in (0, 1] (untuned)")
     ap.add_argument("--icp-scale-max", type=float, default=2.0, help="upper bound of the fitted scale, >= 1 (untuned)")
-    ap.add_argument("--registration", default="ransac", choices=["ransac", "fgr"],
-                    help="correspondence estimator: the reference's RANSAC, or Fast Global Registration (cs_fgr_batch)")
+    ap.add_argument("--registration", default="ransac", choices=["ransac", "fgr", "ransac_fm"],
+                    help="correspondence estimator: the reference's RANSAC, Fast Global Registration (cs_fgr_batch), or "
+                         "feature-matching RANSAC with a mutual filter and pose checkers (cs_ransac_fm_batch; no symmetry "
+                         "hypotheses)")
     ap.add_argument("--fgr-mu-floor", type=float, default=0.025,
                     help="floor of FGR's mu, in units of the clouds' radius (Open3D's default, untuned)")
+    ap.add_argument("--fm-ransac-n", type=int, default=3, choices=[3, 4],
+                    help="pairs per hypothesis of --registration ransac_fm (Open3D's default; untuned, no real scan measured)")
+    ap.add_argument("--fm-edge-similarity", type=float, default=0.9,
+                    help="edge-length checker of ransac_fm, in [0, 1]; 0 = off (Open3D's default; untuned, no real scan "
+                         "measured)")
+    ap.add_argument("--fm-no-mutual", action="store_true",
+                    help="ransac_fm keeps every 1-NN match instead of the mutual ones (untuned, no real scan measured)")
+    ap.add_argument("--fm-iterations", type=int, default=100000,
+                    help="hypotheses per pair of ransac_fm, a fixed number (Open3D's default; untuned, no real scan measured)")
     ap.add_argument("--out-dir", default=".")
     ap.add_argument("--device", default="cuda", choices=["cuda"])
     return ap
@@ -421,7 +448,8 @@ def main(argv=None):
                  icp_kernel_scale=a.icp_kernel_scale, icp_normal_radius=a.icp_normal_radius, max_log_scale=a.max_log_scale,
                  icp_with_scaling=a.icp_with_scaling, icp_scale_bounds=(a.icp_scale_min, a.icp_scale_max),
                  registration=a.registration, fgr_mu_floor=a.fgr_mu_floor, gicp_epsilon=a.gicp_epsilon, features=a.features,
-                 fpfh_radius=a.fpfh_radius, fpfh_max_nn=a.fpfh_max_nn)
+                 fpfh_radius=a.fpfh_radius, fpfh_max_nn=a.fpfh_max_nn, fm_ransac_n=a.fm_ransac_n,
+                 fm_edge_similarity=a.fm_edge_similarity, fm_mutual=not a.fm_no_mutual, fm_iterations=a.fm_iterations)
     results = evaluate(pipe, clouds, cfg)
     postfix = f"shapenet-seed{a.random_seed}-{a.category}-{len(files)}-{a.n_poses_per_model}"
     os.makedirs(a.out_dir, exist_ok=True)

@@ -1201,10 +1201,99 @@ int cs_segment_plane(const float* d_xyz, const int64_t* h_off, int n_seg, double
                      double* d_plane, int32_t* d_stat, uint8_t* d_inlier, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Feature-matching RANSAC: the third correspondence estimator, beside cs_ransac_batch and cs_fgr_batch, after
+ * [O3D-knowledge] Open3D's registration_ransac_based_on_feature_matching(mutual_filter, max_correspondence_distance,
+ * ransac_n, [CorrespondenceCheckerBasedOnEdgeLength(similarity), CorrespondenceCheckerBasedOnDistance(distance)]) as
+ * remembered and not checked against an installation; where the project's habits differ they hold (the list is at the end).
+ * The reference has no such step, so these comments are the specification and tests/featmatch_ref.py restates them bit for
+ * bit.  As in the blocks above: every operation is ONE IEEE f64 operation in the order given (sums without parentheses from
+ * left to right), or an explicit fma; nothing is contracted; only + - * / sqrt fma, scalings by powers of two, integer
+ * arithmetic and comparisons appear; every threshold is STRICT unless >= is written; a comparison with a NaN is false.
+ * Everything is enqueued on `stream`; scratch comes from the calling thread's pool; no host wait, no cooperative launch, no
+ * flag a thread waits on; the only atomics are integer; every loop is bounded by an argument or a segment's rows.  Profile
+ * family "featmatch", one scope per call.
+ *
+ * cs_corr_mutual: the correspondences of n_pair (query, CAD) pairs from two 1-NN lists.
+ *   d_nn_fwd int32 [N0]: the local CAD row of every query row (cs_knn_feat's d_idx at k = 1); d_nn_bwd int32 [N1]: the local
+ *     query row of every CAD row (the same call with the roles of the segments swapped; NULL allowed when mutual = 0);
+ *     d_xyz0 f32 [N0,3], d_xyz1 f32 [N1,3]; h_off0, h_off1 int64 [n_pair + 1] host offsets of the pairs' segments, n0 and n1
+ *     rows; d_src, d_tgt f32 [N0,3] (neither may alias an input); d_m int32 [n_pair]; d_stat int32 [n_pair,2].
+ *   Query row i (local) of a pair is VALID when 0 <= nn_fwd[i] < n1 (a -1 entry -- a non-finite descriptor, an empty CAD -- is
+ *     never a match) and MUTUAL when it is valid and nn_bwd[nn_fwd[i]] == i.  c = the number of mutual rows.
+ *   mutual = 1 and c >= 3 * ransac_n: the mutual rows are kept.  mutual = 1 and c < 3 * ransac_n: [O3D-knowledge] Open3D's
+ *     fallback, decided on the device -- the valid rows are kept and d_stat says so.  mutual = 0: the valid rows are kept.
+ *   The kept rows in ascending i (a STABLE compaction) fill the slots h_off0[p], h_off0[p] + 1, ...: d_src = xyz0[i],
+ *     d_tgt = xyz1[nn_fwd[i]], both copied bit for bit.  d_m[p] = their number.  The capacity of a pair is its n0 slots, so
+ *     the host needs no count; the slots past d_m[p] are written with +0.
+ *   d_stat[p] = (c with mutual = 1, the number of valid rows with mutual = 0;  1 when the fallback was taken, else 0).
+ *   n_pair = 0, empty queries and empty CADs are legal.  Refused (CS_ERR_INVALID): a NULL offset table, a negative count,
+ *     offsets that decrease, ransac_n outside [1, 2^20], mutual other than 0 / 1, NULL d_m or d_stat with n_pair > 0, a NULL
+ *     array that a row needs; (CS_ERR_UNSUPPORTED): a segment of 2^31 rows or more.
+ *   One workgroup per pair: a count pass, then a block scan over its rows.
+ *
+ * cs_ransac_fm_batch: d_src, d_tgt f32 [M,3], pair i = (s_i, q_i) widened to f64; problem p owns the slots
+ *   [h_off[p], h_off[p+1]) (cs_corr_mutual's layout; h_off int64 [n_prob + 1] on the host) of which the first
+ *   m = min(max(d_m[p], 0), capacity) hold pairs; d_m int32 [n_prob] on the device, NULL = every list is full.
+ *   max_corr finite and > 0; ransac_n = n in {3, 4}; edge_similarity in [0, 1], 0 = the edge checker is off; check_distance
+ *   0 = the distance checker is off; 1 <= iterations < 2^31; d_T f64 [n_prob,4,4]; d_stat int32 [n_prob,4]; d_rmse f64 [n_prob].
+ *   thr2 = max_corr * max_corr, sim2 = edge_similarity * edge_similarity, each formed once.
+ *   Hypothesis t = 0 .. iterations - 1 of a problem with m >= n:
+ *     Sampling: i_j = rng_index(seed, t, j, m), j = 0 .. n - 1 (corsair_amd/csrc/common.h: the generator of cs_ransac_batch and
+ *       cs_segment_plane; the draws depend on (seed, t, j, m) alone).  Draws are with replacement.
+ *     Edge-length checker (edge_similarity > 0), before the fit: for every a < b < n, with e = s_ia - s_ib and
+ *       f = q_ia - q_ib, ls2 = fma(e_z, e_z, fma(e_y, e_y, e_x * e_x)), lt2 likewise of f:
+ *       ls2 >= sim2 * lt2 && lt2 >= sim2 * ls2, else t is INVALID.  No square root is taken; a repeated draw passes (0 >= 0).
+ *     Fit, the formulas of cs_ransac_batch's hypothesis kernel with plain divisions: per axis
+ *       cs_c = ((0 + s_i0c) + s_i1c + ...) / (double)n, ct_c likewise;  S_xy = fma(ds_x, dt_y, S_xy) from S = 0 over j in order,
+ *       ds = s_ij - cs, dt = q_ij - ct;  Horn's N from S;  the eigenvector by horn_qcp (corsair_amd/csrc/horn.h) ALONE: a fit it
+ *       declines makes t INVALID (there is no Jacobi fallback here);  qn = sqrt(qw*qw + qx*qx + qy*qy + qz*qz), q = q / qn (four
+ *       divisions);  R from q as cs_ransac_batch forms it;  t_a = ct_a - (R_a0 * cs_0 + R_a1 * cs_1 + R_a2 * cs_2).
+ *       A fit with a value of R or t that is not finite makes t INVALID.
+ *     Distance: the project's canonical chain of the posed source (cs_ransac_batch's count),
+ *       p_c = fma(R_c2, s_z, fma(R_c1, s_y, fma(R_c0, s_x, t_c))),  d_c = p_c - q_c,  d2 = fma(d_z, d_z, fma(d_y, d_y, d_x * d_x)).
+ *     Distance checker (check_distance != 0), after the fit: d2 < thr2 for every sampled pair, else t is INVALID.
+ *     Count: count_t = the pairs i < m of the problem with d2 < thr2.  Invalid hypotheses count nothing and never win.
+ *   Best: the largest count; ties go to the SMALLEST t (cs_segment_plane's rule: a u64 maximum of count << 32 | ~t).
+ *     m < n, no valid hypothesis, or a best count < n: found = 0, d_T = the identity, d_stat = (0, -1, 0, n_valid),
+ *     d_rmse = 0 (cs_ransac_batch answers a problem of fewer than ransac_n pairs the same way).
+ *     Otherwise d_T = (R | t; 0 0 0 1) of the best hypothesis in f64 -- there is NO refit over the inliers -- and
+ *     d_stat = (1, t_best, count, n_valid), n_valid = the hypotheses that passed the checkers and the fit.
+ *   d_rmse = sqrt(((double)E * 2^-k) / (double)count), E = the unsigned 64-bit INTEGER sum over the inliers of the best
+ *     hypothesis of (uint64)(d2 * 2^k) (one product, truncation), k = 61 - eM - ex with eM the smallest integer with
+ *     m <= 2^eM and thr2 = f 2^ex, f in [0.5, 1) (frexp; ex at least -900, 1024 when thr2 is not finite).  A fixed-point sum:
+ *     it depends on the SET of inliers alone, not on any order or launch shape.
+ *   A max_corr whose square overflows to +inf counts every pair with a finite d2; one whose square underflows to 0 counts
+ *     nothing.  Rows with a NaN or infinite coordinate are never inliers and invalidate the hypotheses that sample them.
+ *   Independence: the result of a problem is a function of its pairs in their order, the parameters and the seed alone.  Batch
+ *     neighbours, the capacity behind m, the stream, the launch shape (CS_FM_SLICE, CS_FM_CHUNK) and the run do not reach it.
+ *   n_prob = 0 and empty problems are legal.  Refused (CS_ERR_INVALID): a NULL offset table, a negative count, offsets that
+ *     decrease, max_corr not positive and finite, edge_similarity outside [0, 1] (a NaN too), iterations < 1, NULL outputs with
+ *     n_prob > 0, NULL d_src or d_tgt while a slot exists; (CS_ERR_UNSUPPORTED): ransac_n outside {3, 4}, a problem of 2^31
+ *     slots or more, iterations >= 2^31.
+ *   Differences from [O3D-knowledge] Open3D, deliberate: the number of hypotheses is FIXED (no confidence-based early exit, as
+ *     cs_segment_plane decided); the tie rule (the smallest t; Open3D keeps the first best of an unordered parallel loop);
+ *     thresholds are strict (the edge checker's >= is Open3D's); the counter-based generator; NO final refit over the inliers
+ *     (the ICP stage follows); the winner is ranked by its inlier count alone (Open3D compares fitness, then rmse); a fit that
+ *     horn_qcp declines is dropped.
+ *   Kernels (featmatch.hip), per chunk of CS_FM_CHUNK hypotheses (default 8192, read per call, rounded up to a multiple of
+ *     256 and shrunk so that the lists of a call stay below 256 MiB): one lane per hypothesis appends the valid ones to the
+ *     problem's list through one integer atomicAdd (the order of the list reaches nothing); the count of 256 listed hypotheses
+ *     x one slice of CS_FM_SLICE pairs (default 1024, read per call) per workgroup with one integer atomicAdd per lane; the
+ *     u64 atomicMax.  Then one thread per problem and one pass over the rows.  The same bits for every value of both variables.
+ * ---------------------------------------------------------------------------------------- */
+int cs_corr_mutual(const int32_t* d_nn_fwd, const int32_t* d_nn_bwd, const float* d_xyz0, const int64_t* h_off0,
+                   const float* d_xyz1, const int64_t* h_off1, int n_pair, int ransac_n, int mutual, float* d_src,
+                   float* d_tgt, int32_t* d_m, int32_t* d_stat, void* stream);
+int cs_ransac_fm_batch(const float* d_src, const float* d_tgt, const int64_t* h_off, const int32_t* d_m, int n_prob,
+                       double max_corr, int ransac_n, double edge_similarity, int check_distance, int64_t iterations,
+                       uint64_t seed, double* d_T, int32_t* d_stat, double* d_rmse, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Profiling hooks for bench.py: when enabled the library brackets the launches of each named
  * kernel family with hipEvents on the launch stream and accumulates the elapsed time.
  * names: "conv", "ransac_eval", "ransac_pre", "ransac_hyp", "knn", "chamfer", "topk", "symcut",
- * "kmap", "loss", "hardneg", "icp", "normals", "fgr", "chamfer2", "fpfh", "orient", "outlier", "cluster", "plane".
+ * "kmap", "loss", "hardneg", "icp", "normals", "fgr", "chamfer2", "fpfh", "orient", "outlier", "cluster", "plane",
+ * "featmatch".
  * ---------------------------------------------------------------------------------------- */
 void cs_prof_enable(int on);
 void cs_prof_reset(void);
