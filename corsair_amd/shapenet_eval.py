@@ -70,6 +70,33 @@ class Config:
     features: str = "network"
     fpfh_radius: float = 5.0
     fpfh_max_nn: int = 100
+    # partial_view: the posed copy of every job is reduced to what one virtual depth camera sees of it
+    # (views.render_views) before the descriptors; the model stays whole.  The camera stands view_distance half diagonals of
+    # the copy's bounding box from the box's midpoint, in a direction drawn per job from a generator of its own, with a square
+    # image of view_size pixels over view_fov_deg degrees; view_point_size and view_depth_tol are in VOXELS.  Every default is
+    # UNTUNED, no real scan measured.
+    partial_view: bool = False
+    view_fov_deg: float = 40.0
+    view_size: int = 256
+    view_distance: float = 3.0
+    view_point_size: float = 1.5
+    view_depth_tol: float = 1.5
+
+    def check_partial_view(self):
+        if not isinstance(self.partial_view, (bool, np.bool_)):
+            raise ValueError("Config.partial_view must be a bool, got %r" % (self.partial_view,))
+        real = lambda v: isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, bool) and np.isfinite(v)
+        if not (real(self.view_fov_deg) and 0.0 < self.view_fov_deg < 180.0):
+            raise ValueError("Config.view_fov_deg must be in (0, 180) degrees, got %r" % (self.view_fov_deg,))
+        if not (isinstance(self.view_size, (int, np.integer)) and not isinstance(self.view_size, bool)
+                and 1 <= self.view_size <= 4096):
+            raise ValueError("Config.view_size must be an integer in [1, 4096] pixels, got %r" % (self.view_size,))
+        if not (real(self.view_distance) and self.view_distance > 1.0):
+            raise ValueError("Config.view_distance must be finite and > 1 half diagonal, got %r" % (self.view_distance,))
+        if not (real(self.view_point_size) and self.view_point_size > 0.0):
+            raise ValueError("Config.view_point_size must be finite and > 0 voxels, got %r" % (self.view_point_size,))
+        if not (real(self.view_depth_tol) and self.view_depth_tol > 0.0):
+            raise ValueError("Config.view_depth_tol must be finite and > 0 voxels, got %r" % (self.view_depth_tol,))
 
     def check_registration(self):
         if self.registration not in ("ransac", "fgr", "ransac_fm"):
@@ -136,6 +163,63 @@ def generate_random_pose(cfg, rng):
     return pose
 
 
+VIEW_MIN_ROWS = 10      # a view with fewer visible rows keeps the whole cloud (and is counted)
+
+
+def view_direction(seed, job):
+    """The direction from the posed copy to its camera: a normalised standard_normal(3) from a generator seeded by
+    (seed, job index) alone, so the evaluation's own generator -- the pose draws -- never sees the option."""
+    d = np.random.default_rng([int(seed), int(job)]).standard_normal(3)
+    return d / np.linalg.norm(d)
+
+
+def build_jobs(clouds, cfg, rng, symmetry_label=None):
+    """The (model, pose index, model points, posed copy, pose, symmetry label, scale) tuples of `evaluate`, in its order."""
+    symmetry_label = symmetry_label or get_symmetry_label
+    jobs = []
+    for mi, raw in enumerate(clouds):
+        pc = load_pc(raw)
+        label = symmetry_label(pc, cfg.symmetry_cd_threshold)
+        for pi in range(cfg.n_poses_per_model):
+            pose = generate_random_pose(cfg, rng)
+            # generate_test_pc_pair (:115-119): the model stays in its own type, the posed copy is the f64
+            # product with the f64 pose; quantize_pc (:97-107) floors each in its type and narrows afterwards
+            if cfg.max_log_scale > 0:
+                s_gt = float(np.exp(rng.uniform(-cfg.max_log_scale, cfg.max_log_scale)))
+                jobs.append((mi, pi, pc, s_gt * (pc @ pose[:3, :3].T) + pose[:3, [3]].T, pose, label, s_gt))
+            else:
+                jobs.append((mi, pi, pc, pc @ pose[:3, :3].T + pose[:3, [3]].T, pose, label, 1.0))
+    return jobs
+
+
+def partial_views(xyz, offsets, host, cfg, seed, first_job):
+    """The posed copies of one batch (xyz device [n,3] in its own type, host offsets; host: the same clouds as numpy arrays,
+    for the bounding boxes) reduced to what each one's camera sees: (kept rows of xyz, new offsets, visible share per cloud,
+    views skipped).  The mask is computed on the f32 cast; the selection (backend.select_rows, the one host wait) is applied
+    to the array in its own type."""
+    from . import views as V
+
+    x32 = xyz.to(torch.float32).contiguous()
+    P = len(offsets) - 1
+    h32 = [np.asarray(h, np.float32) for h in host]
+    lo, hi = np.stack([h.min(0) for h in h32]), np.stack([h.max(0) for h in h32])
+    dirs = np.stack([view_direction(seed, first_job + i) for i in range(P)])
+    cams = torch.from_numpy(V.view_cameras(lo, hi, dirs, cfg.view_distance)).to(xyz.device)
+    res = V.render_views(x32, offsets, cams, cfg.view_size, cfg.view_size, V.focal_from_fov(cfg.view_size, cfg.view_fov_deg),
+                         cfg.view_point_size * cfg.voxel_size, cfg.view_depth_tol * cfg.voxel_size)
+    idx, off = B.select_rows(res.visible, offsets)
+    kept = np.diff(off)
+    rows = np.diff(np.asarray(offsets))
+    skipped = [i for i in range(P) if kept[i] < VIEW_MIN_ROWS]
+    if skipped:
+        keep = res.visible.clone()
+        for i in skipped:
+            keep[offsets[i]:offsets[i + 1]] = 1
+        idx, off = B.select_rows(keep, offsets)
+    share = [1.0 if i in skipped else float(kept[i]) / float(rows[i]) for i in range(P)]
+    return xyz[idx], off, share, len(skipped)
+
+
 def chamfer_max(pc0, pc1):
     """Two-sided Hausdorff distance (evaluation-shapenet.py:122-135), two cs_hausdorff_1dir problems."""
     dev = torch.device("cuda")
@@ -186,7 +270,7 @@ def get_symmetry_label(pc, cd_threshold):
     return 0
 
 
-def evaluate(pipe, clouds, cfg=None, pairs_per_batch=16, seed=None, force_gate=False):
+def evaluate(pipe, clouds, cfg=None, pairs_per_batch=16, seed=None, force_gate=False, stat=None):
     """clouds: list of raw [n,3] arrays.  Returns a list of result dicts (one per model x pose) with
     the keys of registration_worker (evaluation-shapenet.py:242-275); with cfg.icp_max_iter > 0 also T_est_icp, rte_icp,
     rre_icp, chamfer_dist_icp and icp_iters of the refined pose.  cfg.max_log_scale > 0: the posed copy is s R x + t with
@@ -194,8 +278,11 @@ def evaluate(pipe, clouds, cfg=None, pairs_per_batch=16, seed=None, force_gate=F
     eval_pose's on it with its 3x3 block divided by the fitted scale, and the results gain scale_gt, scale_icp and
     scale_err_icp = |scale_icp / scale_gt - 1|.  cfg.features = "fpfh": the descriptors are cs_fpfh's (FpfhPipe; `pipe` may
     be None, no checkpoint is needed) and the registration runs without the symmetry hypotheses, so the *_sym entries equal
-    the *_ransac ones; the result keys do not change."""
+    the *_ransac ones; the result keys do not change.  cfg.partial_view: the posed copy of every job is reduced to
+    what one camera sees of it (partial_views) before the descriptors; every result gains visible_share, and a dict passed as
+    `stat` gains stat["partial_view"] = {clouds, rows_in, rows_visible, views_skipped}."""
     cfg = cfg or Config()
+    cfg.check_partial_view()
     if cfg.features not in ("network", "fpfh"):
         raise ValueError("Config.features must be 'network' or 'fpfh', got %r" % (cfg.features,))
     cfg.check_registration()
@@ -215,19 +302,9 @@ def evaluate(pipe, clouds, cfg=None, pairs_per_batch=16, seed=None, force_gate=F
         raise ValueError("Config.max_log_scale must be finite and >= 0, got %r" % (cfg.max_log_scale,))
     rng = np.random.default_rng(cfg.random_seed if seed is None else seed)
     dev = pipe.device
-    jobs = []
-    for mi, raw in enumerate(clouds):
-        pc = load_pc(raw)
-        label = get_symmetry_label(pc, cfg.symmetry_cd_threshold)
-        for pi in range(cfg.n_poses_per_model):
-            pose = generate_random_pose(cfg, rng)
-            # generate_test_pc_pair (:115-119): the model stays in its own type, the posed copy is the f64
-            # product with the f64 pose; quantize_pc (:97-107) floors each in its type and narrows afterwards
-            if cfg.max_log_scale > 0:
-                s_gt = float(np.exp(rng.uniform(-cfg.max_log_scale, cfg.max_log_scale)))
-                jobs.append((mi, pi, pc, s_gt * (pc @ pose[:3, :3].T) + pose[:3, [3]].T, pose, label, s_gt))
-            else:
-                jobs.append((mi, pi, pc, pc @ pose[:3, :3].T + pose[:3, [3]].T, pose, label, 1.0))
+    jobs = build_jobs(clouds, cfg, rng)
+    view_seed = cfg.random_seed if seed is None else seed
+    view_stat = dict(clouds=0, rows_in=0, rows_visible=0, views_skipped=0)
     results = []
     for s in range(0, len(jobs), pairs_per_batch):
         chunk = jobs[s:s + pairs_per_batch]
@@ -235,7 +312,15 @@ def evaluate(pipe, clouds, cfg=None, pairs_per_batch=16, seed=None, force_gate=F
         groups = []
         for col in (2, 3):
             xyz = torch.from_numpy(np.concatenate([j[col] for j in chunk])).to(dev)
-            groups.append((xyz, np.concatenate([[0], np.cumsum([len(j[col]) for j in chunk])]).tolist()))
+            offsets = np.concatenate([[0], np.cumsum([len(j[col]) for j in chunk])]).tolist()
+            if col == 3 and cfg.partial_view:
+                rows_in = offsets[-1]
+                xyz, offsets, shares, skipped = partial_views(xyz, offsets, [j[col] for j in chunk], cfg, view_seed, s)
+                view_stat["clouds"] += len(chunk)
+                view_stat["rows_in"] += int(rows_in)
+                view_stat["rows_visible"] += int(offsets[-1])
+                view_stat["views_skipped"] += int(skipped)
+            groups.append((xyz, offsets))
         es = pipe.embed_groups(groups, cfg.voxel_size)
         P = len(chunk)
         base = es.gather(list(range(P)))
@@ -263,6 +348,8 @@ def evaluate(pipe, clouds, cfg=None, pairs_per_batch=16, seed=None, force_gate=F
                                 rte_ransac=float(rte_r), rre_ransac=float(rre_r), pose_gt=pose))
             if scale_on:
                 results[-1]["scale_gt"] = s_gt
+            if cfg.partial_view:
+                results[-1]["visible_share"] = float(shares[i])
         if icp_on:
             Ti, cdi, iti = res.T_icp.cpu().numpy(), res.cd_icp.cpu().numpy(), res.icp_iters.cpu().numpy()
             sci = res.icp_scale.cpu().numpy() if scale_on else None
@@ -276,7 +363,13 @@ def evaluate(pipe, clouds, cfg=None, pairs_per_batch=16, seed=None, force_gate=F
                                       rre_icp=float(rre_i), icp_iters=int(iti[i]))
                 if scale_on:
                     results[s + i].update(scale_icp=float(sci[i]), scale_err_icp=float(abs(sci[i] / s_gt - 1.0)))
+    if cfg.partial_view and stat is not None:
+        stat["partial_view"] = view_stat
     return results
+
+
+def _has_view(results):
+    return bool(results) and "visible_share" in results[0]
 
 
 def _has_icp(results):
@@ -306,28 +399,34 @@ CSV_COLUMNS = ("model", "pose_idx", "symmetry_label", "sym_success", "rte_sym", 
                "rre_ransac", "cd_ransac")            # evaluation-shapenet.py:323-334
 ICP_CSV_COLUMNS = ("rte_icp", "rre_icp", "cd_icp", "icp_iters")      # trailing, only when the refinement ran
 SCALE_CSV_COLUMNS = ("scale_gt", "scale_icp", "scale_err_icp")       # trailing, only when the refinement fitted a scale
+VIEW_CSV_COLUMNS = ("visible_share",)                                # trailing, only when the posed copies were partial views
 SCALE_THRESHOLDS = (0.05, 0.10, 0.20)
 
 
 def write_results(results, names, csv_file, npz_file):
     """results-*.csv with the reference's columns and poses-*.npz with poses_gt / poses_pred_sym / poses_pred_ransac
     (evaluation-shapenet.py:345-380); results of a run with ICP refinement add the trailing ICP_CSV_COLUMNS and
-    poses_pred_icp, those of one with a fitted scale also the SCALE_CSV_COLUMNS and the arrays of the same names."""
+    poses_pred_icp, those of one with a fitted scale also the SCALE_CSV_COLUMNS and the arrays of the same names, those of one
+    on partial views the VIEW_CSV_COLUMNS and the array visible_share."""
     import csv
 
     icp = _has_icp(results)
     sc = _has_scale(results)
+    pv = _has_view(results)
     with open(csv_file, "w", newline="") as f:
         w = csv.writer(f)
-        w.writerow(CSV_COLUMNS + (ICP_CSV_COLUMNS if icp else ()) + (SCALE_CSV_COLUMNS if sc else ()))
+        w.writerow(CSV_COLUMNS + (ICP_CSV_COLUMNS if icp else ()) + (SCALE_CSV_COLUMNS if sc else ()) +
+                   (VIEW_CSV_COLUMNS if pv else ()))
         for r in results:
             w.writerow([names[r["model"]], r["pose_idx"], r["symmetry_label"], r["sym_success"], r["rte_sym"], r["rre_sym"],
                         r["chamfer_dist_sym"], r["rte_ransac"], r["rre_ransac"], r["chamfer_dist_ransac"]] +
                        ([r["rte_icp"], r["rre_icp"], r["chamfer_dist_icp"], r["icp_iters"]] if icp else []) +
-                       ([r[k] for k in SCALE_CSV_COLUMNS] if sc else []))
+                       ([r[k] for k in SCALE_CSV_COLUMNS] if sc else []) + ([r[k] for k in VIEW_CSV_COLUMNS] if pv else []))
     extra = {"poses_pred_icp": np.stack([r["T_est_icp"] for r in results])} if icp else {}
     if sc:
         extra.update({k: np.asarray([r[k] for r in results], np.float64) for k in SCALE_CSV_COLUMNS})
+    if pv:
+        extra.update({k: np.asarray([r[k] for r in results], np.float64) for k in VIEW_CSV_COLUMNS})
     with open(npz_file, "wb") as f:
         np.savez(f, poses_gt=np.stack([r["pose_gt"] for r in results]),
                  poses_pred_sym=np.stack([r["T_est_sym"] for r in results]),
@@ -411,6 +510,19 @@ def build_parser():
                     help="ransac_fm keeps every 1-NN match instead of the mutual ones (untuned, no real scan measured)")
     ap.add_argument("--fm-iterations", type=int, default=100000,
                     help="hypotheses per pair of ransac_fm, a fixed number (Open3D's default; untuned, no real scan measured)")
+    ap.add_argument("--partial-view", action="store_true",
+                    help="reduce the posed copy of every pair to what one virtual depth camera sees of it (cs_render_views; "
+                         "the model stays whole)")
+    ap.add_argument("--view-fov", type=float, default=40.0,
+                    help="field of view of that camera in degrees, in (0, 180) (untuned, no real scan measured)")
+    ap.add_argument("--view-size", type=int, default=256,
+                    help="side of its square image in pixels, in [1, 4096] (untuned, no real scan measured)")
+    ap.add_argument("--view-distance", type=float, default=3.0,
+                    help="its distance from the cloud in half diagonals of the bounding box, > 1 (untuned, no real scan measured)")
+    ap.add_argument("--view-point-size", type=float, default=1.5,
+                    help="side of a row's square in voxels (untuned, no real scan measured)")
+    ap.add_argument("--view-depth-tol", type=float, default=1.5,
+                    help="depth tolerance of the visibility test in voxels (untuned, no real scan measured)")
     ap.add_argument("--out-dir", default=".")
     ap.add_argument("--device", default="cuda", choices=["cuda"])
     return ap
@@ -449,14 +561,22 @@ def main(argv=None):
                  icp_with_scaling=a.icp_with_scaling, icp_scale_bounds=(a.icp_scale_min, a.icp_scale_max),
                  registration=a.registration, fgr_mu_floor=a.fgr_mu_floor, gicp_epsilon=a.gicp_epsilon, features=a.features,
                  fpfh_radius=a.fpfh_radius, fpfh_max_nn=a.fpfh_max_nn, fm_ransac_n=a.fm_ransac_n,
-                 fm_edge_similarity=a.fm_edge_similarity, fm_mutual=not a.fm_no_mutual, fm_iterations=a.fm_iterations)
-    results = evaluate(pipe, clouds, cfg)
+                 fm_edge_similarity=a.fm_edge_similarity, fm_mutual=not a.fm_no_mutual, fm_iterations=a.fm_iterations,
+                 partial_view=a.partial_view, view_fov_deg=a.view_fov, view_size=a.view_size, view_distance=a.view_distance,
+                 view_point_size=a.view_point_size, view_depth_tol=a.view_depth_tol)
+    cfg.check_partial_view()
+    stat = {}
+    results = evaluate(pipe, clouds, cfg, stat=stat)
     postfix = f"shapenet-seed{a.random_seed}-{a.category}-{len(files)}-{a.n_poses_per_model}"
     os.makedirs(a.out_dir, exist_ok=True)
     csv_file = os.path.join(a.out_dir, f"results-{postfix}.csv")
     npz_file = os.path.join(a.out_dir, f"poses-{postfix}.npz")
     write_results(results, files, csv_file, npz_file)
     print(summary(results))
+    if "partial_view" in stat:
+        pv = stat["partial_view"]
+        print("partial views: %d clouds, %d of %d rows visible, %d views skipped"
+              % (pv["clouds"], pv["rows_visible"], pv["rows_in"], pv["views_skipped"]))
     return results, csv_file, npz_file
 
 

@@ -1289,11 +1289,66 @@ int cs_ransac_fm_batch(const float* d_src, const float* d_tgt, const int64_t* h_
                        uint64_t seed, double* d_T, int32_t* d_stat, double* d_rmse, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Partial views: a virtual depth camera per segment -- hidden-point removal by a splat z-buffer.  The reference
+ * has no such step, so this comment is the specification and tests/view_ref.py restates it bit for bit.  As in the blocks
+ * above: every operation is ONE IEEE f64 operation in the order given, or an explicit fma; nothing is contracted; only
+ * + - * / floor fma min, comparisons and integer arithmetic appear (min(a, b) = a < b ? a : b); every threshold is STRICT; a
+ * comparison with a NaN is false.
+ *
+ * cs_render_views: d_xyz f32 [n,3]; h_off int64 [n_seg + 1] host offsets; segment s is seen by camera s.  d_cam f64
+ *   [n_seg,12] on the device: the rows R | t of the rigid world -> camera map, row c = (R_c0, R_c1, R_c2, t_c); the camera
+ *   looks along +z.  width, height in [1, 4096]; focal (pixels), point_size and depth_tol (world units) finite and > 0.
+ *   d_visible u8 [n] (0 / 1); d_depth f32 [n_seg, height, width] or NULL; d_stat int32 [n_seg,4].
+ *   Per row (x, y, z), widened to f64, of segment s:
+ *     P_c = fma(R_c2, z, fma(R_c1, y, fma(R_c0, x, t_c))), c = 0, 1, 2 (the pose chain of cs_ransac_batch's count and of
+ *       cs_ransac_fm_batch, restated in the unit); Z = P_2.
+ *     The row is IN FRONT when P_0, P_1 and P_2 are finite and Z > 0.  Nothing below is formed for another row.
+ *     u = fma(focal, P_0 / Z, 0.5 * width), v = fma(focal, P_1 / Z, 0.5 * height) (width and height converted to f64).
+ *     h = min(((0.5 * focal) * point_size) / Z, 16.0): half the side of the row's square in pixels.  The cap of 16 pixels is
+ *       part of the semantics: it bounds the work of a row that sits on the lens to 33 x 33 pixels.
+ *     Centre pixel: (cu, cv) = (floor(u), floor(v)).  The row is IN FRAME when 0 <= cu < width && 0 <= cv < height, compared
+ *       as doubles.
+ *     Footprint: the pixel columns floor(u - h) .. floor(u + h) and the rows floor(v - h) .. floor(v + h), each value
+ *       clamped AS A DOUBLE to [-1, width] (to [-1, height]) before the conversion to int, then clipped to the image.  A row
+ *       that is in front but out of frame still covers what its footprint reaches.
+ *   Depth buffer: zbuf[s,y,x] = the minimum Z over the in-front rows of segment s whose footprint covers (x, y), +inf
+ *     without one.  Positive finite doubles order as their bit patterns: one u64 atomicMin per covered pixel, order-free.
+ *   Visible: in front, in frame, and Z - zbuf[s,cv,cu] < depth_tol.  A row's own footprint holds its centre pixel (floor is
+ *     monotonic and h >= 0), so the difference is >= 0.
+ *   d_visible = the mask.  d_depth = the buffer converted ONCE to f32 (round to nearest even; +inf stays, a Z above the
+ *     largest float becomes +inf).  d_stat[s] = (rows in front, rows in frame, rows visible, pixels whose f64 depth is
+ *     finite).
+ *   Independence: the result of a segment is a function of the SET of its rows and of its camera.  A permuted segment gives
+ *     the permuted mask and the same depth image and stat row, bit for bit; batch neighbours, the stream, the launch shape
+ *     (CS_VIEW_CHUNK_BYTES, CS_VIEW_PRECHECK) and the run do not reach it.
+ *   Grazing surfaces: a row whose surface is seen at a flat angle can be hidden by a NEIGHBOUR's camera-facing square that
+ *     covers its centre pixel from more than depth_tol in front; a square below about one row spacing lets rows of the far
+ *     side through between the near ones (tests/test_view_cpu.py).  A depth sensor loses grazing surfaces too.
+ *   n_seg = 0 and empty segments are legal: an empty segment has an all-+inf image and a zero stat row.
+ *   Refused (CS_ERR_INVALID): a NULL offset table, a negative count, offsets that decrease; focal, point_size or depth_tol
+ *     not finite or <= 0; NULL d_cam or d_stat with n_seg > 0; NULL d_xyz or d_visible while a row exists;
+ *     (CS_ERR_UNSUPPORTED): width or height outside [1, 4096], a segment of 2^31 rows or more.  The checks come before any
+ *     device work.
+ *   Differences from [O3D-knowledge] Open3D's hidden_point_removal (Katz's operator: spherical flipping and a convex hull):
+ *     no hull; a pinhole image of a fixed resolution decides, so the result depends on width, height, point_size and
+ *     depth_tol, and rows outside the image are never visible.
+ *   Kernels (view.hip), per chunk of whole segments whose buffers (8 B x height x width each) fit CS_VIEW_CHUNK_BYTES (read
+ *     per call, default 256 MiB, never fewer than one segment): a fill, the splat (one lane per row), the resolve (one lane
+ *     per row, integer stat atomics) and the export (one lane per pixel).  CS_VIEW_PRECHECK=0 (read per call) drops the read
+ *     of a pixel before its atomic; the buffer only decreases, so the read changes no result.  Everything is enqueued on
+ *     `stream`; scratch comes from the calling thread's pool; no host wait, no cooperative launch, no flag a thread waits
+ *     on; the only atomics are integer.  Profile family "view", one scope per call.
+ * ---------------------------------------------------------------------------------------- */
+int cs_render_views(const float* d_xyz, const int64_t* h_off, int n_seg, const double* d_cam, int width, int height,
+                    double focal, double point_size, double depth_tol, uint8_t* d_visible, float* d_depth, int32_t* d_stat,
+                    void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Profiling hooks for bench.py: when enabled the library brackets the launches of each named
  * kernel family with hipEvents on the launch stream and accumulates the elapsed time.
  * names: "conv", "ransac_eval", "ransac_pre", "ransac_hyp", "knn", "chamfer", "topk", "symcut",
  * "kmap", "loss", "hardneg", "icp", "normals", "fgr", "chamfer2", "fpfh", "orient", "outlier", "cluster", "plane",
- * "featmatch".
+ * "featmatch", "view".
  * ---------------------------------------------------------------------------------------- */
 void cs_prof_enable(int on);
 void cs_prof_reset(void);
