@@ -132,6 +132,7 @@ def _declare(lib):
                                    vp]),
         "cs_ransac_fm_batch": (c_int, [vp, vp, POINTER(c_int64), vp, c_int, c_double, c_int, c_double, c_int, c_int64,
                                        c_uint64, vp, vp, vp, vp]),
+        "cs_sc2_batch": (c_int, [vp, vp, POINTER(c_int64), vp, c_int, c_double, c_double, c_int, c_int, vp, vp, vp, vp, vp]),
         "cs_render_views": (c_int, [vp, POINTER(c_int64), c_int, vp, c_int, c_int, c_double, c_double, c_double, vp, vp, vp,
                                     vp]),
         "cs_prof_enable": (None, [c_int]),

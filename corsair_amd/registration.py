@@ -30,6 +30,7 @@ import torch
 from . import _helper
 from . import backend as B
 from . import featmatch as FM
+from . import sc2 as S2
 from ._lib import to_host
 
 ANCHOR_KEY = 0x5A11C0DE
@@ -171,9 +172,10 @@ def _sym_pose_batch(estimator, baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_
                     icp_estimation="point", icp_normal_k=16, normals1=None, icp_normal_radius=None, icp_with_scaling=False,
                     icp_scale_bounds=None, icp_kernel="l2", icp_kernel_scale=None):
     """The body of sym_pose_batch (below, with the documentation).  estimator = (registration, fgr_mu_floor,
-    fgr_iterations, fgr_tuple_test, normals0, gicp_epsilon, fm), the keyword-only options; the first four and fm =
-    (fm_ransac_n, fm_edge_similarity, fm_mutual, fm_iterations) already checked."""
-    registration, fgr_mu_floor, fgr_iterations, fgr_tuple_test, normals0, gicp_epsilon, fm = estimator
+    fgr_iterations, fgr_tuple_test, normals0, gicp_epsilon, fm, sc2), the keyword-only options; the first four, fm =
+    (fm_ransac_n, fm_edge_similarity, fm_mutual, fm_iterations) and sc2 = (sc2_compat_dist, sc2_seeds, sc2_k) already
+    checked."""
+    registration, fgr_mu_floor, fgr_iterations, fgr_tuple_test, normals0, gicp_epsilon, fm, sc2 = estimator
     if registration == "ransac_fm" and use_symmetry:
         raise ValueError("sym_pose_batch: registration 'ransac_fm' needs use_symmetry=False (the part configurations are out "
                          "of scope)")
@@ -357,6 +359,9 @@ def _sym_pose_batch(estimator, baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_
             r = FM.ransac_fm_batch(src, tgt, offs, max_corr, m=fm_m, ransac_n=fm[0], edge_similarity=fm[1],
                                    check_distance=True, iterations=fm[3], seed=seed)
             T, inl, rmse, iters = r.T.to(torch.float32), r.inliers.contiguous(), r.rmse, r.n_valid.contiguous()
+        elif registration == "sc2":
+            r = S2.sc2_batch(src, tgt, offs, max_corr, sc2[0], n_seeds=sc2[1], k_consensus=sc2[2])
+            T, inl, rmse, iters = r.T.to(torch.float32), r.inliers.contiguous(), r.rmse, r.n_valid.contiguous()
         else:
             T, inl, rmse, iters = B.ransac_batch(src, tgt, offs, max_corr, 10, max_iter, confidence, seed)
     else:
@@ -428,6 +433,21 @@ def check_fm_options(ransac_n, edge_similarity, mutual, iterations, who="sym_pos
     return int(ransac_n), float(edge_similarity), bool(mutual), int(iterations)
 
 
+def check_sc2_options(compat_dist, seeds, k, max_corr, who="sym_pose_batch"):
+    """The sc2_* options of registration = "sc2" as (compat_dist, seeds, k), or ValueError.  compat_dist None = max_corr / 2
+    (untuned)."""
+    if compat_dist is None:
+        compat_dist = 0.5 * max_corr
+    if isinstance(compat_dist, bool) or not isinstance(compat_dist, (int, float, np.floating)) or \
+            not 0.0 < compat_dist < float("inf"):
+        raise ValueError("%s: sc2_compat_dist must be positive and finite, got %r" % (who, compat_dist))
+    if isinstance(seeds, bool) or not isinstance(seeds, (int, np.integer)) or not 0 <= seeds < 2 ** 31:
+        raise ValueError("%s: sc2_seeds must be an integer in [0, 2^31) (0 = every correspondence), got %r" % (who, seeds))
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 2 <= k <= 64:
+        raise ValueError("%s: sc2_k must be an integer in [2, 64], got %r" % (who, k))
+    return float(compat_dist), int(seeds), int(k)
+
+
 def sym_pose_batch(*args, registration="ransac", fgr_mu_floor=0.025, fgr_iterations=64, fgr_tuple_test=True, **kwargs):
     """baseF f32 [N0,16], xyz0 f32 [N0,3] (query voxels of all pairs, segment p = off0[p]:off0[p+1]);
     posF/xyz1/off1 likewise for the CAD side; pos_syms: symmetry label per pair.
@@ -477,14 +497,27 @@ def sym_pose_batch(*args, registration="ransac", fgr_mu_floor=0.025, fgr_iterati
     are filled from it and stages 5 - 7 are what they are for the RANSAC.  fm_ransac_n = 3, fm_edge_similarity = 0.9,
     fm_mutual = True, fm_iterations = 100000 are Open3D's defaults, untuned, no real scan measured; like normals0 they are
     accepted by keyword only and taken out of **kwargs here.  It needs use_symmetry=False (ValueError otherwise); max_iter
-    and confidence are unused.  With "ransac" and "fgr" nothing of it is launched."""
-    if registration not in ("ransac", "fgr", "ransac_fm"):
-        raise ValueError("sym_pose_batch: registration must be 'ransac', 'fgr' or 'ransac_fm', got %r" % (registration,))
+    and confidence are unused.  With "ransac" and "fgr" nothing of it is launched.
+    registration = "sc2": the compatibility-graph estimator, for lists with an inlier share of a few per cent.
+    Stage 1 is unchanged (the k_nn lists); stage 4 sends the SAME lists "fgr" gets -- the vanilla list and every part
+    configuration, so use_symmetry=True works -- through ONE cs_sc2_batch call (sc2.sc2_batch): sc2_seeds rows of the largest
+    degree in the graph of correspondences whose lengths agree within sc2_compat_dist, each fitted over its sc2_k best
+    neighbours, the pose with the most inliers at max_corr.  T_all, inliers and iters (= the valid seeds) are filled from it
+    and stages 5 - 7 are what they are for the RANSAC.  sc2_compat_dist = None (half of max_corr), sc2_seeds = 1024 and
+    sc2_k = 20 are UNTUNED, no real scan measured; keyword-only, taken out of **kwargs here.  A list of more than 32 768
+    correspondences is refused by the library (a smaller k_nn).  max_iter, confidence and seed are unused.  With "ransac",
+    "fgr" and "ransac_fm" nothing of it is launched."""
+    if registration not in ("ransac", "fgr", "ransac_fm", "sc2"):
+        raise ValueError("sym_pose_batch: registration must be 'ransac', 'fgr', 'ransac_fm' or 'sc2', got %r"
+                         % (registration,))
     normals0, gicp_epsilon = kwargs.pop("normals0", None), kwargs.pop("gicp_epsilon", 1e-3)
     fm = check_fm_options(kwargs.pop("fm_ransac_n", 3), kwargs.pop("fm_edge_similarity", 0.9), kwargs.pop("fm_mutual", True),
                           kwargs.pop("fm_iterations", 100000))
-    return _sym_pose_batch((registration, fgr_mu_floor, fgr_iterations, fgr_tuple_test, normals0, gicp_epsilon, fm), *args,
-                           **kwargs)
+    max_corr = kwargs["max_corr"] if "max_corr" in kwargs else (args[8] if len(args) > 8 else 0.20)
+    sc2 = check_sc2_options(kwargs.pop("sc2_compat_dist", None), kwargs.pop("sc2_seeds", 1024), kwargs.pop("sc2_k", 20),
+                            max_corr)
+    return _sym_pose_batch((registration, fgr_mu_floor, fgr_iterations, fgr_tuple_test, normals0, gicp_epsilon, fm, sc2),
+                           *args, **kwargs)
 
 
 # the positional interface (everything but the keyword-only estimator options), as introspection has always shown it

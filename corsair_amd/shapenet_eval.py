@@ -64,6 +64,12 @@ class Config:
     fm_edge_similarity: float = 0.9
     fm_mutual: bool = True
     fm_iterations: int = 100000
+    # "sc2" (DESIGN 27): the compatibility-graph estimator (cs_sc2_batch) over the k_nn lists -- sc2_seeds rows of the largest
+    # degree among the correspondences whose lengths agree within sc2_compat_dist (in VOXELS), each fitted over its sc2_k best
+    # neighbours.  Every default is UNTUNED, no real scan measured.  The symmetry hypotheses stay as they are.
+    sc2_compat_dist: float = 1.0
+    sc2_seeds: int = 1024
+    sc2_k: int = 20
     # the descriptors: "network" (the ResUNet forward, needs a checkpoint) or "fpfh" (registration.fpfh_features: no weights;
     # sym_pose_batch then runs with use_symmetry=False, the part cut takes the network's widths only).  fpfh_radius is in
     # VOXELS, 5 is Open3D's example value, UNTUNED; fpfh_max_nn is cs_fpfh's max_nn
@@ -99,9 +105,12 @@ class Config:
             raise ValueError("Config.view_depth_tol must be finite and > 0 voxels, got %r" % (self.view_depth_tol,))
 
     def check_registration(self):
-        if self.registration not in ("ransac", "fgr", "ransac_fm"):
-            raise ValueError("Config.registration must be 'ransac', 'fgr' or 'ransac_fm', got %r" % (self.registration,))
+        if self.registration not in ("ransac", "fgr", "ransac_fm", "sc2"):
+            raise ValueError("Config.registration must be 'ransac', 'fgr', 'ransac_fm' or 'sc2', got %r" % (self.registration,))
         R.check_fm_options(self.fm_ransac_n, self.fm_edge_similarity, self.fm_mutual, self.fm_iterations, "Config")
+        if isinstance(self.sc2_compat_dist, bool) or not isinstance(self.sc2_compat_dist, (int, float, np.floating)):
+            raise ValueError("Config.sc2_compat_dist must be positive and finite (voxels), got %r" % (self.sc2_compat_dist,))
+        R.check_sc2_options(self.sc2_compat_dist * self.voxel_size, self.sc2_seeds, self.sc2_k, self.max_corr, "Config")
 
     def icp_distance(self):
         return self.icp_max_dist if self.icp_max_dist > 0 else 2.0 * self.voxel_size
@@ -289,6 +298,8 @@ def evaluate(pipe, clouds, cfg=None, pairs_per_batch=16, seed=None, force_gate=F
     fm_on = cfg.registration == "ransac_fm"     # no symmetry hypotheses under it (the part configurations are out of scope)
     fm_kw = dict(fm_ransac_n=cfg.fm_ransac_n, fm_edge_similarity=cfg.fm_edge_similarity, fm_mutual=cfg.fm_mutual,
                  fm_iterations=cfg.fm_iterations) if fm_on else {}
+    if cfg.registration == "sc2":
+        fm_kw = dict(sc2_compat_dist=cfg.sc2_compat_dist * cfg.voxel_size, sc2_seeds=cfg.sc2_seeds, sc2_k=cfg.sc2_k)
     fpfh_on = cfg.features == "fpfh"
     if fpfh_on:
         pipe = FpfhPipe("cuda" if pipe is None else pipe.device, cfg.fpfh_radius, cfg.fpfh_max_nn)
@@ -495,10 +506,10 @@ def build_parser():
                     help="the ICP refinement also fits an isotropic scale (needs --icp-iters > 0, no robust kernel)")
     ap.add_argument("--icp-scale-min", type=float, default=0.5, help="lower bound of the fitted scale, in (0, 1] (untuned)")
     ap.add_argument("--icp-scale-max", type=float, default=2.0, help="upper bound of the fitted scale, >= 1 (untuned)")
-    ap.add_argument("--registration", default="ransac", choices=["ransac", "fgr", "ransac_fm"],
-                    help="correspondence estimator: the reference's RANSAC, Fast Global Registration (cs_fgr_batch), or "
+    ap.add_argument("--registration", default="ransac", choices=["ransac", "fgr", "ransac_fm", "sc2"],
+                    help="correspondence estimator: the reference's RANSAC, Fast Global Registration (cs_fgr_batch), "
                          "feature-matching RANSAC with a mutual filter and pose checkers (cs_ransac_fm_batch; no symmetry "
-                         "hypotheses)")
+                         "hypotheses), or the compatibility-graph estimator for low inlier shares (cs_sc2_batch)")
     ap.add_argument("--fgr-mu-floor", type=float, default=0.025,
                     help="floor of FGR's mu, in units of the clouds' radius (Open3D's default, untuned)")
     ap.add_argument("--fm-ransac-n", type=int, default=3, choices=[3, 4],
@@ -510,6 +521,14 @@ def build_parser():
                     help="ransac_fm keeps every 1-NN match instead of the mutual ones (untuned, no real scan measured)")
     ap.add_argument("--fm-iterations", type=int, default=100000,
                     help="hypotheses per pair of ransac_fm, a fixed number (Open3D's default; untuned, no real scan measured)")
+    ap.add_argument("--sc2-compat-dist", type=float, default=1.0,
+                    help="two correspondences of --registration sc2 are compatible when their source and target distances "
+                         "differ by less than this, in voxels (untuned, no real scan measured)")
+    ap.add_argument("--sc2-seeds", type=int, default=1024,
+                    help="correspondences of the largest degree that sc2 tries, 0 = all (untuned, no real scan measured)")
+    ap.add_argument("--sc2-k", type=int, default=20,
+                    help="correspondences a seed of sc2 is fitted over beside itself, in [2, 64] (untuned, no real scan "
+                         "measured)")
     ap.add_argument("--partial-view", action="store_true",
                     help="reduce the posed copy of every pair to what one virtual depth camera sees of it (cs_render_views; "
                          "the model stays whole)")
@@ -562,6 +581,7 @@ def main(argv=None):
                  registration=a.registration, fgr_mu_floor=a.fgr_mu_floor, gicp_epsilon=a.gicp_epsilon, features=a.features,
                  fpfh_radius=a.fpfh_radius, fpfh_max_nn=a.fpfh_max_nn, fm_ransac_n=a.fm_ransac_n,
                  fm_edge_similarity=a.fm_edge_similarity, fm_mutual=not a.fm_no_mutual, fm_iterations=a.fm_iterations,
+                 sc2_compat_dist=a.sc2_compat_dist, sc2_seeds=a.sc2_seeds, sc2_k=a.sc2_k,
                  partial_view=a.partial_view, view_fov_deg=a.view_fov, view_size=a.view_size, view_distance=a.view_distance,
                  view_point_size=a.view_point_size, view_depth_tol=a.view_depth_tol)
     cfg.check_partial_view()

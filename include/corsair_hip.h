@@ -1289,6 +1289,79 @@ int cs_ransac_fm_batch(const float* d_src, const float* d_tgt, const int64_t* h_
                        uint64_t seed, double* d_T, int32_t* d_stat, double* d_rmse, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The compatibility-graph correspondence estimator: a pose from a correspondence list whose inlier share is a few
+ * per cent, by searching the graph of pairwise length-compatible correspondences instead of sampling it (the family of
+ * spectral matching, Leordeanu and Hebert 2005, and SC2-PCR, Chen et al. 2022, as remembered from the papers; the list of
+ * differences is at the end).  The reference has no such step, so this comment is the specification and tests/sc2_ref.py
+ * restates it bit for bit.  As in the blocks above: every operation is ONE IEEE f64 operation in the order given (sums
+ * without parentheses from left to right), or an explicit fma; nothing is contracted; every threshold is STRICT; a comparison
+ * with a NaN is false.  Everything is enqueued on `stream`; scratch comes from the calling thread's pool; no host wait, no
+ * cooperative launch, no flag a thread waits on; the only atomics are integer; every loop is bounded by an argument or a
+ * problem's rows.  Profile family "sc2", one scope per call.
+ *
+ * cs_sc2_batch: d_src, d_tgt f32 [M,3], pair i = (s_i, q_i) widened to f64; problem p owns the slots [h_off[p], h_off[p+1])
+ *   (cs_ransac_fm_batch's layout; h_off int64 [n_prob + 1] on the host) of which the first m = min(max(d_m[p], 0), capacity)
+ *   hold pairs; d_m int32 [n_prob] on the device, NULL = every list is full.  compat_dist (tau) and max_corr finite and > 0;
+ *   n_seeds >= 0, 0 = every row is a seed; k_consensus = K in [2, 64].  d_T f64 [n_prob,4,4]; d_stat int32 [n_prob,6]; d_rmse
+ *   f64 [n_prob]; d_inlier u8 [h_off[n_prob]] or NULL.  tau2 = tau * tau and thr2 = max_corr * max_corr, each formed once.
+ *   a. Compatibility of the rows i != j, both FINITE (all six coordinates): with e = s_i - s_j and f = q_i - q_j,
+ *        ls2 = fma(e_z, e_z, fma(e_y, e_y, e_x * e_x)), lt2 likewise of f, a = (ls2 + lt2) - tau2,
+ *        c_ij = ls2 > 0 && lt2 > 0 && (a < 0 || a * a < 4.0 * (ls2 * lt2)).
+ *      This is | |e| - |f| | < tau without a square root (square twice; a < 0 is the case in which the first squaring is
+ *      not an equivalence).  It is symmetric in i and j to the bit (e and f change sign, the squares do not), so the matrix
+ *      may be built from one triangle.  Two matches of one source point (ls2 = 0, as k-NN lists have them) or onto one target
+ *      point (lt2 = 0) are never compatible.  c_ii = 0.  A row that is not finite is compatible with nothing.  A tau whose
+ *      square overflows to +inf makes every two finite rows with ls2 > 0, lt2 > 0 and a finite ls2 + lt2 compatible; one
+ *      whose square underflows to 0 leaves the comparison a * a < 4 (ls2 * lt2) as its rounding decides it.
+ *   b. Degrees and seeds: deg_i = sum_j c_ij.  The seeds are the rows of rank < S under the key (deg_i << 32) | ~i (~i: the
+ *      32-bit complement), the largest key first: the largest degree, ties to the SMALLEST row.  S = m with n_seeds = 0,
+ *      else min(n_seeds, m).  The seed of rank r is hypothesis r.
+ *   c. Second-order count of a seed s and a row j with c_sj = 1: sc_sj = the rows k with c_sk = 1 and c_jk = 1
+ *      (popcount(row_s & row_j)).
+ *   d. Consensus set A_s: s and the min(K, deg_s) rows j with c_sj = 1 of the largest key (sc_sj << 32) | ~j (ties to the
+ *      smallest row).  |A_s| < 3 makes the seed INVALID.
+ *   e. Fit over A_s, its rows taken in ASCENDING ROW INDEX, cs_ransac_fm_batch's fit formulas at n = |A_s|: the centroids by
+ *      the left-to-right sum from 0 divided by (double)n, S_xy by fma in that order, Horn's N, horn_qcp ALONE (a fit it
+ *      declines makes the seed INVALID), the same normalisation, R and t.  A value of R or t that is not finite makes the
+ *      seed INVALID.
+ *   f. Count: count_r = the pairs i < m with d2 < thr2, d2 by the canonical chain of the posed source (cs_ransac_fm_batch).
+ *   g. Best: the largest count; ties go to the SMALLEST rank (a u64 maximum of count << 32 | ~r).  m < 3, no valid seed, or a
+ *      best count < 3: found = 0, d_T = the identity, d_stat = (0, -1, 0, n_valid, -1, 0), d_rmse = 0.  Otherwise
+ *      d_T = (R | t; 0 0 0 1) of the best seed -- there is NO refit over the inliers, the ICP stage follows -- and
+ *      d_stat = (1, the seed's row, count, n_valid, its rank, its degree), n_valid = the valid seeds.  d_rmse follows
+ *      cs_ransac_fm_batch's fixed-point rule (the same k, the same truncation).  d_inlier = the best pose's mask (d2 < thr2)
+ *      over the first m slots of the problem and 0 in the slots behind them and in every slot of a problem without a pose;
+ *      slots before h_off[0] are written with 0.
+ *   Rows with a NaN or infinite coordinate are compatible with nothing and never inliers.  A max_corr whose square overflows
+ *     counts every pair with a finite d2; one whose square underflows counts nothing.
+ *   h. Independence: the result of a problem is a function of its pairs in their order and of the parameters alone.  Batch
+ *      neighbours, the capacity behind m, the stream, the launch shape (CS_SC2_CHUNK_BYTES, CS_SC2_SLICE, CS_SC2_SPAN) and the
+ *      run do not reach it.  A permutation of the pairs permutes the matrix, the degrees and the second-order counts with
+ *      it; it enters the result through the ~i tie keys (which of several rows of one degree is a seed and of which rank,
+ *      which of several rows of one count joins A_s, which of two seeds of one count wins) and through the order of the
+ *      fit's sums (the last bits of R and t) only.
+ *   n_prob = 0, empty problems and m < 3 are legal.  Refused (CS_ERR_INVALID): a NULL offset table, a negative count, offsets
+ *     that decrease, compat_dist or max_corr not positive and finite, n_seeds < 0, NULL d_T, d_stat or d_rmse with
+ *     n_prob > 0, NULL d_src or d_tgt while a slot exists; (CS_ERR_UNSUPPORTED): k_consensus outside [2, 64], a problem of
+ *     more than 32 768 slots (its bit matrix is 128 MiB; the message advises a smaller k_nn).  The checks come before any
+ *     device work.
+ *   Memory: one bit per ordered pair, sized by the CAPACITY, which the host knows (8 B x capacity x ceil(capacity / 64)).  A
+ *     call whose matrices exceed CS_SC2_CHUNK_BYTES (read per call, default 256 MiB) runs in chunks of whole consecutive
+ *     problems, never fewer than one, with the same bits.  The checks and the planner stand in corsair_amd/csrc/sc2_plan.h.
+ *   Differences from SC2-PCR and spectral matching, deliberate: NO eigenvector -- seeds are ranked by the integer degree;
+ *     no non-maximum suppression among the seeds; ONE consensus stage instead of two; an UNWEIGHTED fit; a HARD compatibility
+ *     instead of a soft one; the winner is ranked by its inlier count; NO final refit over the inliers.
+ *   Kernels (sc2.hip), per chunk: the matrix build (a lane owns a row and walks 64 wave-uniform rows per word; one triangle
+ *     and its transpose; CS_SC2_SPAN word columns per wave, default 8), the degrees by integer atomicAdd, the rank by
+ *     counting larger keys, one wave per seed for the second-order counts and the K best, one thread per seed for the fit,
+ *     the count of 256 seeds x one slice of CS_SC2_SLICE pairs (default 1024) per workgroup, the u64 atomicMax.  The same
+ *     bits for every value of the three variables.
+ * ---------------------------------------------------------------------------------------- */
+int cs_sc2_batch(const float* d_src, const float* d_tgt, const int64_t* h_off, const int32_t* d_m, int n_prob,
+                 double compat_dist, double max_corr, int n_seeds, int k_consensus, double* d_T, int32_t* d_stat,
+                 double* d_rmse, uint8_t* d_inlier, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Partial views: a virtual depth camera per segment -- hidden-point removal by a splat z-buffer.  The reference
  * has no such step, so this comment is the specification and tests/view_ref.py restates it bit for bit.  As in the blocks
  * above: every operation is ONE IEEE f64 operation in the order given, or an explicit fma; nothing is contracted; only
@@ -1348,7 +1421,7 @@ int cs_render_views(const float* d_xyz, const int64_t* h_off, int n_seg, const d
  * kernel family with hipEvents on the launch stream and accumulates the elapsed time.
  * names: "conv", "ransac_eval", "ransac_pre", "ransac_hyp", "knn", "chamfer", "topk", "symcut",
  * "kmap", "loss", "hardneg", "icp", "normals", "fgr", "chamfer2", "fpfh", "orient", "outlier", "cluster", "plane",
- * "featmatch", "view".
+ * "featmatch", "view", "sc2".
  * ---------------------------------------------------------------------------------------- */
 void cs_prof_enable(int on);
 void cs_prof_reset(void);
