@@ -135,6 +135,8 @@ def _declare(lib):
         "cs_sc2_batch": (c_int, [vp, vp, POINTER(c_int64), vp, c_int, c_double, c_double, c_int, c_int, vp, vp, vp, vp, vp]),
         "cs_render_views": (c_int, [vp, POINTER(c_int64), c_int, vp, c_int, c_int, c_double, c_double, c_double, vp, vp, vp,
                                     vp]),
+        "cs_ppf_batch": (c_int, [vp, vp, POINTER(c_int64), vp, vp, POINTER(c_int64), POINTER(c_int32), POINTER(c_int32), c_int,
+                                 POINTER(c_double), c_double, c_int, c_int, vp, vp, vp, vp, vp, vp, vp]),
         "cs_prof_enable": (None, [c_int]),
         "cs_prof_reset": (None, []),
         "cs_prof_get": (c_int, [c_char_p, POINTER(c_double), POINTER(c_int64)]),

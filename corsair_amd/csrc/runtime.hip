@@ -239,7 +239,7 @@ static const char* kProfNames[] = {"conv",    "ransac_eval", "ransac_hyp", "knn"
                                    "hardneg", "icp",         "normals",    "fgr",
                                    "chamfer2", "fpfh",       "orient",     "outlier",
                                    "cluster", "plane",      "featmatch",  "view",
-                                   "sc2"};
+                                   "sc2",     "ppf"};
 static constexpr int kNumProf = sizeof(kProfNames) / sizeof(kProfNames[0]);
 static int g_prof_on = 0;
 static std::atomic<uint64_t> g_prof_epoch{1};   // bumped by cs_prof_reset: deferred units of an older region are dropped

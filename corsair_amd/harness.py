@@ -187,6 +187,9 @@ class Config:
         if self.registration == "sc2":
             raise ValueError("Config.registration 'sc2' (the compatibility-graph estimator, DESIGN 27) is not wired into the harness, "
                              "the sharded evaluation or the cache format: use registration.sym_pose_batch or shapenet_eval")
+        if self.registration == "ppf":
+            raise ValueError("Config.registration 'ppf' (point-pair-feature voting, DESIGN 28) is not wired into the harness, "
+                             "the sharded evaluation or the cache format: use registration.sym_pose_batch or shapenet_eval")
         if self.registration not in ("ransac", "fgr"):
             raise ValueError("Config.registration must be 'ransac' or 'fgr', got %r" % (self.registration,))
         if not (0.0 < float(self.fgr_mu_floor) < float("inf")):

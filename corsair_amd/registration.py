@@ -30,6 +30,7 @@ import torch
 from . import _helper
 from . import backend as B
 from . import featmatch as FM
+from . import ppf as PPF
 from . import sc2 as S2
 from ._lib import to_host
 
@@ -172,16 +173,18 @@ def _sym_pose_batch(estimator, baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_
                     icp_estimation="point", icp_normal_k=16, normals1=None, icp_normal_radius=None, icp_with_scaling=False,
                     icp_scale_bounds=None, icp_kernel="l2", icp_kernel_scale=None):
     """The body of sym_pose_batch (below, with the documentation).  estimator = (registration, fgr_mu_floor,
-    fgr_iterations, fgr_tuple_test, normals0, gicp_epsilon, fm, sc2), the keyword-only options; the first four, fm =
-    (fm_ransac_n, fm_edge_similarity, fm_mutual, fm_iterations) and sc2 = (sc2_compat_dist, sc2_seeds, sc2_k) already
-    checked."""
-    registration, fgr_mu_floor, fgr_iterations, fgr_tuple_test, normals0, gicp_epsilon, fm, sc2 = estimator
+    fgr_iterations, fgr_tuple_test, normals0, gicp_epsilon, fm, sc2, ppf), the keyword-only options; the first four, fm =
+    (fm_ransac_n, fm_edge_similarity, fm_mutual, fm_iterations), sc2 = (sc2_compat_dist, sc2_seeds, sc2_k) and ppf =
+    (scene_side, dist_step, ref_step, n_cand, view_points) already checked."""
+    registration, fgr_mu_floor, fgr_iterations, fgr_tuple_test, normals0, gicp_epsilon, fm, sc2, ppf = estimator
+    if registration == "ppf" and use_symmetry:
+        raise ValueError("sym_pose_batch: registration 'ppf' needs use_symmetry=False (symmetry hypotheses are out of scope)")
     if registration == "ransac_fm" and use_symmetry:
         raise ValueError("sym_pose_batch: registration 'ransac_fm' needs use_symmetry=False (the part configurations are out "
                          "of scope)")
     if icp_estimation == "gicp" and (icp_with_scaling or icp_kernel != "l2"):
         raise ValueError("sym_pose_batch: icp_estimation 'gicp' with icp_with_scaling or a robust icp_kernel is out of scope")
-    if icp_estimation != "gicp" and normals0 is not None:
+    if icp_estimation != "gicp" and normals0 is not None and registration != "ppf":
         raise ValueError("sym_pose_batch: normals0 is used by icp_estimation = 'gicp' only")
     if icp_with_scaling and icp_kernel != "l2":
         raise ValueError("sym_pose_batch: icp_with_scaling with a robust icp_kernel (%r) is out of scope" % (icp_kernel,))
@@ -201,13 +204,76 @@ def _sym_pose_batch(estimator, baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_
     if use_symmetry and baseF.shape[1] not in (16, 32):
         raise ValueError("sym_pose_batch: use_symmetry needs 16- or 32-wide descriptors (cs_symcut_fit), got %d columns; "
                          "FPFH descriptors (33) register with use_symmetry=False" % (baseF.shape[1],))
-    dev = baseF.device
+    dev = xyz0.device if registration == "ppf" else baseF.device      # "ppf" reads no descriptors: they may be None
     P = len(off0) - 1
     off0 = [int(v) for v in off0]
     off1 = [int(v) for v in off1]
     n0 = [off0[p + 1] - off0[p] for p in range(P)]
     n1 = [off1[p + 1] - off1[p] for p in range(P)]
     k = 1 if registration == "ransac_fm" else k_nn      # the feature-matching recipe takes 1-NN matches; k_nn is not used
+
+    def finish(T, inl, iters, prob_pair, prob_cfg, ok, nonfinite):
+        """Stages 5 - 7, the same behind every estimator."""
+        # ---- 5. Chamfer of every estimate (utils/preprocess.py:39-48,67-70) -----------------------------
+        cd = B.chamfer_1dir(xyz0, off0, xyz1, off1, prob_pair, prob_pair, T)
+
+        # ---- 6. best hypothesis per pair: first minimum, vanilla first (utils/symmetry.py:322-324) ----
+        if nonfinite is not None:
+            cd_h, bad_q, bad_c = to_host(cd, *nonfinite)   # (every launch above has finished, the helper's RANSAC included)
+            _refuse_nonfinite(bad_q, bad_c)
+        else:
+            cd_h = to_host(cd)[0]
+        pair_h = np.asarray(prob_pair)
+        best = np.arange(P)
+        for j in range(P, len(pair_h)):
+            p = pair_h[j]
+            if cd_h[best[p]] > cd_h[j]:
+                best[p] = j
+        best_t = torch.from_numpy(best).to(dev)
+        res = SymPoseResult(T_best=T[best_t], cd_best=cd[best_t], T_ransac=T[:P], cd_ransac=cd[:P],
+                            ok=ok, iters=iters, n_problems=len(prob_pair), T_all=T, cd_all=cd, inliers=inl,
+                            prob_pair=prob_pair, prob_cfg=prob_cfg, best=best)
+
+        # ---- 7. optional refinement of the kept estimate on the geometry itself (Open3D: registration_icp) ----
+        if icp_max_iter > 0:
+            pairs = list(range(P))
+            nrm = None
+            if icp_estimation in ("plane", "gicp"):
+                nrm = normals1 if normals1 is not None else B.estimate_normals(xyz1, off1, icp_normal_k, icp_normal_radius)
+            scaling = {}
+            if icp_with_scaling:
+                scaling = {"with_scaling": True}
+                if icp_scale_bounds is not None:
+                    scaling["scale_bounds"] = icp_scale_bounds
+            if icp_estimation == "gicp":     # the query voxels' normals, in the query's own (posed) frame
+                snrm = normals0 if normals0 is not None else B.estimate_normals(xyz0, off0, icp_normal_k, icp_normal_radius)
+                scaling = {"estimation": "gicp", "src_normals": snrm, "gicp_epsilon": gicp_epsilon}
+            r = B.icp_batch(xyz0, off0, xyz1, off1, pairs, pairs, res.T_best, icp_max_dist, icp_max_iter, tgt_normals=nrm,
+                            kernel=icp_kernel, kernel_scale=icp_kernel_scale, **scaling)
+            res.T_icp, res.icp_fitness, res.icp_rmse, res.icp_iters = r.T32, r.fitness, r.rmse, r.iters
+            res.icp_wfitness = r.wfitness
+            res.icp_scale = r.scale
+            res.icp_mrmse = r.mrmse
+            res.cd_icp = B.chamfer_1dir(xyz0, off0, xyz1, off1, pairs, pairs, r.T32)
+        return res
+
+    if registration == "ppf":
+        # ---- 4'. point-pair-feature voting on the geometry itself (DESIGN 28): no descriptors, no correspondence lists ----
+        side, dist_step, ref_step, n_cand, view_points = ppf
+        clouds, offs, given = (xyz0, xyz1), (off0, off1), (normals0, normals1)
+        nrm = []
+        for c in (side, 1 - side):                       # the scene, then the model
+            v = given[c]
+            if v is None:
+                v = B.estimate_normals(clouds[c], offs[c], icp_normal_k, icp_normal_radius)
+                towards = view_points if c == side else None
+                B.orient_normals(clouds[c], offs[c], v, towards, towards is None)
+            nrm.append(v)
+        steps = PPF.default_dist_step(clouds[1 - side], offs[1 - side]) if dist_step is None else dist_step
+        r = PPF.ppf_batch(clouds[side], nrm[0], offs[side], clouds[1 - side], nrm[1], offs[1 - side], list(range(P)),
+                          list(range(P)), steps, max_corr, ref_step, n_cand)
+        T = (r.T if side == 0 else r.T_inv).to(torch.float32).reshape(P, 4, 4)
+        return finish(T, r.count.contiguous(), r.votes.contiguous(), list(range(P)), [None] * P, np.zeros(P, dtype=bool), None)
 
     # ---- 1. vanilla correspondences (find_kcorr, utils/eval_pose.py:48-79) -----------------
     # A CAD cloud with fewer than k voxels has no k-th neighbour: SciPy's KD-tree returns the out-of-range index n
@@ -375,48 +441,7 @@ def _sym_pose_batch(estimator, baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_
             t.record_stream(cur)
         T, inl, rmse, iters = (torch.cat([a] + [q[i] for q in parts]) for i, a in enumerate(first))
 
-    # ---- 5. Chamfer of every estimate (utils/preprocess.py:39-48,67-70) -----------------------------
-    cd = B.chamfer_1dir(xyz0, off0, xyz1, off1, prob_pair, prob_pair, T)
-
-    # ---- 6. best hypothesis per pair: first minimum, vanilla first (utils/symmetry.py:322-324) ----
-    if nonfinite is not None:
-        cd_h, bad_q, bad_c = to_host(cd, *nonfinite)   # (every launch above has finished, the helper's RANSAC included)
-        _refuse_nonfinite(bad_q, bad_c)
-    else:
-        cd_h = to_host(cd)[0]
-    pair_h = np.asarray(prob_pair)
-    best = np.arange(P)
-    for j in range(P, len(pair_h)):
-        p = pair_h[j]
-        if cd_h[best[p]] > cd_h[j]:
-            best[p] = j
-    best_t = torch.from_numpy(best).to(dev)
-    res = SymPoseResult(T_best=T[best_t], cd_best=cd[best_t], T_ransac=T[:P], cd_ransac=cd[:P],
-                        ok=ok, iters=iters, n_problems=len(prob_pair), T_all=T, cd_all=cd, inliers=inl,
-                        prob_pair=prob_pair, prob_cfg=prob_cfg, best=best)
-
-    # ---- 7. optional refinement of the kept estimate on the geometry itself (Open3D: registration_icp) ----
-    if icp_max_iter > 0:
-        pairs = list(range(P))
-        nrm = None
-        if icp_estimation in ("plane", "gicp"):
-            nrm = normals1 if normals1 is not None else B.estimate_normals(xyz1, off1, icp_normal_k, icp_normal_radius)
-        scaling = {}
-        if icp_with_scaling:
-            scaling = {"with_scaling": True}
-            if icp_scale_bounds is not None:
-                scaling["scale_bounds"] = icp_scale_bounds
-        if icp_estimation == "gicp":     # the query voxels' normals, in the query's own (posed) frame
-            snrm = normals0 if normals0 is not None else B.estimate_normals(xyz0, off0, icp_normal_k, icp_normal_radius)
-            scaling = {"estimation": "gicp", "src_normals": snrm, "gicp_epsilon": gicp_epsilon}
-        r = B.icp_batch(xyz0, off0, xyz1, off1, pairs, pairs, res.T_best, icp_max_dist, icp_max_iter, tgt_normals=nrm,
-                        kernel=icp_kernel, kernel_scale=icp_kernel_scale, **scaling)
-        res.T_icp, res.icp_fitness, res.icp_rmse, res.icp_iters = r.T32, r.fitness, r.rmse, r.iters
-        res.icp_wfitness = r.wfitness
-        res.icp_scale = r.scale
-        res.icp_mrmse = r.mrmse
-        res.cd_icp = B.chamfer_1dir(xyz0, off0, xyz1, off1, pairs, pairs, r.T32)
-    return res
+    return finish(T, inl, iters, prob_pair, prob_cfg, ok, nonfinite)
 
 
 def check_fm_options(ransac_n, edge_similarity, mutual, iterations, who="sym_pose_batch"):
@@ -446,6 +471,28 @@ def check_sc2_options(compat_dist, seeds, k, max_corr, who="sym_pose_batch"):
     if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 2 <= k <= 64:
         raise ValueError("%s: sc2_k must be an integer in [2, 64], got %r" % (who, k))
     return float(compat_dist), int(seeds), int(k)
+
+
+def check_ppf_options(scene_side, dist_step, ref_step, n_cand, who="sym_pose_batch"):
+    """The ppf_* options of registration = "ppf" as (scene_side, dist_step, ref_step, n_cand), or ValueError.  dist_step None
+    = 0.05 of each model's bounding-box diagonal (untuned)."""
+    if isinstance(scene_side, bool) or scene_side not in (0, 1):
+        raise ValueError("%s: ppf_scene_side must be 0 or 1, got %r" % (who, scene_side))
+    steps = dist_step if isinstance(dist_step, (list, tuple, np.ndarray)) else [dist_step]      # one per pair, or one for all
+    for v in steps:
+        if v is not None and (isinstance(v, bool) or not isinstance(v, (int, float, np.floating)) or
+                              not 0.0 < v < float("inf")):
+            raise ValueError("%s: ppf_dist_step must be positive and finite (None = 0.05 of the model's diagonal), got %r"
+                             % (who, dist_step))
+    if isinstance(ref_step, bool) or not isinstance(ref_step, (int, np.integer)) or not 1 <= ref_step < 2 ** 31:
+        raise ValueError("%s: ppf_ref_step must be an integer in [1, 2^31), got %r" % (who, ref_step))
+    if isinstance(n_cand, bool) or not isinstance(n_cand, (int, np.integer)) or not 1 <= n_cand <= 64:
+        raise ValueError("%s: ppf_n_cand must be an integer in [1, 64], got %r" % (who, n_cand))
+    if steps is not dist_step:
+        dist_step = None if dist_step is None else float(dist_step)
+    else:
+        dist_step = [float(v) for v in steps]
+    return int(scene_side), dist_step, int(ref_step), int(n_cand)
 
 
 def sym_pose_batch(*args, registration="ransac", fgr_mu_floor=0.025, fgr_iterations=64, fgr_tuple_test=True, **kwargs):
@@ -506,9 +553,24 @@ def sym_pose_batch(*args, registration="ransac", fgr_mu_floor=0.025, fgr_iterati
     and stages 5 - 7 are what they are for the RANSAC.  sc2_compat_dist = None (half of max_corr), sc2_seeds = 1024 and
     sc2_k = 20 are UNTUNED, no real scan measured; keyword-only, taken out of **kwargs here.  A list of more than 32 768
     correspondences is refused by the library (a smaller k_nn).  max_iter, confidence and seed are unused.  With "ransac",
-    "fgr" and "ransac_fm" nothing of it is launched."""
-    if registration not in ("ransac", "fgr", "ransac_fm", "sc2"):
-        raise ValueError("sym_pose_batch: registration must be 'ransac', 'fgr', 'ransac_fm' or 'sc2', got %r"
+    "fgr" and "ransac_fm" nothing of it is launched.
+    registration = "ppf": point-pair-feature voting, which reads NO descriptors: baseF and posF may be None,
+    stages 1 - 3 are skipped and use_symmetry=True is refused.  Stage 4 is ONE cs_ppf_batch call (ppf.ppf_batch) on the
+    voxels and their ORIENTED normals: the scene is side ppf_scene_side (0 = the query, 1 = the CAD side) and the model the
+    other one; normals0 / normals1 are used as they are when given (normals0 is accepted for this estimator with any
+    icp_estimation), else they come from estimate_normals (icp_normal_k, icp_normal_radius) and orient_normals -- the scene
+    towards ppf_view_points f64 [P,3] (the camera of a depth view) when given, else away from its centroid; the model away
+    from its centroid.  ppf_dist_step = None: 0.05 of every model's bounding-box diagonal (one small download), else one
+    positive number for all pairs or a list of one per pair; every
+    ppf_ref_step-th scene row is a reference, the ppf_n_cand references with the most votes are verified within max_corr.
+    T_ransac is the pose in this function's direction, xyz0 -> xyz1: the scene -> model pose when the scene is side 0, the
+    inverse the library forms when it is side 1; inliers = the verification count, iters = the votes of the winner's peak.
+    Stages 5 - 7 are what they are for the RANSAC.  ppf_scene_side = 0, ppf_dist_step = None, ppf_ref_step = 5, ppf_n_cand =
+    16 are UNTUNED, no real scan measured; keyword-only, taken out of **kwargs here.  A model above 4 096 rows or a scene above
+    16 384 is refused by the library (a coarser voxel).  k_nn, max_iter, confidence and seed are unused.  With the four other
+    estimators nothing of it is launched."""
+    if registration not in ("ransac", "fgr", "ransac_fm", "sc2", "ppf"):
+        raise ValueError("sym_pose_batch: registration must be 'ransac', 'fgr', 'ransac_fm', 'sc2' or 'ppf', got %r"
                          % (registration,))
     normals0, gicp_epsilon = kwargs.pop("normals0", None), kwargs.pop("gicp_epsilon", 1e-3)
     fm = check_fm_options(kwargs.pop("fm_ransac_n", 3), kwargs.pop("fm_edge_similarity", 0.9), kwargs.pop("fm_mutual", True),
@@ -516,7 +578,9 @@ def sym_pose_batch(*args, registration="ransac", fgr_mu_floor=0.025, fgr_iterati
     max_corr = kwargs["max_corr"] if "max_corr" in kwargs else (args[8] if len(args) > 8 else 0.20)
     sc2 = check_sc2_options(kwargs.pop("sc2_compat_dist", None), kwargs.pop("sc2_seeds", 1024), kwargs.pop("sc2_k", 20),
                             max_corr)
-    return _sym_pose_batch((registration, fgr_mu_floor, fgr_iterations, fgr_tuple_test, normals0, gicp_epsilon, fm, sc2),
+    ppf = check_ppf_options(kwargs.pop("ppf_scene_side", 0), kwargs.pop("ppf_dist_step", None), kwargs.pop("ppf_ref_step", 5),
+                            kwargs.pop("ppf_n_cand", 16)) + (kwargs.pop("ppf_view_points", None),)
+    return _sym_pose_batch((registration, fgr_mu_floor, fgr_iterations, fgr_tuple_test, normals0, gicp_epsilon, fm, sc2, ppf),
                            *args, **kwargs)
 
 

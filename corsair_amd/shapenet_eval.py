@@ -70,6 +70,13 @@ class Config:
     sc2_compat_dist: float = 1.0
     sc2_seeds: int = 1024
     sc2_k: int = 20
+    # "ppf" (DESIGN 28): point-pair-feature voting (cs_ppf_batch) on the voxels and their oriented normals -- no descriptors
+    # are computed and no checkpoint is needed.  The scene is the posed copy (oriented towards its camera under partial_view,
+    # else away from its centroid), the model the whole cloud.  ppf_dist_step is a FRACTION of the model's bounding-box
+    # diagonal.  Every default is UNTUNED, no real scan measured.  The symmetry hypotheses are off under it.
+    ppf_ref_step: int = 5
+    ppf_n_cand: int = 16
+    ppf_dist_step: float = 0.05
     # the descriptors: "network" (the ResUNet forward, needs a checkpoint) or "fpfh" (registration.fpfh_features: no weights;
     # sym_pose_batch then runs with use_symmetry=False, the part cut takes the network's widths only).  fpfh_radius is in
     # VOXELS, 5 is Open3D's example value, UNTUNED; fpfh_max_nn is cs_fpfh's max_nn
@@ -105,8 +112,10 @@ class Config:
             raise ValueError("Config.view_depth_tol must be finite and > 0 voxels, got %r" % (self.view_depth_tol,))
 
     def check_registration(self):
-        if self.registration not in ("ransac", "fgr", "ransac_fm", "sc2"):
-            raise ValueError("Config.registration must be 'ransac', 'fgr', 'ransac_fm' or 'sc2', got %r" % (self.registration,))
+        if self.registration not in ("ransac", "fgr", "ransac_fm", "sc2", "ppf"):
+            raise ValueError("Config.registration must be 'ransac', 'fgr', 'ransac_fm', 'sc2' or 'ppf', got %r"
+                             % (self.registration,))
+        R.check_ppf_options(1, self.ppf_dist_step, self.ppf_ref_step, self.ppf_n_cand, "Config")
         R.check_fm_options(self.fm_ransac_n, self.fm_edge_similarity, self.fm_mutual, self.fm_iterations, "Config")
         if isinstance(self.sc2_compat_dist, bool) or not isinstance(self.sc2_compat_dist, (int, float, np.floating)):
             raise ValueError("Config.sc2_compat_dist must be positive and finite (voxels), got %r" % (self.sc2_compat_dist,))
@@ -147,6 +156,26 @@ class FpfhPipe:
         F, normal = R.fpfh_features(origin, out_off, self.radius_voxels * voxel_size, self.max_nn)
         return EmbeddedSet(F, origin, out_off, torch.zeros((len(out_off) - 1, 0), dtype=torch.float32, device=origin.device),
                            normal)
+
+
+class PpfPipe:
+    """Stands where FpfhPipe stands when Config.registration = "ppf": voxelisation only.  The descriptors are an [n, 0]
+    array that nothing reads; sym_pose_batch estimates and orients the normals itself (it knows the cameras)."""
+
+    def __init__(self, device="cuda"):
+        self.device = torch.device(device)
+
+    def embed_groups(self, groups, voxel_size):
+        from .harness import EmbeddedSet
+
+        origins, out_off = [], [0]
+        for xyz, offsets in groups:
+            keep, _, off = B.voxelize(xyz, offsets, voxel_size)
+            origins.append(xyz[keep].to(torch.float32))
+            out_off += [out_off[-1] + int(o) for o in off[1:]]
+        origin = torch.cat(origins).contiguous()
+        none = torch.zeros((origin.shape[0], 0), dtype=torch.float32, device=origin.device)
+        return EmbeddedSet(none, origin, out_off, torch.zeros((len(out_off) - 1, 0), dtype=torch.float32, device=origin.device))
 
 
 def load_pc(pc):
@@ -229,6 +258,21 @@ def partial_views(xyz, offsets, host, cfg, seed, first_job):
     return xyz[idx], off, share, len(skipped)
 
 
+def partial_views_with_cameras(xyz, offsets, host, cfg, seed, first_job):
+    """partial_views, and as a fifth value the eye of each cloud's camera in world coordinates, f64 [P,3] (the view points
+    registration = "ppf" orients the scene's normals towards): the same boxes, directions and views.view_cameras call."""
+    from . import views as V
+
+    out = partial_views(xyz, offsets, host, cfg, seed, first_job)
+    P = len(offsets) - 1
+    h32 = [np.asarray(h, np.float32) for h in host]
+    lo, hi = np.stack([h.min(0) for h in h32]), np.stack([h.max(0) for h in h32])
+    dirs = np.stack([view_direction(seed, first_job + i) for i in range(P)])
+    Rt = V.view_cameras(lo, hi, dirs, cfg.view_distance).reshape(P, 3, 4)
+    eyes = -np.einsum("pba,pb->pa", Rt[:, :, :3], Rt[:, :, 3])          # the world -> camera map is R | t: the eye is -R^T t
+    return out + (eyes,)
+
+
 def chamfer_max(pc0, pc1):
     """Two-sided Hausdorff distance (evaluation-shapenet.py:122-135), two cs_hausdorff_1dir problems."""
     dev = torch.device("cuda")
@@ -300,9 +344,12 @@ def evaluate(pipe, clouds, cfg=None, pairs_per_batch=16, seed=None, force_gate=F
                  fm_iterations=cfg.fm_iterations) if fm_on else {}
     if cfg.registration == "sc2":
         fm_kw = dict(sc2_compat_dist=cfg.sc2_compat_dist * cfg.voxel_size, sc2_seeds=cfg.sc2_seeds, sc2_k=cfg.sc2_k)
-    fpfh_on = cfg.features == "fpfh"
+    ppf_on = cfg.registration == "ppf"          # no descriptors and no symmetry hypotheses under it
+    fpfh_on = cfg.features == "fpfh" and not ppf_on
     if fpfh_on:
         pipe = FpfhPipe("cuda" if pipe is None else pipe.device, cfg.fpfh_radius, cfg.fpfh_max_nn)
+    if ppf_on:
+        pipe = PpfPipe("cuda" if pipe is None else pipe.device)
     icp_on = cfg.icp_max_iter > 0
     scale_on = bool(cfg.icp_with_scaling)
     if scale_on and not icp_on:
@@ -326,7 +373,8 @@ def evaluate(pipe, clouds, cfg=None, pairs_per_batch=16, seed=None, force_gate=F
             offsets = np.concatenate([[0], np.cumsum([len(j[col]) for j in chunk])]).tolist()
             if col == 3 and cfg.partial_view:
                 rows_in = offsets[-1]
-                xyz, offsets, shares, skipped = partial_views(xyz, offsets, [j[col] for j in chunk], cfg, view_seed, s)
+                xyz, offsets, shares, skipped, eyes = partial_views_with_cameras(xyz, offsets, [j[col] for j in chunk], cfg,
+                                                                                 view_seed, s)
                 view_stat["clouds"] += len(chunk)
                 view_stat["rows_in"] += int(rows_in)
                 view_stat["rows_visible"] += int(offsets[-1])
@@ -337,10 +385,16 @@ def evaluate(pipe, clouds, cfg=None, pairs_per_batch=16, seed=None, force_gate=F
         base = es.gather(list(range(P)))
         posed = es.gather(list(range(P, 2 * P)))
         labels = [j[5] for j in chunk]
+        if ppf_on:      # the scene is the posed copy (side 1); the step is a fraction of each model's diagonal
+            from . import ppf as PPF
+
+            fm_kw = dict(ppf_scene_side=1, ppf_ref_step=cfg.ppf_ref_step, ppf_n_cand=cfg.ppf_n_cand,
+                         ppf_dist_step=PPF.default_dist_step(base.origin, base.offsets, cfg.ppf_dist_step),
+                         ppf_view_points=eyes if cfg.partial_view else None)
         res = R.sym_pose_batch(base.F, base.origin, base.offsets, posed.F, posed.origin, posed.offsets,
                                labels, cfg.k_nn, cfg.max_corr, 0,
                                [(2 * (s + i), 2 * (s + i) + 1) for i in range(P)], 100,
-                               cfg.ransac_max_iter, cfg.ransac_confidence, not fpfh_on and not fm_on, force_gate, None,
+                               cfg.ransac_max_iter, cfg.ransac_confidence, not fpfh_on and not fm_on and not ppf_on, force_gate, None,
                                cfg.icp_max_iter, cfg.icp_distance() if icp_on else None, cfg.icp_estimation,
                                cfg.icp_normal_k, None, cfg.normal_radius(), icp_with_scaling=scale_on,
                                icp_scale_bounds=tuple(cfg.icp_scale_bounds) if scale_on else None,
@@ -506,10 +560,12 @@ def build_parser():
                     help="the ICP refinement also fits an isotropic scale (needs --icp-iters > 0, no robust kernel)")
     ap.add_argument("--icp-scale-min", type=float, default=0.5, help="lower bound of the fitted scale, in (0, 1] (untuned)")
     ap.add_argument("--icp-scale-max", type=float, default=2.0, help="upper bound of the fitted scale, >= 1 (untuned)")
-    ap.add_argument("--registration", default="ransac", choices=["ransac", "fgr", "ransac_fm", "sc2"],
+    ap.add_argument("--registration", default="ransac", choices=["ransac", "fgr", "ransac_fm", "sc2", "ppf"],
                     help="correspondence estimator: the reference's RANSAC, Fast Global Registration (cs_fgr_batch), "
                          "feature-matching RANSAC with a mutual filter and pose checkers (cs_ransac_fm_batch; no symmetry "
-                         "hypotheses), or the compatibility-graph estimator for low inlier shares (cs_sc2_batch)")
+                         "hypotheses), the compatibility-graph estimator for low inlier shares (cs_sc2_batch), or "
+                         "point-pair-feature voting on the voxels and their normals (cs_ppf_batch; no descriptors, no "
+                         "--ckpt, no symmetry hypotheses)")
     ap.add_argument("--fgr-mu-floor", type=float, default=0.025,
                     help="floor of FGR's mu, in units of the clouds' radius (Open3D's default, untuned)")
     ap.add_argument("--fm-ransac-n", type=int, default=3, choices=[3, 4],
@@ -529,6 +585,14 @@ def build_parser():
     ap.add_argument("--sc2-k", type=int, default=20,
                     help="correspondences a seed of sc2 is fitted over beside itself, in [2, 64] (untuned, no real scan "
                          "measured)")
+    ap.add_argument("--ppf-ref-step", type=int, default=5,
+                    help="every n-th row of the posed copy is a reference of --registration ppf (untuned, no real scan "
+                         "measured)")
+    ap.add_argument("--ppf-n-cand", type=int, default=16,
+                    help="references with the most votes that ppf verifies, in [1, 64] (untuned, no real scan measured)")
+    ap.add_argument("--ppf-dist-step", type=float, default=0.05,
+                    help="distance step of ppf as a fraction of the model's bounding-box diagonal (Drost et al.'s sampling; "
+                         "untuned, no real scan measured)")
     ap.add_argument("--partial-view", action="store_true",
                     help="reduce the posed copy of every pair to what one virtual depth camera sees of it (cs_render_views; "
                          "the model stays whole)")
@@ -565,7 +629,7 @@ def main(argv=None):
     if 0 < a.n_models < len(files):                                   # evaluation-shapenet.py:200-203
         files = sorted(rng.choice(files, a.n_models, replace=False).tolist())
     clouds = [np.load(os.path.join(a.data_dir, f)) for f in files]
-    if a.features == "fpfh":
+    if a.features == "fpfh" or a.registration == "ppf":
         pipe = None
     else:
         if not a.ckpt:
@@ -582,6 +646,7 @@ def main(argv=None):
                  fpfh_radius=a.fpfh_radius, fpfh_max_nn=a.fpfh_max_nn, fm_ransac_n=a.fm_ransac_n,
                  fm_edge_similarity=a.fm_edge_similarity, fm_mutual=not a.fm_no_mutual, fm_iterations=a.fm_iterations,
                  sc2_compat_dist=a.sc2_compat_dist, sc2_seeds=a.sc2_seeds, sc2_k=a.sc2_k,
+                 ppf_ref_step=a.ppf_ref_step, ppf_n_cand=a.ppf_n_cand, ppf_dist_step=a.ppf_dist_step,
                  partial_view=a.partial_view, view_fov_deg=a.view_fov, view_size=a.view_size, view_distance=a.view_distance,
                  view_point_size=a.view_point_size, view_depth_tol=a.view_depth_tol)
     cfg.check_partial_view()

@@ -1362,6 +1362,103 @@ int cs_sc2_batch(const float* d_src, const float* d_tgt, const int64_t* h_off, c
                  double* d_rmse, uint8_t* d_inlier, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Point-pair-feature voting: a pose of a scene against a model from oriented points alone, with no descriptor
+ * and no correspondence list (Drost, Ulrich, Navab and Ilic, CVPR 2010, as remembered from the paper; the list of
+ * differences is at the end).  The reference has no such step, so this comment is the specification and tests/ppf_ref.py
+ * restates it bit for bit.  Every operation is ONE IEEE f64 operation in the order the parentheses give; an fma appears only
+ * where fma( is written (step h); nothing is contracted; only + - * / sqrt fma, casts and comparisons appear; a comparison
+ * with a NaN is false.  Everything is enqueued on `stream`; scratch comes from the calling thread's pool; no host wait, no
+ * cooperative launch, no flag a thread waits on; the only atomics are integer; every loop is bounded by an argument or a
+ * segment's rows.  Profile family "ppf", one scope per call.
+ *
+ * cs_ppf_batch: d_scene, d_scene_normal f32 [rows,3] with host offsets h_soff; d_model, d_model_normal f32 [rows,3] with host
+ *   offsets h_moff; problem p < n_prob pairs scene segment h_scene_seg[p] with model segment h_model_seg[p], selected as in
+ *   cs_icp_batch; segments may be shared between problems.  h_dist_step f64 [n_prob] on the host: one distance step per
+ *   problem; max_dist: the verification radius; ref_step >= 1; n_cand in [1, 64].  Outputs, all on the device: d_T, d_Tinv
+ *   f64 [n_prob,4,4]; d_stat int32 [n_prob,8]; d_rmse f64 [n_prob]; d_cand_T f64 [n_prob,n_cand,4,4]; d_cand_stat int32
+ *   [n_prob,n_cand,4].  Normals must be ORIENTED (cs_orient_normals); they need not be unit vectors.
+ *   Row: x = the coordinates and N = the normal, widened to f64.  nn = sqrt((N_0 * N_0 + N_1 * N_1) + N_2 * N_2).  The row is
+ *     VALID when its six values are finite and nn > 0; then u = (N_0 / nn, N_1 / nn, N_2 / nn).  An invalid row is no
+ *     reference, takes part in no pair and stands in no table; step h counts it when its coordinates are finite.
+ *   b. Local frame of a valid row: the rotation that takes u to +x, I + [v]x + [v]x^2 / (1 + c) with v = u cross x and
+ *      c = u_0, written out: k = 1.0 + u_0; when k >= 2^-20, with w = (u_1 * u_2) / k:
+ *        row0 = (u_0, u_1, u_2),  row1 = (-u_1, 1.0 - (u_1 * u_1) / k, -w),  row2 = (-u_2, -w, 1.0 - (u_2 * u_2) / k);
+ *      otherwise (u within 1.4e-3 rad of -x) the half turn about y: row0 = (-1, 0, 0), row1 = (0, 1, 0), row2 = (0, 0, -1).
+ *      The frame of the row is p -> R (p - x).
+ *   a. Feature of the ordered pair (i, j), i != j, of two valid rows of ONE segment: d = x_j - x_i (three subtractions),
+ *      len = sqrt((d_0 * d_0 + d_1 * d_1) + d_2 * d_2), q = len / dist_step, dot(a, b) = (a_0 * b_0 + a_1 * b_1) + a_2 * b_2,
+ *        c1 = dot(u_i, d) / len,  c2 = dot(u_j, d) / len,  c3 = dot(u_i, u_j),
+ *        y = (float)dot(row1_i, d),  z = (float)dot(row2_i, d)      -- the in-plane direction of the pair, stored as f32.
+ *      The pair is SKIPPED when !(len > 0), when !(q < 64.0), or when y or z is not finite or both are zero (d parallel to
+ *      the normal: no in-plane direction).  dbin = (int)q.  An angle has 15 bins of 12 degrees: bin(c) = the number of
+ *      k in 1..14 with c <= C_k, C_k = cos(12 k degrees) -- an angle AT a boundary belongs to the bin above it, a cosine
+ *      beyond +-1 by a rounding goes to bin 0 or 14.  corsair_amd/csrc/ppf_bounds.h (tools/gen_ppf_bounds.py) tabulates C_k
+ *      as f64 literals and THOSE numbers are the specification.  key = ((dbin * 15 + bin(c1)) * 15 + bin(c2)) * 15 + bin(c3).
+ *   c. Model table of (model segment, dist_step): every ordered pair of the segment that is not skipped, as the entry
+ *      (m_r = i local to the segment, y, z), grouped by key.  A table is built once per chunk (below) for all the problems of
+ *      the chunk that share the segment and the step.  The order of the entries inside a key reaches no output.
+ *   d. Voting.  The references of a problem are the scene rows r (local to the segment) with r % ref_step == 0; n_ref of
+ *      them.  For a valid reference r and every scene row i != r whose pair (r, i) is not skipped, every entry (m_r, ym, zm)
+ *      of the table under the pair's key casts ONE vote, an integer increment of the cell m_r * 30 + bin.  With (ys, zs) of
+ *      the scene pair, all four f32 values widened:  px = ym * ys + zm * zs,  py = zm * ys - ym * zs  (the complex product of
+ *      the model direction and the conjugate of the scene direction; alpha = its angle, the turn about x that takes the
+ *      scene pair onto the model pair).  30 bins over [-pi, pi): bin = the number of boundaries theta_m = 2 pi (m - 15) / 30,
+ *      m = 1..29, not above alpha, found without a transcendental function: ppf_bounds.h tabulates (c_m, s_m) =
+ *      (cos theta_m, sin theta_m), t_m = c_m * py - s_m * px (no fma).  py < 0: the number of m in 1..14 with t_m >= 0; else
+ *      15 + the number of m in 16..29 with t_m >= 0.  DELIBERATE DIFFERENCE from atan2, as in cs_fpfh: py = -0 with px < 0
+ *      gives bin 29 like py = +0.
+ *   e. Peak of a reference: the maximum over its cells with votes > 0 of votes << 32 | ~cell (~: the 32-bit complement): the
+ *      most votes, ties to the SMALLEST cell.  An invalid reference and one without a vote have votes = 0.
+ *   f. Candidates of a problem: the min(n_cand, n_ref) references of the largest key votes << 32 | ~(r / ref_step), the
+ *      largest first (cs_sc2_batch's rank rule): candidate c has rank c.  A candidate with votes = 0 is INVALID.
+ *   g. Pose of a valid candidate (reference s with frame Rs, model row m with frame Rm, bin b): Tm^-1 Rx(alpha_b) Ts with
+ *      (ca, sa) = (cos alpha_b, sin alpha_b), alpha_b = 2 pi (b - 14.5) / 30 the centre of the bin, tabulated in ppf_bounds.h:
+ *        A_0k = Rs_0k,  A_1k = ca * Rs_1k - sa * Rs_2k,  A_2k = sa * Rs_1k + ca * Rs_2k,
+ *        R_ak = (Rm_0a * A_0k + Rm_1a * A_1k) + Rm_2a * A_2k,
+ *        t_a = x_m,a - ((R_a0 * x_s,0 + R_a1 * x_s,1) + R_a2 * x_s,2).      T = (R | t; 0 0 0 1) maps the SCENE onto the MODEL.
+ *   h. Verification of a valid candidate: for every scene row (x, y, z) of the segment with finite coordinates,
+ *        P_a = fma(R_a2, z, fma(R_a1, y, fma(R_a0, x, t_a)))   (the canonical chain of the posed source),
+ *        d2_j = fma(e_2, e_2, fma(e_1, e_1, e_0 * e_0)),  e = P - x_j,  over EVERY model row j (valid or not; a NaN or
+ *        infinite d2 is never the minimum), dmin = the smallest.  The row COUNTS when dmin < max_dist * max_dist (formed
+ *        once), strictly.  count = the rows that count; the squared error is the sum of (uint64)(dmin * 2^k) over them,
+ *        k = 61 - eM - ex, ns <= 2^eM, max_dist^2 = f 2^ex (cs_sc2_batch's fixed-point rule with the scene rows as m).
+ *   i. Winner: the valid candidate of the largest count << 32 | ~rank (ties to the smallest rank).
+ *      d_T = its T; d_Tinv = (R^T | ti), ti_a = -((R_0a * t_0 + R_1a * t_1) + R_2a * t_2), maps the model onto the scene;
+ *      d_stat = (1, votes, scene row, model row, alpha bin, count, rank, n_ref); d_rmse = sqrt((error * 2^-k) / count), 0 when
+ *      count = 0.  d_cand_T[c], d_cand_stat[c] = T and (votes, count, scene row, cell) of candidate c; the identity and
+ *      (0, 0, -1, -1) for an invalid candidate and for the slots behind min(n_cand, n_ref).
+ *      No valid candidate -- an empty or one-row scene or model, every row invalid, every pair skipped -- : found = 0,
+ *      d_T = d_Tinv = the identity, d_stat = (0, 0, -1, -1, -1, 0, -1, n_ref), d_rmse = 0.
+ *   Independence: the result of a problem is a function of its two segments and of dist_step, max_dist, ref_step and n_cand
+ *     alone.  Batch neighbours, the stream, the launch shape (CS_PPF_CHUNK_BYTES, CS_PPF_ACC) and the run do not reach it.  A
+ *     permutation of the rows permutes the tables and the votes with it; it enters the result through the ~ tie keys and
+ *     through which rows are references only.
+ *   n_prob = 0 and empty segments are legal.  Refused (CS_ERR_INVALID): a negative problem count, a NULL host table, a
+ *     negative segment id, offsets that decrease or are negative, a dist_step or max_dist not positive and finite,
+ *     ref_step < 1, a NULL output with n_prob > 0, a NULL array while a row exists; (CS_ERR_UNSUPPORTED): n_cand outside
+ *     [1, 64], a model segment of more than 4 096 rows (its table of all ordered pairs is 192 MiB; the message advises a
+ *     coarser voxel), a scene segment of more than 16 384 rows.  The checks come before any device work.
+ *   Memory: a table takes 12 B per ordered pair and 8 B x 216 001 keys.  The accumulator of a reference, model rows x 30 u32
+ *     counters, lives in the LDS of its workgroup when the model has at most 1 360 rows (163 200 B of the 160 KiB of a CU) and
+ *     in one of 256 zeroed global slabs otherwise; CS_PPF_ACC=global (read per call) sends every problem to the slabs,
+ *     CS_PPF_ACC=lds names the default.  The same bits on both paths: both add integers.  A call whose tables and slabs
+ *     exceed CS_PPF_CHUNK_BYTES (read per call, default 512 MiB; every problem is counted with a table of its own) runs in
+ *     chunks of whole consecutive problems, never fewer than one, with the same bits.  The checks, the accumulator rule and
+ *     the planner stand in corsair_amd/csrc/ppf_plan.h.
+ *   Differences from Drost et al., deliberate: NO pose clustering and NO averaging of the poses of a cluster -- the
+ *     candidates are the best references, each verified by an exhaustive nearest-row count, and the ICP stage follows; the
+ *     model is NOT subsampled here (the caller's voxel size does that) and the table holds ALL m^2 pairs; every n-th row is
+ *     a reference instead of a random fifth; alpha is binned from the pair of directions at vote time instead of being
+ *     stored as an angle.  The raw pose carries the 12 degree resolution of alpha: up to 6 degrees about the normal.
+ *   Limits: a flipped normal (a concave part oriented away from the centroid) changes the feature and loses the
+ *     votes of its pairs; a symmetric model has several equal peaks and the tie rule picks one; the table grows with m^2.
+ * ---------------------------------------------------------------------------------------- */
+int cs_ppf_batch(const float* d_scene, const float* d_scene_normal, const int64_t* h_soff, const float* d_model,
+                 const float* d_model_normal, const int64_t* h_moff, const int32_t* h_scene_seg, const int32_t* h_model_seg,
+                 int n_prob, const double* h_dist_step, double max_dist, int ref_step, int n_cand, double* d_T, double* d_Tinv,
+                 int32_t* d_stat, double* d_rmse, double* d_cand_T, int32_t* d_cand_stat, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Partial views: a virtual depth camera per segment -- hidden-point removal by a splat z-buffer.  The reference
  * has no such step, so this comment is the specification and tests/view_ref.py restates it bit for bit.  As in the blocks
  * above: every operation is ONE IEEE f64 operation in the order given, or an explicit fma; nothing is contracted; only
@@ -1421,7 +1518,7 @@ int cs_render_views(const float* d_xyz, const int64_t* h_off, int n_seg, const d
  * kernel family with hipEvents on the launch stream and accumulates the elapsed time.
  * names: "conv", "ransac_eval", "ransac_pre", "ransac_hyp", "knn", "chamfer", "topk", "symcut",
  * "kmap", "loss", "hardneg", "icp", "normals", "fgr", "chamfer2", "fpfh", "orient", "outlier", "cluster", "plane",
- * "featmatch", "view", "sc2".
+ * "featmatch", "view", "sc2", "ppf".
  * ---------------------------------------------------------------------------------------- */
 void cs_prof_enable(int on);
 void cs_prof_reset(void);
