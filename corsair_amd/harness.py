@@ -22,6 +22,7 @@ import torch
 
 from . import backend as B
 from . import engine as E
+from . import estimators
 from . import registration as R
 from .utils.eval_pose import eval_pose
 
@@ -181,17 +182,12 @@ class Config:
         return self.icp_kernel_scale if self.icp_kernel_scale > 0 else 1.0 * self.voxel_size
 
     def check_icp(self):
-        if self.registration == "ransac_fm":
-            raise ValueError("Config.registration 'ransac_fm' (feature-matching RANSAC, DESIGN 25) is not wired into the harness, "
-                             "the sharded evaluation or the cache format: use registration.sym_pose_batch or shapenet_eval")
-        if self.registration == "sc2":
-            raise ValueError("Config.registration 'sc2' (the compatibility-graph estimator, DESIGN 27) is not wired into the harness, "
-                             "the sharded evaluation or the cache format: use registration.sym_pose_batch or shapenet_eval")
-        if self.registration == "ppf":
-            raise ValueError("Config.registration 'ppf' (point-pair-feature voting, DESIGN 28) is not wired into the harness, "
-                             "the sharded evaluation or the cache format: use registration.sym_pose_batch or shapenet_eval")
-        if self.registration not in ("ransac", "fgr"):
-            raise ValueError("Config.registration must be 'ransac' or 'fgr', got %r" % (self.registration,))
+        for e in estimators.TABLE:
+            if not e.wired and self.registration == e.name:
+                raise ValueError("Config.registration %r (%s, DESIGN %d) is not wired into the harness, the sharded evaluation "
+                                 "or the cache format: use registration.sym_pose_batch or shapenet_eval"
+                                 % (e.name, e.what, e.design))
+        estimators.lookup(self.registration, "Config.registration", estimators.WIRED)
         if not (0.0 < float(self.fgr_mu_floor) < float("inf")):
             raise ValueError("Config.fgr_mu_floor must be positive and finite, got %r" % (self.fgr_mu_floor,))
         if self.icp_estimation not in ("point", "plane", "gicp"):
@@ -992,7 +988,7 @@ def build_parser():
                     help="lower bound of the scale the ICP may add, in (0, 1] (an untuned default)")
     ap.add_argument("--icp-scale-max", type=float, default=2.0,
                     help="upper bound of the scale the ICP may add, >= 1 (an untuned default)")
-    ap.add_argument("--registration", default="ransac", choices=["ransac", "fgr"],
+    ap.add_argument("--registration", default="ransac", choices=list(estimators.WIRED),
                     help="correspondence estimator: the reference's RANSAC, or Fast Global Registration (cs_fgr_batch)")
     ap.add_argument("--fgr-mu-floor", type=float, default=0.025,
                     help="floor of FGR's mu, in units of the clouds' radius (Open3D's default, untuned)")

@@ -22,17 +22,19 @@ from __future__ import annotations
 
 import inspect
 import os
+from collections import namedtuple
 from dataclasses import dataclass
+from types import SimpleNamespace
 
 import numpy as np
 import torch
 
 from . import _helper
 from . import backend as B
+from . import estimators as E
 from . import featmatch as FM
-from . import ppf as PPF
-from . import sc2 as S2
 from ._lib import to_host
+from .estimators import check_fm_options, check_ppf_options, check_sc2_options  # noqa: F401  (their callers find them here)
 
 ANCHOR_KEY = 0x5A11C0DE
 
@@ -167,24 +169,26 @@ def _refuse_nonfinite(bad_query, bad_cad):
                              "reference's KD-tree refuses them: %s)" % (side, int(hit[0]), said))
 
 
+# What sym_pose_batch takes by keyword only, as it hands it to its body: the entry of estimators.TABLE, every estimator's options
+# by keyword (as given or the table's default, unchecked), and the two ICP options that ride along
+_KeywordOnly = namedtuple("_KeywordOnly", "entry options normals0 gicp_epsilon")
+
+
 def _sym_pose_batch(estimator, baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_nn=5, max_corr=0.20, seed=0,
                     anchor_ids=None, n_anchor=100, max_iter=100000, confidence=0.999,
                     use_symmetry=True, force_gate=False, query_anchors=None, icp_max_iter=0, icp_max_dist=None,
                     icp_estimation="point", icp_normal_k=16, normals1=None, icp_normal_radius=None, icp_with_scaling=False,
                     icp_scale_bounds=None, icp_kernel="l2", icp_kernel_scale=None):
-    """The body of sym_pose_batch (below, with the documentation).  estimator = (registration, fgr_mu_floor,
-    fgr_iterations, fgr_tuple_test, normals0, gicp_epsilon, fm, sc2, ppf), the keyword-only options; the first four, fm =
-    (fm_ransac_n, fm_edge_similarity, fm_mutual, fm_iterations), sc2 = (sc2_compat_dist, sc2_seeds, sc2_k) and ppf =
-    (scene_side, dist_step, ref_step, n_cand, view_points) already checked."""
-    registration, fgr_mu_floor, fgr_iterations, fgr_tuple_test, normals0, gicp_epsilon, fm, sc2, ppf = estimator
-    if registration == "ppf" and use_symmetry:
-        raise ValueError("sym_pose_batch: registration 'ppf' needs use_symmetry=False (symmetry hypotheses are out of scope)")
-    if registration == "ransac_fm" and use_symmetry:
-        raise ValueError("sym_pose_batch: registration 'ransac_fm' needs use_symmetry=False (the part configurations are out "
-                         "of scope)")
+    """The body of sym_pose_batch (below, with the documentation).  estimator: the call's _KeywordOnly."""
+    entry, normals0, gicp_epsilon = estimator.entry, estimator.normals0, estimator.gicp_epsilon
+    # the options of every estimator are checked, the chosen one's kept by keyword; here, where max_corr is a parameter
+    # (sc2_compat_dist = None is half of it)
+    o = E.checked_options(entry, estimator.options, max_corr)
+    if entry.no_symmetry and use_symmetry:
+        raise ValueError("sym_pose_batch: registration %r needs use_symmetry=False (%s)" % (entry.name, entry.no_symmetry))
     if icp_estimation == "gicp" and (icp_with_scaling or icp_kernel != "l2"):
         raise ValueError("sym_pose_batch: icp_estimation 'gicp' with icp_with_scaling or a robust icp_kernel is out of scope")
-    if icp_estimation != "gicp" and normals0 is not None and registration != "ppf":
+    if icp_estimation != "gicp" and normals0 is not None and entry.descriptors:
         raise ValueError("sym_pose_batch: normals0 is used by icp_estimation = 'gicp' only")
     if icp_with_scaling and icp_kernel != "l2":
         raise ValueError("sym_pose_batch: icp_with_scaling with a robust icp_kernel (%r) is out of scope" % (icp_kernel,))
@@ -204,13 +208,13 @@ def _sym_pose_batch(estimator, baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_
     if use_symmetry and baseF.shape[1] not in (16, 32):
         raise ValueError("sym_pose_batch: use_symmetry needs 16- or 32-wide descriptors (cs_symcut_fit), got %d columns; "
                          "FPFH descriptors (33) register with use_symmetry=False" % (baseF.shape[1],))
-    dev = xyz0.device if registration == "ppf" else baseF.device      # "ppf" reads no descriptors: they may be None
+    dev = baseF.device if entry.descriptors else xyz0.device      # descriptors that are not read may be None
     P = len(off0) - 1
     off0 = [int(v) for v in off0]
     off1 = [int(v) for v in off1]
     n0 = [off0[p + 1] - off0[p] for p in range(P)]
     n1 = [off1[p + 1] - off1[p] for p in range(P)]
-    k = 1 if registration == "ransac_fm" else k_nn      # the feature-matching recipe takes 1-NN matches; k_nn is not used
+    k = entry.k or k_nn      # the feature-matching recipe takes 1-NN matches; k_nn is not used
 
     def finish(T, inl, iters, prob_pair, prob_cfg, ok, nonfinite):
         """Stages 5 - 7, the same behind every estimator."""
@@ -257,23 +261,21 @@ def _sym_pose_batch(estimator, baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_
             res.cd_icp = B.chamfer_1dir(xyz0, off0, xyz1, off1, pairs, pairs, r.T32)
         return res
 
-    if registration == "ppf":
+    if not entry.descriptors:
         # ---- 4'. point-pair-feature voting on the geometry itself: no descriptors, no correspondence lists ----
-        side, dist_step, ref_step, n_cand, view_points = ppf
+        side = o["ppf_scene_side"]
         clouds, offs, given = (xyz0, xyz1), (off0, off1), (normals0, normals1)
         nrm = []
         for c in (side, 1 - side):                       # the scene, then the model
             v = given[c]
             if v is None:
                 v = B.estimate_normals(clouds[c], offs[c], icp_normal_k, icp_normal_radius)
-                towards = view_points if c == side else None
+                towards = o["ppf_view_points"] if c == side else None
                 B.orient_normals(clouds[c], offs[c], v, towards, towards is None)
             nrm.append(v)
-        steps = PPF.default_dist_step(clouds[1 - side], offs[1 - side]) if dist_step is None else dist_step
-        r = PPF.ppf_batch(clouds[side], nrm[0], offs[side], clouds[1 - side], nrm[1], offs[1 - side], list(range(P)),
-                          list(range(P)), steps, max_corr, ref_step, n_cand)
-        T = (r.T if side == 0 else r.T_inv).to(torch.float32).reshape(P, 4, 4)
-        return finish(T, r.count.contiguous(), r.votes.contiguous(), list(range(P)), [None] * P, np.zeros(P, dtype=bool), None)
+        T, inl, _, iters = E.run_stage4(entry, o, SimpleNamespace(
+            clouds=(clouds[side], clouds[1 - side]), normals=nrm, offs=(offs[side], offs[1 - side]), max_corr=max_corr))
+        return finish(T, inl, iters, list(range(P)), [None] * P, np.zeros(P, dtype=bool), None)
 
     # ---- 1. vanilla correspondences (find_kcorr, utils/eval_pose.py:48-79) -----------------
     # A CAD cloud with fewer than k voxels has no k-th neighbour: SciPy's KD-tree returns the out-of-range index n
@@ -300,11 +302,11 @@ def _sym_pose_batch(estimator, baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_
     # correspondence lists straight from the neighbour lists (one launch; rounds 1-2 built index tensors with
     # repeat_interleave / arange / gathers): pair p = query rows off0[p]:off0[p+1] against the CAD cloud at off1[p]
     fm_m = None
-    if registration == "ransac_fm":
+    if entry.name == "ransac_fm":
         # the backward 1-NN (the segments swap their roles), then the mutual filter with Open3D's fallback on the device:
         # pair p's correspondences fill the slots off0[p]... and their number stays on the device (fm_m)
-        nn_bwd = B.knn_feat(posF, off1, baseF, off0, 1) if fm[2] else None
-        v_src, v_tgt, fm_m, _ = FM.mutual_correspondences(nn, nn_bwd, xyz0, off0, xyz1, off1, fm[0], fm[2])
+        nn_bwd = B.knn_feat(posF, off1, baseF, off0, 1) if o["fm_mutual"] else None
+        v_src, v_tgt, fm_m, _ = FM.mutual_correspondences(nn, nn_bwd, xyz0, off0, xyz1, off1, o["fm_ransac_n"], o["fm_mutual"])
     else:
         desc_v = np.asarray([[off0[p], off0[p], off1[p], n0[p], off0[p]] for p in range(P)], dtype=np.int64).reshape(P, 5)
         v_src, v_tgt = B.corr_assemble(xyz0, xyz1, None, nn, desc_v, off0[-1], max(n0) if P else 0)
@@ -315,7 +317,7 @@ def _sym_pose_batch(estimator, baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_
     prob_cfg = [None] * P
     ok = np.zeros(P, dtype=bool)
     vanilla = None
-    if registration == "ransac" and use_symmetry and dev.type == "cuda" and \
+    if entry.name == "ransac" and use_symmetry and dev.type == "cuda" and \
             os.environ.get("CORSAIR_SPLIT_RANSAC", "1") != "0":
         v_offs = np.concatenate([[0], np.cumsum(prob_len)]).tolist()
         for t in (v_src, v_tgt):
@@ -417,19 +419,8 @@ def _sym_pose_batch(estimator, baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_
         src = corr_src[0] if len(corr_src) == 1 else torch.cat(corr_src)
         tgt = corr_tgt[0] if len(corr_tgt) == 1 else torch.cat(corr_tgt)
         offs = np.concatenate([[0], np.cumsum(prob_len)]).tolist()
-        if registration == "fgr":
-            r = B.fgr_batch(src, tgt, offs, max_corr, mu_floor=fgr_mu_floor, iteration_number=fgr_iterations,
-                            tuple_test=fgr_tuple_test, seed=seed)
-            T, inl, rmse, iters = r.T, r.inliers, r.rmse, r.iters
-        elif registration == "ransac_fm":
-            r = FM.ransac_fm_batch(src, tgt, offs, max_corr, m=fm_m, ransac_n=fm[0], edge_similarity=fm[1],
-                                   check_distance=True, iterations=fm[3], seed=seed)
-            T, inl, rmse, iters = r.T.to(torch.float32), r.inliers.contiguous(), r.rmse, r.n_valid.contiguous()
-        elif registration == "sc2":
-            r = S2.sc2_batch(src, tgt, offs, max_corr, sc2[0], n_seeds=sc2[1], k_consensus=sc2[2])
-            T, inl, rmse, iters = r.T.to(torch.float32), r.inliers.contiguous(), r.rmse, r.n_valid.contiguous()
-        else:
-            T, inl, rmse, iters = B.ransac_batch(src, tgt, offs, max_corr, 10, max_iter, confidence, seed)
+        T, inl, rmse, iters = E.run_stage4(entry, o, SimpleNamespace(
+            src=src, tgt=tgt, offs=offs, m=fm_m, max_corr=max_corr, max_iter=max_iter, confidence=confidence, seed=seed))
     else:
         parts = []
         if len(corr_src) > 1:
@@ -444,57 +435,6 @@ def _sym_pose_batch(estimator, baseF, xyz0, off0, posF, xyz1, off1, pos_syms, k_
     return finish(T, inl, iters, prob_pair, prob_cfg, ok, nonfinite)
 
 
-def check_fm_options(ransac_n, edge_similarity, mutual, iterations, who="sym_pose_batch"):
-    """The fm_* options of registration = "ransac_fm" as (ransac_n, edge_similarity, mutual, iterations), or ValueError."""
-    if isinstance(ransac_n, bool) or ransac_n not in (3, 4):
-        raise ValueError("%s: fm_ransac_n must be 3 or 4, got %r" % (who, ransac_n))
-    if isinstance(edge_similarity, bool) or not isinstance(edge_similarity, (int, float)) or \
-            not 0.0 <= edge_similarity <= 1.0:
-        raise ValueError("%s: fm_edge_similarity must lie in [0, 1] (0 = no edge checker), got %r" % (who, edge_similarity))
-    if not isinstance(mutual, (bool, np.bool_)):
-        raise ValueError("%s: fm_mutual must be a bool, got %r" % (who, mutual))
-    if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or not 1 <= iterations < 2 ** 31:
-        raise ValueError("%s: fm_iterations must be an integer in [1, 2^31), got %r" % (who, iterations))
-    return int(ransac_n), float(edge_similarity), bool(mutual), int(iterations)
-
-
-def check_sc2_options(compat_dist, seeds, k, max_corr, who="sym_pose_batch"):
-    """The sc2_* options of registration = "sc2" as (compat_dist, seeds, k), or ValueError.  compat_dist None = max_corr / 2
-    (untuned)."""
-    if compat_dist is None:
-        compat_dist = 0.5 * max_corr
-    if isinstance(compat_dist, bool) or not isinstance(compat_dist, (int, float, np.floating)) or \
-            not 0.0 < compat_dist < float("inf"):
-        raise ValueError("%s: sc2_compat_dist must be positive and finite, got %r" % (who, compat_dist))
-    if isinstance(seeds, bool) or not isinstance(seeds, (int, np.integer)) or not 0 <= seeds < 2 ** 31:
-        raise ValueError("%s: sc2_seeds must be an integer in [0, 2^31) (0 = every correspondence), got %r" % (who, seeds))
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 2 <= k <= 64:
-        raise ValueError("%s: sc2_k must be an integer in [2, 64], got %r" % (who, k))
-    return float(compat_dist), int(seeds), int(k)
-
-
-def check_ppf_options(scene_side, dist_step, ref_step, n_cand, who="sym_pose_batch"):
-    """The ppf_* options of registration = "ppf" as (scene_side, dist_step, ref_step, n_cand), or ValueError.  dist_step None
-    = 0.05 of each model's bounding-box diagonal (untuned)."""
-    if isinstance(scene_side, bool) or scene_side not in (0, 1):
-        raise ValueError("%s: ppf_scene_side must be 0 or 1, got %r" % (who, scene_side))
-    steps = dist_step if isinstance(dist_step, (list, tuple, np.ndarray)) else [dist_step]      # one per pair, or one for all
-    for v in steps:
-        if v is not None and (isinstance(v, bool) or not isinstance(v, (int, float, np.floating)) or
-                              not 0.0 < v < float("inf")):
-            raise ValueError("%s: ppf_dist_step must be positive and finite (None = 0.05 of the model's diagonal), got %r"
-                             % (who, dist_step))
-    if isinstance(ref_step, bool) or not isinstance(ref_step, (int, np.integer)) or not 1 <= ref_step < 2 ** 31:
-        raise ValueError("%s: ppf_ref_step must be an integer in [1, 2^31), got %r" % (who, ref_step))
-    if isinstance(n_cand, bool) or not isinstance(n_cand, (int, np.integer)) or not 1 <= n_cand <= 64:
-        raise ValueError("%s: ppf_n_cand must be an integer in [1, 64], got %r" % (who, n_cand))
-    if steps is not dist_step:
-        dist_step = None if dist_step is None else float(dist_step)
-    else:
-        dist_step = [float(v) for v in steps]
-    return int(scene_side), dist_step, int(ref_step), int(n_cand)
-
-
 def sym_pose_batch(*args, registration="ransac", fgr_mu_floor=0.025, fgr_iterations=64, fgr_tuple_test=True, **kwargs):
     """baseF f32 [N0,16], xyz0 f32 [N0,3] (query voxels of all pairs, segment p = off0[p]:off0[p+1]);
     posF/xyz1/off1 likewise for the CAD side; pos_syms: symmetry label per pair.
@@ -505,6 +445,7 @@ def sym_pose_batch(*args, registration="ransac", fgr_mu_floor=0.025, fgr_iterati
     query_anchors: the query-side draws (draw_anchors(n0[p], n_anchor, anchor_ids[p][0]) for every p)
     when the caller has already made them -- e.g. while the embedding kernels were still running; the
     ~1 ms of host work would otherwise sit between the 5-NN and the part-cut launches.
+
     icp_max_iter > 0: T_best of every pair is refined by point-to-point ICP (cs_icp_batch: source = the query's voxels,
     target = the CAD's voxels, the direction of stage 5; correspondence distance icp_max_dist, required then) and the
     result's T_icp / cd_icp / icp_* fields are filled; with the default 0 nothing is launched.
@@ -520,6 +461,16 @@ def sym_pose_batch(*args, registration="ransac", fgr_mu_floor=0.025, fgr_iterati
     out of scope and refused.  These two parameters stand BEFORE icp_kernel / icp_kernel_scale, which stay the last two: a
     caller that passed icp_kernel by position must pass it by keyword now (such a call fails on the scale bounds, it does
     not run with other settings).
+    icp_estimation = "gicp": the refinement is plane-to-plane Generalized ICP (cs_icp_gicp_batch), which models a local
+    plane on BOTH clouds: the CAD side works as for "plane" (normals1, else estimated here), the query side takes normals0
+    f32 [N0,3] in the query's own frame, else cs_estimate_normals over the query voxels with the same icp_normal_k /
+    icp_normal_radius.  gicp_epsilon in [2^-10, 1] is the covariance floor along the normal (Open3D's default; untuned here,
+    as is icp_normal_k for this estimation).  normals0 (default None) and gicp_epsilon (default 1e-3) are accepted by keyword
+    only, like the fgr_* options, and are taken out of **kwargs here.  icp_mrmse is filled too.  A robust icp_kernel or
+    icp_with_scaling with "gicp" is out of scope and refused.
+    Descriptors of another width (fpfh_features: 33 columns) register with use_symmetry=False; with use_symmetry the part
+    cut takes 16 or 32 columns and anything else is refused with ValueError before any launch.
+
     registration = "fgr" (keyword-only, like the fgr_* arguments): stage 4 sends the vanilla and every part-configuration
     list through ONE cs_fgr_batch call (Fast Global Registration: tuple test + graduated non-convexity, backend.fgr_batch)
     in place of both RANSAC calls and the helper-thread split; T_all, inliers and iters (= updates applied) are filled from
@@ -528,14 +479,7 @@ def sym_pose_batch(*args, registration="ransac", fgr_mu_floor=0.025, fgr_iterati
     the default "ransac" nothing of it is launched.  These four are accepted by keyword ONLY, behind every parameter
     above; `inspect.signature` keeps reporting the parameters above (`__signature__` below), whose order and end existing
     callers and tests rely on.
-    icp_estimation = "gicp": the refinement is plane-to-plane Generalized ICP (cs_icp_gicp_batch), which models a local
-    plane on BOTH clouds: the CAD side works as for "plane" (normals1, else estimated here), the query side takes normals0
-    f32 [N0,3] in the query's own frame, else cs_estimate_normals over the query voxels with the same icp_normal_k /
-    icp_normal_radius.  gicp_epsilon in [2^-10, 1] is the covariance floor along the normal (Open3D's default; untuned here,
-    as is icp_normal_k for this estimation).  normals0 (default None) and gicp_epsilon (default 1e-3) are accepted by keyword
-    only, like the fgr_* options, and are taken out of **kwargs here.  icp_mrmse is filled too.  A robust icp_kernel or icp_with_scaling with "gicp" is out of scope and refused.
-    Descriptors of another width (fpfh_features: 33 columns) register with use_symmetry=False; with use_symmetry the part
-    cut takes 16 or 32 columns and anything else is refused with ValueError before any launch.
+
     registration = "ransac_fm": Open3D's registration_ransac_based_on_feature_matching recipe, for hand-crafted
     descriptors.  Stage 1 runs cs_knn_feat at k = 1 in BOTH directions (k_nn is not used) and cs_corr_mutual keeps the mutual
     matches (a pair with fewer than 3 fm_ransac_n of them keeps all of its 1-NN matches); stage 4 is ONE cs_ransac_fm_batch
@@ -545,6 +489,7 @@ def sym_pose_batch(*args, registration="ransac", fgr_mu_floor=0.025, fgr_iterati
     fm_mutual = True, fm_iterations = 100000 are Open3D's defaults, untuned, no real scan measured; like normals0 they are
     accepted by keyword only and taken out of **kwargs here.  It needs use_symmetry=False (ValueError otherwise); max_iter
     and confidence are unused.  With "ransac" and "fgr" nothing of it is launched.
+
     registration = "sc2": the compatibility-graph estimator, for lists with an inlier share of a few per cent.
     Stage 1 is unchanged (the k_nn lists); stage 4 sends the SAME lists "fgr" gets -- the vanilla list and every part
     configuration, so use_symmetry=True works -- through ONE cs_sc2_batch call (sc2.sc2_batch): sc2_seeds rows of the largest
@@ -554,6 +499,7 @@ def sym_pose_batch(*args, registration="ransac", fgr_mu_floor=0.025, fgr_iterati
     sc2_k = 20 are UNTUNED, no real scan measured; keyword-only, taken out of **kwargs here.  A list of more than 32 768
     correspondences is refused by the library (a smaller k_nn).  max_iter, confidence and seed are unused.  With "ransac",
     "fgr" and "ransac_fm" nothing of it is launched.
+
     registration = "ppf": point-pair-feature voting, which reads NO descriptors: baseF and posF may be None,
     stages 1 - 3 are skipped and use_symmetry=True is refused.  Stage 4 is ONE cs_ppf_batch call (ppf.ppf_batch) on the
     voxels and their ORIENTED normals: the scene is side ppf_scene_side (0 = the query, 1 = the CAD side) and the model the
@@ -561,26 +507,19 @@ def sym_pose_batch(*args, registration="ransac", fgr_mu_floor=0.025, fgr_iterati
     icp_estimation), else they come from estimate_normals (icp_normal_k, icp_normal_radius) and orient_normals -- the scene
     towards ppf_view_points f64 [P,3] (the camera of a depth view) when given, else away from its centroid; the model away
     from its centroid.  ppf_dist_step = None: 0.05 of every model's bounding-box diagonal (one small download), else one
-    positive number for all pairs or a list of one per pair; every
-    ppf_ref_step-th scene row is a reference, the ppf_n_cand references with the most votes are verified within max_corr.
+    positive number for all pairs or a list of one per pair; every ppf_ref_step-th scene row is a reference, the ppf_n_cand
+    references with the most votes are verified within max_corr.
     T_ransac is the pose in this function's direction, xyz0 -> xyz1: the scene -> model pose when the scene is side 0, the
     inverse the library forms when it is side 1; inliers = the verification count, iters = the votes of the winner's peak.
     Stages 5 - 7 are what they are for the RANSAC.  ppf_scene_side = 0, ppf_dist_step = None, ppf_ref_step = 5, ppf_n_cand =
     16 are UNTUNED, no real scan measured; keyword-only, taken out of **kwargs here.  A model above 4 096 rows or a scene above
     16 384 is refused by the library (a coarser voxel).  k_nn, max_iter, confidence and seed are unused.  With the four other
     estimators nothing of it is launched."""
-    if registration not in ("ransac", "fgr", "ransac_fm", "sc2", "ppf"):
-        raise ValueError("sym_pose_batch: registration must be 'ransac', 'fgr', 'ransac_fm', 'sc2' or 'ppf', got %r"
-                         % (registration,))
-    normals0, gicp_epsilon = kwargs.pop("normals0", None), kwargs.pop("gicp_epsilon", 1e-3)
-    fm = check_fm_options(kwargs.pop("fm_ransac_n", 3), kwargs.pop("fm_edge_similarity", 0.9), kwargs.pop("fm_mutual", True),
-                          kwargs.pop("fm_iterations", 100000))
-    max_corr = kwargs["max_corr"] if "max_corr" in kwargs else (args[8] if len(args) > 8 else 0.20)
-    sc2 = check_sc2_options(kwargs.pop("sc2_compat_dist", None), kwargs.pop("sc2_seeds", 1024), kwargs.pop("sc2_k", 20),
-                            max_corr)
-    ppf = check_ppf_options(kwargs.pop("ppf_scene_side", 0), kwargs.pop("ppf_dist_step", None), kwargs.pop("ppf_ref_step", 5),
-                            kwargs.pop("ppf_n_cand", 16)) + (kwargs.pop("ppf_view_points", None),)
-    return _sym_pose_batch((registration, fgr_mu_floor, fgr_iterations, fgr_tuple_test, normals0, gicp_epsilon, fm, sc2, ppf),
+    entry = E.lookup(registration, "sym_pose_batch: registration")
+    options = dict(fgr_mu_floor=fgr_mu_floor, fgr_iterations=fgr_iterations, fgr_tuple_test=fgr_tuple_test)
+    for e in E.TABLE:
+        options.update((key, kwargs.pop(key, default)) for key, default in e.options.items() if key not in options)
+    return _sym_pose_batch(_KeywordOnly(entry, options, kwargs.pop("normals0", None), kwargs.pop("gicp_epsilon", 1e-3)),
                            *args, **kwargs)
 
 

@@ -12,6 +12,8 @@ import numpy as np
 import torch
 
 from . import backend as B
+from . import estimators as E
+from . import ppf as PPF
 from . import registration as R
 from .synth import euler2mat
 from .utils.eval_pose import eval_pose
@@ -111,15 +113,26 @@ class Config:
         if not (real(self.view_depth_tol) and self.view_depth_tol > 0.0):
             raise ValueError("Config.view_depth_tol must be finite and > 0 voxels, got %r" % (self.view_depth_tol,))
 
-    def check_registration(self):
-        if self.registration not in ("ransac", "fgr", "ransac_fm", "sc2", "ppf"):
-            raise ValueError("Config.registration must be 'ransac', 'fgr', 'ransac_fm', 'sc2' or 'ppf', got %r"
-                             % (self.registration,))
-        R.check_ppf_options(1, self.ppf_dist_step, self.ppf_ref_step, self.ppf_n_cand, "Config")
-        R.check_fm_options(self.fm_ransac_n, self.fm_edge_similarity, self.fm_mutual, self.fm_iterations, "Config")
+    def registration_options(self, entry=None, models=None, view_points=None):
+        """The estimator options of registration.sym_pose_batch from this Config's own units -- sc2_compat_dist in voxels, the
+        scene of "ppf" the posed copy (side 1) --, every estimator's, or `entry`'s alone; then ppf_dist_step, a fraction of the
+        diagonal here, is the length for each of `models` (the batch's whole clouds) and the scene looks at `view_points`."""
         if isinstance(self.sc2_compat_dist, bool) or not isinstance(self.sc2_compat_dist, (int, float, np.floating)):
             raise ValueError("Config.sc2_compat_dist must be positive and finite (voxels), got %r" % (self.sc2_compat_dist,))
-        R.check_sc2_options(self.sc2_compat_dist * self.voxel_size, self.sc2_seeds, self.sc2_k, self.max_corr, "Config")
+        step = self.ppf_dist_step
+        if entry is not None and entry.name == "ppf":
+            step = PPF.default_dist_step(models.origin, models.offsets, step)
+        kw = dict(fgr_mu_floor=self.fgr_mu_floor, fm_ransac_n=self.fm_ransac_n, fm_edge_similarity=self.fm_edge_similarity,
+                  fm_mutual=self.fm_mutual, fm_iterations=self.fm_iterations,
+                  sc2_compat_dist=self.sc2_compat_dist * self.voxel_size, sc2_seeds=self.sc2_seeds, sc2_k=self.sc2_k,
+                  ppf_scene_side=1, ppf_dist_step=step, ppf_ref_step=self.ppf_ref_step, ppf_n_cand=self.ppf_n_cand,
+                  ppf_view_points=view_points)
+        return kw if entry is None else {key: kw[key] for key in entry.options if key in kw}
+
+    def check_registration(self):
+        entry = E.lookup(self.registration, "Config.registration")
+        E.checked_options(entry, self.registration_options(), self.max_corr, "Config")
+        return entry
 
     def icp_distance(self):
         return self.icp_max_dist if self.icp_max_dist > 0 else 2.0 * self.voxel_size
@@ -338,17 +351,12 @@ def evaluate(pipe, clouds, cfg=None, pairs_per_batch=16, seed=None, force_gate=F
     cfg.check_partial_view()
     if cfg.features not in ("network", "fpfh"):
         raise ValueError("Config.features must be 'network' or 'fpfh', got %r" % (cfg.features,))
-    cfg.check_registration()
-    fm_on = cfg.registration == "ransac_fm"     # no symmetry hypotheses under it (the part configurations are out of scope)
-    fm_kw = dict(fm_ransac_n=cfg.fm_ransac_n, fm_edge_similarity=cfg.fm_edge_similarity, fm_mutual=cfg.fm_mutual,
-                 fm_iterations=cfg.fm_iterations) if fm_on else {}
-    if cfg.registration == "sc2":
-        fm_kw = dict(sc2_compat_dist=cfg.sc2_compat_dist * cfg.voxel_size, sc2_seeds=cfg.sc2_seeds, sc2_k=cfg.sc2_k)
-    ppf_on = cfg.registration == "ppf"          # no descriptors and no symmetry hypotheses under it
-    fpfh_on = cfg.features == "fpfh" and not ppf_on
+    entry = cfg.check_registration()
+    fpfh_on = cfg.features == "fpfh" and entry.descriptors
+    use_symmetry = not fpfh_on and entry.no_symmetry is None
     if fpfh_on:
         pipe = FpfhPipe("cuda" if pipe is None else pipe.device, cfg.fpfh_radius, cfg.fpfh_max_nn)
-    if ppf_on:
+    if not entry.descriptors:
         pipe = PpfPipe("cuda" if pipe is None else pipe.device)
     icp_on = cfg.icp_max_iter > 0
     scale_on = bool(cfg.icp_with_scaling)
@@ -385,23 +393,17 @@ def evaluate(pipe, clouds, cfg=None, pairs_per_batch=16, seed=None, force_gate=F
         base = es.gather(list(range(P)))
         posed = es.gather(list(range(P, 2 * P)))
         labels = [j[5] for j in chunk]
-        if ppf_on:      # the scene is the posed copy (side 1); the step is a fraction of each model's diagonal
-            from . import ppf as PPF
-
-            fm_kw = dict(ppf_scene_side=1, ppf_ref_step=cfg.ppf_ref_step, ppf_n_cand=cfg.ppf_n_cand,
-                         ppf_dist_step=PPF.default_dist_step(base.origin, base.offsets, cfg.ppf_dist_step),
-                         ppf_view_points=eyes if cfg.partial_view else None)
+        est_kw = cfg.registration_options(entry, base, eyes if cfg.partial_view else None)
         res = R.sym_pose_batch(base.F, base.origin, base.offsets, posed.F, posed.origin, posed.offsets,
                                labels, cfg.k_nn, cfg.max_corr, 0,
                                [(2 * (s + i), 2 * (s + i) + 1) for i in range(P)], 100,
-                               cfg.ransac_max_iter, cfg.ransac_confidence, not fpfh_on and not fm_on and not ppf_on, force_gate, None,
+                               cfg.ransac_max_iter, cfg.ransac_confidence, use_symmetry, force_gate, None,
                                cfg.icp_max_iter, cfg.icp_distance() if icp_on else None, cfg.icp_estimation,
                                cfg.icp_normal_k, None, cfg.normal_radius(), icp_with_scaling=scale_on,
                                icp_scale_bounds=tuple(cfg.icp_scale_bounds) if scale_on else None,
                                icp_kernel=cfg.icp_kernel,
                                icp_kernel_scale=cfg.icp_scale() if cfg.icp_kernel != "l2" else None,
-                               registration=cfg.registration, fgr_mu_floor=cfg.fgr_mu_floor,
-                               gicp_epsilon=cfg.gicp_epsilon, **fm_kw)
+                               registration=entry.name, gicp_epsilon=cfg.gicp_epsilon, **est_kw)
         Tb, Tr = res.T_best.cpu().numpy(), res.T_ransac.cpu().numpy()
         cdb, cdr = res.cd_best.cpu().numpy(), res.cd_ransac.cpu().numpy()
         for i, (mi, pi, _, _, pose, label, s_gt) in enumerate(chunk):
@@ -560,7 +562,7 @@ def build_parser():
                     help="the ICP refinement also fits an isotropic scale (needs --icp-iters > 0, no robust kernel)")
     ap.add_argument("--icp-scale-min", type=float, default=0.5, help="lower bound of the fitted scale, in (0, 1] (untuned)")
     ap.add_argument("--icp-scale-max", type=float, default=2.0, help="upper bound of the fitted scale, >= 1 (untuned)")
-    ap.add_argument("--registration", default="ransac", choices=["ransac", "fgr", "ransac_fm", "sc2", "ppf"],
+    ap.add_argument("--registration", default="ransac", choices=list(E.NAMES),
                     help="correspondence estimator: the reference's RANSAC, Fast Global Registration (cs_fgr_batch), "
                          "feature-matching RANSAC with a mutual filter and pose checkers (cs_ransac_fm_batch; no symmetry "
                          "hypotheses), the compatibility-graph estimator for low inlier shares (cs_sc2_batch), or "
@@ -629,7 +631,7 @@ def main(argv=None):
     if 0 < a.n_models < len(files):                                   # evaluation-shapenet.py:200-203
         files = sorted(rng.choice(files, a.n_models, replace=False).tolist())
     clouds = [np.load(os.path.join(a.data_dir, f)) for f in files]
-    if a.features == "fpfh" or a.registration == "ppf":
+    if a.features == "fpfh" or not E.lookup(a.registration, "--registration").descriptors:
         pipe = None
     else:
         if not a.ckpt:

@@ -251,6 +251,49 @@ def test_sym_pose_batch_with_sc2_equals_the_restatement(gpu):
         R.sym_pose_batch(bad, *args[1:], False, **kw)
 
 
+def test_sc2_compat_dist_none_is_half_of_max_corr_by_position_keyword_and_default(gpu):
+    """sc2_compat_dist = None means max_corr / 2 of THIS call's max_corr, whether that arrives by position, by keyword or not at
+    all: each call equals sc2.sc2_batch at that compat_dist on the rebuilt 5-NN lists, bit for bit."""
+    import inspect
+
+    from corsair_amd import backend as B, registration as R, sc2 as S2
+
+    q, off0, c, off1, Fq, Fc, _, _ = _real()
+    # two pairs of about a hundred query voxels (every 4th row of the builder's), the CAD sides whole
+    rows = [torch.arange(off0[p], off0[p + 1], 4, device=gpu) for p in range(2)]
+    offq = [0, len(rows[0]), len(rows[0]) + len(rows[1])]
+    rows = torch.cat(rows)
+    q, Fq, c, Fc, off1 = q[rows].contiguous(), Fq[rows].contiguous(), c[:off1[2]], Fc[:off1[2]], off1[:3]
+    assert off1[0] == 0 and Fq.shape[1] == 33 and all(90 <= offq[p + 1] - offq[p] <= 110 for p in range(2))
+    nn = B.knn_feat(Fq, offq, Fc, off1, 5).long()
+    src = q.repeat_interleave(5, 0)
+    tgt = torch.cat([c[off1[p] + nn[offq[p]:offq[p + 1]].reshape(-1)] for p in range(2)])
+    offs = [5 * v for v in offq]
+    assert any((offs[p + 1] - offs[p]) % 64 for p in range(2))
+
+    def direct(max_corr, compat_dist):
+        r = S2.sc2_batch(src, tgt, offs, max_corr, compat_dist, n_seeds=SC2_SEEDS, k_consensus=20)
+        return _bits(r.T.to(torch.float32)), _bits(r.inliers), _bits(r.n_valid)
+
+    def got(res):
+        assert res.n_problems == 2
+        return _bits(res.T_all), _bits(res.inliers), _bits(res.iters)
+
+    head = (Fq, q, offq, Fc, c, off1, [1, 1], 5)
+    kw = dict(registration="sc2", sc2_compat_dist=None, sc2_seeds=SC2_SEEDS, sc2_k=20)
+    default = inspect.signature(R.sym_pose_batch).parameters["max_corr"].default
+    other = 0.3
+    assert other != default
+    by_position = got(R.sym_pose_batch(*head, other, 0, None, 100, 100000, 0.999, False, **kw))
+    by_keyword = got(R.sym_pose_batch(*head, max_corr=other, use_symmetry=False, **kw))
+    by_default = got(R.sym_pose_batch(*head, use_symmetry=False, **kw))
+    assert by_position == by_keyword
+    assert by_position == direct(other, other / 2) and by_keyword == direct(other, other / 2)
+    assert by_default == direct(default, default / 2)
+    # the control: on these lists the threshold is felt, so a call that took half of ANOTHER max_corr would have been seen
+    assert direct(other, default / 2) != direct(other, other / 2)
+
+
 def test_defaults_launch_nothing_of_the_family(gpu):
     from corsair_amd import _lib, registration as R, shapenet_eval as SE
     from tests.test_gpu_real_clouds import _real_clouds
